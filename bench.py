@@ -7,17 +7,24 @@ batch of synthetic H&M-shaped users: two dropout views (p=0.2) of SASRecUserTowe
 all-time-steps LogQ in-batch loss (N ~ 153k valid positions at 8192 users, N x N implicit
 logits), DuoRec (InfoNCE + SupCon), backward, clip_grad_norm_(5.0), AdamW (item matrix
 unfrozen, lr x 0.05: the reference's epoch >= 2 steady state). Inputs are resident in HBM
-before timing. Secondary lines: batch 4096 (configs[1]), the fp32 parity mode, batch 32768 on
+before timing.
+
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps and prints
+the headline line (with the rooflines read from the timed steps' own HIP events).
+``--dump-outputs DIR`` also writes what the last timed step returned and left behind (losses,
+clipped gradients, post-AdamW parameters) as ``DIR/<name>.npy``. Everything else runs only with
+``--full``: the secondary lines -- batch 4096 (configs[1]), the fp32 parity mode, batch 32768 on
 one GPU, DeepFM (configs[2]), retrieve->rerank (configs[4] on one GPU), the item tower
-(configs[0] shape), HNM; the CPU oracle on the headline's own batch (cpu_baseline).
+(configs[0] shape), HNM --, the CPU oracle on the headline's own batch (cpu_baseline), the
+unloaded host cost of a step and the GPU clocks around the timed steps.
 
 Multi-GPU (one process per GPU, RCCL): ``--gpus N`` without torchrun's environment starts
 ``torch.distributed.run --nproc-per-node N`` as a child process (this parent never touches
 the GPU); under torchrun each rank holds 8192 users by default, so the global batch is
 8192 x N (weak scaling; N=4 is configs[3]'s global batch 32768, negatives all-gathered).
 ``--batch G`` fixes the global batch instead (strong scaling). Users are split by rank; see
-dist.py. At every N the JSON also carries ``strong_32768`` (configs[3]: the FIXED global batch
-32768 split over the N ranks; at N > 1 with rank 0's one-GPU run of the same batch in the same
+dist.py. With ``--full`` the JSON at every N also carries ``strong_32768`` (configs[3]: the FIXED
+global batch 32768 split over the N ranks; at N > 1 with rank 0's one-GPU run of the same batch in the same
 process and the speedup over it) and, at N > 1, ``retrieve_rerank_sharded`` (configs[4]: the 1M
 corpus sharded by item range, merged top-100 over RCCL, DeepFM rerank sharded by query).
 Prints ONE JSON line on rank 0.
@@ -53,6 +60,14 @@ def parse():
                          "`torch.distributed.run --nproc-per-node N` as a child and exits with its code")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the secondary lines, the CPU baselines with their agreement "
+                         "checks, the unloaded-host-cost steps and the GPU clock samples (each has its own --no-* "
+                         "switch). Without it only the headline is set up, warmed up, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline returned and left behind (losses, clipped "
+                         "gradients, post-AdamW parameters) as DIR/<name>.npy (float32 / float64, at most 64 MB in "
+                         "all: a fixed seeded sample of the arrays that would not fit)")
     ap.add_argument("--batch", type=int, default=None,
                     help="fixed global batch (users) for every N: strong scaling. Default: --batch-per-gpu x N")
     ap.add_argument("--batch-per-gpu", type=int, default=8192,
@@ -1017,11 +1032,14 @@ def bench_eval_forward(args, device, model, items, users=4096, iters=10):
 
 
 def train_bench(args, global_batch, steps, warmup, items, cfg, model, item_tower, opt, bucket, rank, world,
-                device, sample_clocks=False):
+                device, sample_clocks=False, unloaded=True, after_timed=None):
     """Times `steps` full train steps (after `warmup`) on this rank's slice of two seeded global
     batches of `global_batch` users (seeds args.seed + 100, + 101). -> dict with the max-over-ranks
     seconds, per-op HIP-event times, last losses, per-batch valid counts per rank, per-batch distinct
-    targets, packed tokens per view, host enqueue time per step and allocator retry counts."""
+    targets, packed tokens per view, host enqueue time per step and allocator retry counts.
+    unloaded: also run the untimed steps that price the host cost of a step on an idle GPU
+    ("host_unloaded"; None without them). after_timed(losses): called once the timed steps are done
+    and read out, before anything else touches the model (the --dump-outputs hook)."""
     from recsys_amd import dist as D
     from recsys_amd import ops, synth
     b_loc = global_batch // world
@@ -1105,6 +1123,25 @@ def train_bench(args, global_batch, steps, warmup, items, cfg, model, item_tower
     if pf is not None:
         pf.close()
     torch.cuda.synchronize()
+    if after_timed is not None:
+        after_timed(losses)
+    host_unloaded = (host_unloaded_steps(model, item_tower, log_q, batches, opt, cfg, lookup, bucket, world)
+                     if unloaded else None)
+    elapsed = torch.tensor([t1 - t0], device=device, dtype=torch.float64)
+    if world > 1:
+        D.all_reduce_(elapsed, op=torch.distributed.ReduceOp.MAX)
+    return {"elapsed": float(elapsed.item()), "kernel_times": kernel_times, "losses": losses, "n_glob": n_glob,
+            "n_dist": n_dist, "n_tok": n_tok, "host_enqueue_ms": round(1e3 * sum(enqueue) / max(len(enqueue), 1), 3),
+            "host_unloaded": host_unloaded, "alloc_retries": int(retries), "fwdg_kernel_ms": fwdg_kernel_ms,
+            "gather_events": gather_events,
+            "clocks": {"before_timed_steps": clk0, "after_timed_steps": clk1} if sample_clocks else None,
+            "users_local": b_loc}
+
+
+def host_unloaded_steps(model, item_tower, log_q, batches, opt, cfg, lookup, bucket, world):
+    """A few more (untimed) train steps on train_bench's batches, each started on an idle GPU.
+    -> {"index_inline_ms", "step_enqueue_ms", "total_ms"}: the host's time per step."""
+    from recsys_amd import dist as D
     # Host cost of one step with the GPU idle when it starts: inside the timed loop the host runs
     # ahead until the launch queue is full, after which every launch waits for the GPU, so the
     # timed loop's enqueue time approaches the GPU step time. Here each step starts from an
@@ -1149,15 +1186,36 @@ def train_bench(args, global_batch, steps, warmup, items, cfg, model, item_tower
     host_unloaded = {"index_inline_ms": round(1e3 * sum(u[0] for u in unloaded) / len(unloaded), 3),
                      "step_enqueue_ms": round(1e3 * sum(u[1] for u in unloaded) / len(unloaded), 3)}
     host_unloaded["total_ms"] = round(host_unloaded["index_inline_ms"] + host_unloaded["step_enqueue_ms"], 3)
-    elapsed = torch.tensor([t1 - t0], device=device, dtype=torch.float64)
-    if world > 1:
-        D.all_reduce_(elapsed, op=torch.distributed.ReduceOp.MAX)
-    return {"elapsed": float(elapsed.item()), "kernel_times": kernel_times, "losses": losses, "n_glob": n_glob,
-            "n_dist": n_dist, "n_tok": n_tok, "host_enqueue_ms": round(1e3 * sum(enqueue) / max(len(enqueue), 1), 3),
-            "host_unloaded": host_unloaded, "alloc_retries": int(retries), "fwdg_kernel_ms": fwdg_kernel_ms,
-            "gather_events": gather_events,
-            "clocks": {"before_timed_steps": clk0, "after_timed_steps": clk1} if sample_clocks else None,
-            "users_local": b_loc}
+    return host_unloaded
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all the .npy files together
+DUMP_SMALL_BYTES = 1 << 20      # arrays up to this size are always written whole
+
+
+def dump_outputs(path, model, item_matrix, losses):
+    """--dump-outputs: what a caller of the timed path (dist.contrastive_step_dp) holds after its last
+    timed step, as `path`/<name>.npy: losses.npy (total, main, cl; float64) and, for every user-tower
+    parameter by its state_dict name plus "item_matrix", param.<name>.npy (after AdamW) and
+    grad.<name>.npy (after clipping; zeros where the step left none), float32. If the arrays exceed
+    DUMP_BUDGET_BYTES, each one over DUMP_SMALL_BYTES is cut to the same fraction of its elements: a
+    sorted sample of its flattened index drawn with a fixed seed, so it is the same for every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"losses": np.array([float(x) for x in losses], dtype=np.float64)}
+    for n, p in list(model.named_parameters()) + [("item_matrix", item_matrix)]:
+        arrays["param." + n] = p.detach().float().cpu().numpy()
+        g = p.grad if p.grad is not None else torch.zeros_like(p)
+        arrays["grad." + n] = g.detach().float().cpu().numpy()
+    small = sum(a.nbytes for a in arrays.values() if a.nbytes <= DUMP_SMALL_BYTES)
+    large = sum(a.nbytes for a in arrays.values() if a.nbytes > DUMP_SMALL_BYTES)
+    # 128 B per file for the .npy header
+    frac = min(1.0, (DUMP_BUDGET_BYTES - small - 128 * len(arrays)) / max(large, 1))
+    for name, a in arrays.items():
+        if frac < 1.0 and a.nbytes > DUMP_SMALL_BYTES:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, int(frac * a.size), replace=False))
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def nce_roofline(args, tb, global_batch, rank, world, precision):
@@ -1366,8 +1424,12 @@ def main():
     bucket = D.GradBucket(list(model.parameters()) + list(item_tower.parameters()))
 
     # two distinct global batches, this rank's user slice of each, resident in HBM
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(losses):
+            dump_outputs(args.dump_outputs, model, item_tower.item_matrix.weight, losses)
     tb = train_bench(args, args.batch, args.steps, args.warmup, items, cfg, model, item_tower, opt, bucket, rank,
-                     world, device, sample_clocks=(rank == 0))
+                     world, device, sample_clocks=(args.full and rank == 0), unloaded=args.full, after_timed=dump)
     total_loss = float(tb["losses"][0].item())
     kt = {k: {"launches": n, "avg_ms": round(t / max(n, 1), 4)} for k, (n, t) in sorted(tb["kernel_times"].items())}
     result = {
@@ -1421,14 +1483,14 @@ def main():
         "build": N.build_info(),
     }
     del tb
-    if world == 1 and not args.no_batch4096 and args.batch != 4096:
+    if args.full and world == 1 and not args.no_batch4096 and args.batch != 4096:
         # BASELINE configs[1]: same step, same model and optimiser state, global batch 4096
         t4 = train_bench(args, 4096, args.steps4096, 3, items, cfg, model, item_tower, opt, bucket, rank, world,
                          device)
         result["secondary_batch4096"] = train_line(args, t4, 4096, args.steps4096, 3)
         del t4
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_fp32_line:
+    if args.full and world == 1 and not args.no_fp32_line:
         # the fp32 parity mode: loss products on the fp32 MFMA, token GEMMs / attention
         # in fp32, at the headline's batch
         prev = (ops.set_nce_precision("fp32"), ops.set_gemm_precision("fp32"), ops.mha_precision())
@@ -1443,7 +1505,7 @@ def main():
         ops.set_mha_precision(prev[2])
         del tf
         torch.cuda.empty_cache()
-    if not args.no_batch32768 and (world > 1 or args.batch != 32768):
+    if args.full and not args.no_batch32768 and (world > 1 or args.batch != 32768):
         # configs[3]: FIXED global batch 32,768 (all negatives in one pool), users split by rank
         # (32768 / N each): the strong-scaling line. At N = 1 it is the one-GPU baseline.
         t32 = train_bench(args, 32768, args.steps32768, 2, items, cfg, model, item_tower, opt, bucket, rank, world,
@@ -1477,12 +1539,12 @@ def main():
         result["strong_32768"] = line
         if world == 1:
             result["secondary_batch32768"] = line
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         result["secondary_eval_forward"] = bench_eval_forward(args, device, model, items)
         result["secondary_gather_1m"] = bench_gather_1m(device)
         torch.cuda.empty_cache()
-    cpu_lines = rank == 0 and world == 1 and not args.no_cpu_baseline
-    if rank == 0 and world == 1 and not args.no_deepfm:
+    cpu_lines = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if args.full and rank == 0 and world == 1 and not args.no_deepfm:
         torch.cuda.empty_cache()
         deepfm, result["secondary"], dfm_x = bench_deepfm(args, device)
         if not args.no_rerank:
@@ -1502,7 +1564,7 @@ def main():
             del dst
         del deepfm, dfm_x
         torch.cuda.empty_cache()
-    if world > 1 and not args.no_deepfm and not args.no_rerank:
+    if args.full and world > 1 and not args.no_deepfm and not args.no_rerank:
         # configs[4] on N GPUs: corpus sharded by item range, DeepFM rerank sharded by query
         from recsys_amd.temp_model.ranker_skelet import DeepFM
         torch.cuda.empty_cache()
@@ -1511,7 +1573,7 @@ def main():
         result["retrieve_rerank_sharded"], _ = bench_retrieve_rerank(args, device, deepfm, rank, world)
         del deepfm
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_item_tower:
+    if args.full and rank == 0 and world == 1 and not args.no_item_tower:
         result["secondary_item_tower"], (it_model, it_inputs) = bench_item_tower(args, device)
         if cpu_lines:
             line = result["secondary_item_tower"]
@@ -1523,7 +1585,7 @@ def main():
         result["secondary_hard_emphasis"] = bench_hard_emphasis(args, device)
         torch.cuda.empty_cache()
         result["secondary_hnm"] = bench_hnm(args, device)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu_lines:
         result["cpu_baseline"] = cpu_baseline(args, items, cfg, args.batch, args.seed + 100, device)
         result["gpu_over_cpu"] = round(result["value"] / result["cpu_baseline"]["value"], 1)
         if "secondary_batch4096" in result:       # configs[1]: the same step at 4,096 users
