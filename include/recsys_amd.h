@@ -439,6 +439,55 @@ int rsx_deepfm_fused_run(const int64_t* x, int64_t R, int F, const float* const*
 int rsx_deepfm_pack(const float* V, const float* W, int64_t vocab, float* packed, void* stream);
 int rsx_deepfm_fused_uses_packed(int F);
 
+/* ---- A16 training: one DeepFM step (Logloss backward + sparse Adam), csrc/deepfm_train.hip ----
+ * Trains the model of the forward above where the reference trains its ranker before use
+ * (RecommendationRanker.train, CatBoost Logloss, temp_model/ranker_skelet.py:114-137); deepctr-torch's
+ * own fit() cannot be run here: parity unpinned. Loss = binary cross-entropy on the logit, table rows
+ * updated with torch.optim.SparseAdam semantics, deterministic (no float atomics). embed_dim 16,
+ * last hidden layer 128, 1 <= F <= 64, R * F < 2^31. Call order (ops.deepfm_train_step):
+ * rsx_deepfm_train_keys: x [R, F] -> keys [R*F] = field << 40 | id, xs [R*F] = the ids with every id
+ *   outside [0, vocab[f]) (vocab: F host values) replaced by 0 (what the gathers read); such a pair's
+ *   key id is 2^40 - 1 (its contribution is summed but never applied) and *flag (device int32) = 1.
+ * The caller sorts the keys (stable) -> keys_sorted, perm.
+ * rsx_deepfm_train_segments: head [n] = 1 where a new key starts, inv [n] = inverse of perm.
+ * rsx_deepfm_train_starts: head_cum [n] = inclusive scan of head -> seg_start [U + 1] (last = n) and
+ *   *nseg = U, the number of distinct (field, id), all on the device.
+ * rsx_deepfm_train_head: h2 [R, H = 128], wo [128], lin [R] (rsx_deepfm_embed's lin_out), bias [1]
+ *   (device, nullable: added to every logit, so the step never reads out.bias on the host), y [R] ->
+ *   logit [R], g [R] = (sigmoid(logit) - y) * (mean ? 1/R : 1), dh2 [R, 128] = g wo [h2 > 0],
+ *   loss[0] (double) = sum or mean of max(z,0) - z y + log1p(exp(-|z|)), dbias[0] = sum g,
+ *   dwo [128] = sum_r g_r h2_r; per-64-row partials in ws, added in a fixed two-level order.
+ * rsx_relu_bwd: dx[i] = h[i] > 0 ? dx[i] : 0 (n floats, n % 4 == 0).
+ * rsx_deepfm_train_contrib: emb [R, F*16] (the forward's), dE [R, ldE] (DNN input gradient) ->
+ *   gV [n, 16] / gW [n] at each pair's sorted position inv[r*F + f]:
+ *   g_r (sum_f' v_rf' - v_rf) + dE[r, f*16 ..] and g_r.
+ * rsx_deepfm_train_sparse_adam: sums gV / gW per distinct key in sorted order (segments longer than
+ *   128 as 64-contribution partials in ws, added in order) and applies, for step count `step` (>= 1,
+ *   shared by all tables), m += (1-b1)(g-m); v += (1-b2)(g^2-v);
+ *   p -= lr sqrt(1-b2^step)/(1-b1^step) m / (sqrt(v) + eps) to row id of V[f] [vocab_f, 16],
+ *   W[f] [vocab_f] and their moments; no other row is read or written. out_dV [n, 16] / out_dW [n]
+ *   (nullable, together) receive the summed gradient of segment u at row u (the values the update
+ *   consumed; segments in keys_sorted[seg_start[u]] order). */
+int rsx_deepfm_train_keys(const int64_t* x, int64_t R, int F, const int64_t* vocab, int64_t* keys, int64_t* xs,
+                          int* flag, void* stream);
+int rsx_deepfm_train_segments(const int64_t* keys_sorted, const int64_t* perm, int64_t n, int* head, int* inv,
+                              void* stream);
+int rsx_deepfm_train_starts(const int* head_cum, int64_t n, int* seg_start, int* nseg, void* stream);
+int64_t rsx_deepfm_train_head_workspace_bytes(int64_t R);
+int rsx_deepfm_train_head(const float* h2, int64_t H, const float* wo, const float* lin, const float* bias,
+                          const float* y, int64_t R, int mean, float* logit, float* g, float* dh2, void* ws,
+                          int64_t ws_bytes, double* loss, float* dbias, float* dwo, void* stream);
+int rsx_relu_bwd(float* dx, const float* h, int64_t n, void* stream);
+int rsx_deepfm_train_contrib(const float* emb, const float* g, const float* dE, int64_t ldE, const int* inv,
+                             int64_t R, int F, int E, float* gV, float* gW, void* stream);
+int64_t rsx_deepfm_train_sparse_workspace_bytes(int64_t n);
+int rsx_deepfm_train_sparse_adam(const int64_t* keys_sorted, const int* head_cum, const int* seg_start,
+                                 const int* nseg, int64_t n, int F, int E, const int64_t* vocab, const float* gV,
+                                 const float* gW, float* const* V, float* const* W, float* const* mV,
+                                 float* const* vV, float* const* mW, float* const* vW, double lr, double beta1,
+                                 double beta2, double eps, int64_t step, void* ws, int64_t ws_bytes, float* out_dV,
+                                 float* out_dW, void* stream);
+
 /* ---- §8f #3: GDCN reranker batch (utils/data_preprocessing/feature_processor.py:144-195) ----
  * rsx_reranker_batch replaces RerankerDataset.__getitem__ (:156-181) + reranker_collate_fn
  * (:184-191) for a batch of (user row uidx[b], item row iidx[b]) on device tables:

@@ -22,9 +22,10 @@ c_p = ctypes.c_void_p
 c_i64 = ctypes.c_int64
 c_i = ctypes.c_int
 c_f = ctypes.c_float
+c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 5  # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 6  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -136,6 +137,17 @@ _SIGS = {
     "rsx_hnm_mine": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, ctypes.c_size_t, c_p, c_p, c_p, c_p]),
     "rsx_hnm_workspace_bytes": (c_i64, [c_i64]),
     "rsx_hnm_max_rows": (c_i64, []),
+    "rsx_deepfm_train_keys": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_deepfm_train_segments": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_deepfm_train_starts": (c_i, [c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_deepfm_train_head_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_deepfm_train_head": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p,
+                                    c_p]),
+    "rsx_relu_bwd": (c_i, [c_p, c_p, c_i64, c_p]),
+    "rsx_deepfm_train_contrib": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_i, c_i, c_p, c_p, c_p]),
+    "rsx_deepfm_train_sparse_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_deepfm_train_sparse_adam": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                           c_p, c_p, c_d, c_d, c_d, c_d, c_i64, c_p, c_i64, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -1335,8 +1335,9 @@ def _dx(dy, w, tag="tok_linear_dx"):
     return gemm_x3(dy, w.t(), tag=tag)
 
 
-def linear_wgrad(dy, x, weight_shape, need_bias, tag="linear_wgrad"):
-    """(dW, db) of y = x W^T + b over the token axis: split-K over tokens, deterministic."""
+def linear_wgrad(dy, x, weight_shape, need_bias, tag="linear_wgrad", precision=None):
+    """(dW, db) of y = x W^T + b over the token axis: split-K over tokens, deterministic.
+    precision: "fp32" | "bf16x3" (default: the module's GEMM precision)."""
     N.ensure_device(dy)
     dy = _c(dy)
     x = _c(x)
@@ -1347,7 +1348,7 @@ def linear_wgrad(dy, x, weight_shape, need_bias, tag="linear_wgrad"):
     ws = torch.empty(nws, device=dy.device, dtype=torch.float32)
     dw = torch.empty(n, k, device=dy.device, dtype=torch.float32)
     db = torch.empty(n, device=dy.device, dtype=torch.float32) if need_bias else None
-    fn = N.lib().rsx_linear_wgrad_x3 if _gemm_precision == "bf16x3" else N.lib().rsx_linear_wgrad
+    fn = N.lib().rsx_linear_wgrad_x3 if (precision or _gemm_precision) == "bf16x3" else N.lib().rsx_linear_wgrad
     with timed(tag):
         rc = fn(N.ptr(dy), dy.stride(0), N.ptr(x), x.stride(0), t, n, k, N.ptr(dw), dw.stride(0), N.ptr(db), 0,
                 N.ptr(ws), nws, N.stream())
@@ -1904,6 +1905,172 @@ def deepfm_forward(x, emb_tables, lin_tables, out_bias, dnn_weights, dnn_biases,
                                         N.ptr(prob), N.stream())
     N.check(rc, "linear_dot_fwd")
     return logit, prob
+
+
+# ----------------------------------------------------------------------------------------
+# A16 training: one DeepFM step (csrc/deepfm_train.hip)
+_DEEPFM_ID_BITS = 40
+_DEEPFM_DROPPED = (1 << _DEEPFM_ID_BITS) - 1
+
+
+def deepfm_train_supported(F, embed_dim, hidden):
+    """None when the training kernels cover the shape, else the text naming the limit."""
+    if embed_dim != 16:
+        return f"DeepFM training needs embed_dim 16 (got {embed_dim})"
+    if tuple(hidden) != (256, 128):
+        return f"DeepFM training needs dnn_hidden_units (256, 128) (got {tuple(hidden)})"
+    if not 1 <= F <= 64:
+        return f"DeepFM training needs 1 <= F <= 64 fields (got {F})"
+    return None
+
+
+class DeepFMStep:
+    """What deepfm_train_step returns: loss (0-d float64 device tensor), logit [R], dense (the
+    gradients of W1, b1, W2, b2, w_out [128], out.bias [1]) and, with return_grads, sparse_grads()."""
+
+    def __init__(self, loss, logit, dense, sparse):
+        self.loss, self.logit, self.dense, self._sparse = loss, logit, dense, sparse
+
+    def sparse_grads(self):
+        """Per field (distinct ids [U_f], dV [U_f, 16], dW [U_f], U_f as a device scalar): the summed
+        rows the sparse update consumed (one host read: the number of distinct (field, id))."""
+        if self._sparse is None:
+            raise RuntimeError("deepfm_train_step was called without return_grads=True")
+        keys_sorted, seg_start, nseg, oV, oW, F = self._sparse[:6]
+        U = int(nseg.item())
+        keys = keys_sorted[seg_start[:U].long()]
+        fld, ids = keys >> _DEEPFM_ID_BITS, keys & _DEEPFM_DROPPED
+        out = []
+        for f in range(F):
+            sel = (fld == f) & (ids != _DEEPFM_DROPPED)
+            out.append((ids[sel], oV[:U][sel], oW[:U][sel], sel.sum()))
+        return out
+
+    def contributions(self):
+        """(keys [R*F] sorted, field << 40 | id, gV [R*F, 16], gW [R*F]): the per-(row, field) gradient
+        rows in the order the coalescing pass summed them (id 2^40 - 1: a dropped contribution)."""
+        if self._sparse is None:
+            raise RuntimeError("deepfm_train_step was called without return_grads=True")
+        return self._sparse[0], self._sparse[6], self._sparse[7]
+
+
+def deepfm_train_step(x, y, emb_tables, lin_tables, emb_m, emb_v, lin_m, lin_v, out_bias, dnn_weights, dnn_biases,
+                      w_out, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, reduction="mean", return_grads=False,
+                      id_flag=None, cache=None):
+    """One DeepFM training step over raw tensors, no host synchronisation: forward keeping the
+    activations, Logloss (binary cross-entropy on the logit, reduction "mean" | "sum"), backward, and
+    the torch.optim.SparseAdam update of the rows of emb_tables [vocab_f, 16] / lin_tables [vocab_f]
+    that occur in x [R, F] (moments emb_m / emb_v / lin_m / lin_v, same shapes; `step` = the shared
+    step count after this step's increment, >= 1), applied in place. The dense gradients are returned
+    for the caller's Adam (DeepFMStep.dense: W1, b1, W2, b2, w_out, out.bias). out_bias: the [1]
+    device tensor. id_flag: device int32 [1] set to 1 when an id lies outside its field's vocab (such
+    an id reads row 0 and its contribution is dropped). cache: a dict the caller keeps for the
+    zero-padded image of W1's columns (refreshed here every step)."""
+    N.ensure_device(x)
+    if reduction not in ("mean", "sum"):
+        raise ValueError('reduction must be "mean" or "sum"')
+    x = _c(x.to(torch.int64))
+    R, F = x.shape
+    why = deepfm_train_supported(F, emb_tables[0].shape[1], [w.shape[0] for w in dnn_weights])
+    if why:
+        raise NotImplementedError(why)
+    if len(emb_tables) != F or len(lin_tables) != F or tuple(dnn_weights[0].shape) != (256, F * 16):
+        raise ValueError(f"deepfm: {len(emb_tables)} embedding / {len(lin_tables)} linear tables for {F} fields")
+    if R < 1:
+        raise ValueError("deepfm_train_step needs at least one row")
+    groups = (emb_tables, lin_tables, emb_m, emb_v, lin_m, lin_v)
+    for grp in groups:
+        for t, e in zip(grp, emb_tables):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape[0] != e.shape[0] or t.device != x.device:
+                raise ValueError("deepfm_train_step: tables and moments must be contiguous fp32 of their field's vocab")
+    dev, lib, st = x.device, N.lib(), N.stream()
+    n = R * F
+    y = _c(y.to(device=dev, dtype=torch.float32).reshape(-1))
+    if y.numel() != R:
+        raise ValueError(f"deepfm_train_step: {y.numel()} labels for {R} rows")
+    w1, w2 = _c(dnn_weights[0]), _c(dnn_weights[1])
+    b1, b2 = _c(dnn_biases[0]), _c(dnn_biases[1])
+    wo = _c(w_out.reshape(-1))
+    vocab = N.i64_array([t.shape[0] for t in emb_tables])
+    flag = id_flag if id_flag is not None else torch.zeros(1, device=dev, dtype=torch.int32)
+
+    # 1. keys, checked ids, the sorted index (segment heads and counts stay on the device)
+    keys = torch.empty(n, device=dev, dtype=torch.int64)
+    xs = torch.empty(n, device=dev, dtype=torch.int64)
+    with timed("deepfm_train/index"):
+        N.check(lib.rsx_deepfm_train_keys(N.ptr(x), R, F, vocab, N.ptr(keys), N.ptr(xs), N.ptr(flag), st),
+                "deepfm_train_keys")
+        keys_sorted, perm = torch.sort(keys, stable=True)
+        head = torch.empty(n, device=dev, dtype=torch.int32)
+        inv = torch.empty(n, device=dev, dtype=torch.int32)
+        N.check(lib.rsx_deepfm_train_segments(N.ptr(keys_sorted), N.ptr(perm), n, N.ptr(head), N.ptr(inv), st),
+                "deepfm_train_segments")
+        cum = torch.cumsum(head, 0, dtype=torch.int32)
+        seg_start = torch.empty(n + 1, device=dev, dtype=torch.int32)
+        nseg = torch.empty(1, device=dev, dtype=torch.int32)
+        N.check(lib.rsx_deepfm_train_starts(N.ptr(cum), n, N.ptr(seg_start), N.ptr(nseg), st), "deepfm_train_starts")
+
+    # 2. forward keeping emb, h1, h2; the head
+    V, W = N.ptr_array(emb_tables), N.ptr_array(lin_tables)
+    emb = torch.empty(R, F * 16, device=dev, dtype=torch.float32)
+    lin = torch.empty(R, device=dev, dtype=torch.float32)
+    with timed("deepfm_train/forward"):
+        N.check(lib.rsx_deepfm_embed(N.ptr(xs), R, F, 16, V, W, 0.0, N.ptr(emb), N.ptr(lin), st), "deepfm_embed")
+        h1 = linear(emb, w1, b1, ACT_RELU)
+        h2 = linear(h1, w2, b2, ACT_RELU)
+        logit = torch.empty(R, device=dev, dtype=torch.float32)
+        g = torch.empty(R, device=dev, dtype=torch.float32)
+        dh2 = torch.empty(R, 128, device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float64)
+        dbias = torch.empty(1, device=dev, dtype=torch.float32)
+        dwo = torch.empty(128, device=dev, dtype=torch.float32)
+        nws = lib.rsx_deepfm_train_head_workspace_bytes(R)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        N.check(lib.rsx_deepfm_train_head(N.ptr(h2), 128, N.ptr(wo), N.ptr(lin), N.ptr(_c(out_bias)), N.ptr(y), R,
+                                          1 if reduction == "mean" else 0, N.ptr(logit), N.ptr(g), N.ptr(dh2),
+                                          N.ptr(ws), nws, N.ptr(loss), N.ptr(dbias), N.ptr(dwo), st),
+                "deepfm_train_head")
+
+    # 3. dense backward on the existing GEMMs
+    with timed("deepfm_train/dense_bwd"):
+        # exact fp32 products for the dense weight gradients
+        dw2, db2 = linear_wgrad(dh2, h1, w2.shape, True, tag="deepfm_train/dw2", precision="fp32")
+        dh1 = gemm_x3_tn(dh2, w2, tag="deepfm_train/dh1")
+        N.check(lib.rsx_relu_bwd(N.ptr(dh1), N.ptr(h1), dh1.numel(), st), "relu_bwd")
+        dw1, db1 = linear_wgrad(dh1, emb, w1.shape, True, tag="deepfm_train/dw1", precision="fp32")
+        K = F * 16
+        if K % 128 == 0:
+            w1p = w1
+        else:
+            Kp = (K + 127) // 128 * 128
+            w1p = cache.get("w1_padded") if cache is not None else None
+            if w1p is None or w1p.shape != (256, Kp) or w1p.device != dev:
+                w1p = torch.zeros(256, Kp, device=dev, dtype=torch.float32)
+                if cache is not None:
+                    cache["w1_padded"] = w1p
+            w1p[:, :K].copy_(w1)
+        dE = gemm_x3_tn(dh1, w1p, tag="deepfm_train/dE")
+
+    # 4./5. contribution rows at their sorted positions, then coalesce + SparseAdam per distinct id
+    gV = torch.empty(n, 16, device=dev, dtype=torch.float32)
+    gW = torch.empty(n, device=dev, dtype=torch.float32)
+    oV = torch.empty(n, 16, device=dev, dtype=torch.float32) if return_grads else None
+    oW = torch.empty(n, device=dev, dtype=torch.float32) if return_grads else None
+    nws = lib.rsx_deepfm_train_sparse_workspace_bytes(n)
+    ws2 = torch.empty(nws, device=dev, dtype=torch.uint8)
+    with timed("deepfm_train/sparse"):
+        N.check(lib.rsx_deepfm_train_contrib(N.ptr(emb), N.ptr(g), N.ptr(dE), dE.stride(0), N.ptr(inv), R, F, 16,
+                                             N.ptr(gV), N.ptr(gW), st), "deepfm_train_contrib")
+        N.check(lib.rsx_deepfm_train_sparse_adam(
+            N.ptr(keys_sorted), N.ptr(cum), N.ptr(seg_start), N.ptr(nseg), n, F, 16, vocab, N.ptr(gV), N.ptr(gW), V, W,
+            N.ptr_array(emb_m), N.ptr_array(emb_v), N.ptr_array(lin_m), N.ptr_array(lin_v), float(lr), float(betas[0]),
+            float(betas[1]), float(eps), int(step), N.ptr(ws2), nws, N.ptr(oV), N.ptr(oW), st), "deepfm_train_sparse_adam")
+    # the kernels wrote through raw pointers: advance the version counters the inference caches key on
+    for grp in groups:
+        for t in grp:
+            torch.autograd.graph.increment_version(t)
+    sparse = (keys_sorted, seg_start, nseg, oV, oW, F, gV, gW) if return_grads else None
+    return DeepFMStep(loss, logit, [dw1, db1, dw2, db2, dwo, dbias], sparse)
 
 
 # ----------------------------------------------------------------------------------------

@@ -7,7 +7,9 @@ Reference (temp_model/ranker_skelet.py):
     lives here as `DeepFM`, with a CatBoost-compatible `predict_proba` wrapper.
   * CrossNet :239-272 and RankingModel (DCN-V2) :274-357 — dead code in the reference, kept
     as a second neural reranker with the same parameter names and init.
-Compute: DeepFM forward = rsx_deepfm_embed + rsx_linear_fwd + rsx_linear_dot_fwd; retrieval
+Compute: DeepFM forward = rsx_deepfm_embed + rsx_linear_fwd + rsx_linear_dot_fwd; DeepFM training
+(the reference trains its ranker before use, RecommendationRanker.train :114-137, Logloss) =
+ops.deepfm_train_step (DeepFM.make_trainer / DeepFM.fit); retrieval
 (user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk).
 """
 from __future__ import annotations
@@ -95,6 +97,107 @@ class DeepFM(nn.Module):
             X = torch.as_tensor(np.asarray(X), dtype=torch.int64)
         dev = next(self.parameters()).device
         return self.forward_logits(X.to(dev))[1].cpu().numpy()
+
+    def make_trainer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, reduction="mean", max_grad_norm=None):
+        """A DeepFMTrainer over this model's parameters (Logloss; SparseAdam semantics on the tables,
+        Adam on the dense parameters). Raises NotImplementedError for shapes the training kernels do
+        not cover (embed_dim 16, dnn_hidden_units (256, 128), 1 <= F <= 64)."""
+        return DeepFMTrainer(self, lr, betas, eps, reduction, max_grad_norm)
+
+    def fit(self, X, y, batch_size, epochs=1, shuffle=True, seed=0, **trainer_kw):
+        """Train on X [R, F] int64 / y [R] in {0, 1} (the slot of RecommendationRanker.train :114-137)
+        for `epochs` passes in batches of batch_size (the last short batch included; row order
+        shuffled per epoch from `seed`). Returns the per-epoch mean row losses (one host read per
+        epoch). trainer_kw: make_trainer's arguments."""
+        tr = self.make_trainer(**trainer_kw)
+        dev = next(self.parameters()).device
+        X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X).to(dev, torch.int64)
+        y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(dev, torch.float32).reshape(-1)
+        R = X.shape[0]
+        gen = torch.Generator().manual_seed(seed)
+        means = []
+        for _ in range(epochs):
+            order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
+            total = torch.zeros((), device=dev, dtype=torch.float64)
+            for s in range(0, R, batch_size):
+                e = min(R, s + batch_size)
+                xb, yb = (X[s:e], y[s:e]) if order is None else (X[order[s:e]], y[order[s:e]])
+                loss = tr.step(xb, yb)
+                total += loss * (e - s) if tr.reduction == "mean" else loss
+            means.append(float((total / R).item()))
+        tr.check_ids()
+        return means
+
+
+class DeepFMTrainer:
+    """One-call training steps for a DeepFM on the device (ops.deepfm_train_step): step(X, y) runs the
+    forward, the Logloss, the backward, the sparse Adam update of the table rows that occur in X
+    (torch.optim.SparseAdam semantics, one step count shared by all tables) and Adam on the dense
+    parameters (a torch.optim.AdamW(weight_decay=0) stepped by ops.clip_adamw_step, with
+    clip_grad_norm_ over the dense parameters when max_grad_norm is given), without a host
+    synchronisation. Embedding L2 regularisation is not applied."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, reduction="mean", max_grad_norm=None):
+        hidden = [m.out_features for m in model.dnn.linears]
+        why = ops.deepfm_train_supported(len(model.field_names), model.embed_dim, hidden)
+        if why:
+            raise NotImplementedError(why)
+        if reduction not in ("mean", "sum"):
+            raise ValueError('reduction must be "mean" or "sum"')
+        self.model = model
+        self.lr, self.betas, self.eps, self.reduction, self.max_grad_norm = lr, tuple(betas), eps, reduction, max_grad_norm
+        emb, lin, ws, bs, wo = model._param_lists()
+        self.emb_m = [torch.zeros_like(t) for t in emb]
+        self.emb_v = [torch.zeros_like(t) for t in emb]
+        self.lin_m = [torch.zeros_like(t) for t in lin]
+        self.lin_v = [torch.zeros_like(t) for t in lin]
+        self.step_count = 0
+        self.dense = [ws[0], bs[0], ws[1], bs[1], wo, model.out.bias]
+        self.optimizer = torch.optim.AdamW(self.dense, lr=lr, betas=self.betas, eps=eps, weight_decay=0)
+        self._guard = ops.IdRangeGuard("DeepFM training ids")
+        self._cache = {}
+
+    @torch.no_grad()
+    def step(self, X, y):
+        """One step on the batch X [R, F] int64, y [R]; returns the loss (0-d device tensor)."""
+        m = self.model
+        emb, lin, ws, bs, wo = m._param_lists()
+        flag = torch.zeros(1, device=emb[0].device, dtype=torch.int32)
+        self.step_count += 1
+        res = ops.deepfm_train_step(X, y, emb, lin, self.emb_m, self.emb_v, self.lin_m, self.lin_v, m.out.bias, ws, bs,
+                                    wo, self.step_count, self.lr, self.betas, self.eps, self.reduction,
+                                    id_flag=flag, cache=self._cache)
+        self._guard.watch(flag)
+        for p, g in zip(self.dense, res.dense):
+            p.grad = g.view(p.shape)
+        clip = self.dense if self.max_grad_norm is not None else []
+        if ops.clip_adamw_step(self.optimizer, clip, self.max_grad_norm or 0.0) is None:
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(self.dense, self.max_grad_norm)
+            self.optimizer.step()
+        for p in self.dense:
+            p.grad = None
+            torch.autograd.graph.increment_version(p)   # rsx_clip_adamw writes through raw pointers
+        return res.loss
+
+    def check_ids(self):
+        """Raise IndexError if any batch so far held an id outside its field's vocabulary."""
+        self._guard.check()
+
+    def state_dict(self):
+        """A snapshot (copies): the shared step count, the tables' moments, the dense optimizer's state."""
+        import copy
+        sd = {name: [t.clone() for t in getattr(self, name)] for name in ("emb_m", "emb_v", "lin_m", "lin_v")}
+        sd["step"] = self.step_count
+        sd["dense"] = copy.deepcopy(self.optimizer.state_dict())
+        return sd
+
+    def load_state_dict(self, sd):
+        self.step_count = int(sd["step"])
+        for name in ("emb_m", "emb_v", "lin_m", "lin_v"):
+            for dst, src in zip(getattr(self, name), sd[name]):
+                dst.copy_(src)
+        self.optimizer.load_state_dict(sd["dense"])
 
 
 class FeatureEngineer:
