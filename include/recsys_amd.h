@@ -488,6 +488,27 @@ int rsx_deepfm_train_sparse_adam(const int64_t* keys_sorted, const int* head_cum
                                  double beta2, double eps, int64_t step, void* ws, int64_t ws_bytes, float* out_dV,
                                  float* out_dW, void* stream);
 
+/* ---- A16 validation: exact AUC and Logloss of a binary ranker, csrc/binary_eval.hip ---------------
+ * The metrics the reference's ranker is trained against (CatBoostClassifier(eval_metric='AUC',
+ * early_stopping_rounds=50), temp_model/ranker_skelet.py:98-108; eval_set / use_best_model, :123-135),
+ * for R scored rows with one host read. logit [R], y [R] fp32 ->
+ *   counts [3] (int64) = P = #{y == 1}, N = #{y == 0}, U2 = sum over positive rows i of
+ *     #{negative j : z_j < z_i} + #{negative j : z_j <= z_i}: twice the Mann-Whitney U statistic with
+ *     ties at one half, an exact integer (U2 <= 2 P N < 2^61); AUC = U2 / (2 P N), formed by the
+ *     caller in double. Scores compare as reals: -0.0 and +0.0 tie.
+ *   loss_sum [1] (double) = sum_r max(z,0) - z y + log1p(exp(-|z|)) (rsx_deepfm_train_head's row
+ *     expression), from per-workgroup partials added in a fixed order: the same bits every run.
+ *   flag [1] (int32): bit 0 = a logit is NaN or +-inf, bit 1 = a label is neither 0 nor 1; with a flag
+ *     set the other outputs are unspecified (every access stays in bounds).
+ * Key pass, radix sort of (key, label), three scans over 2048-row tiles; no step walks a tie group, so
+ * one group spanning all R rows costs what distinct scores cost. Integer sums and one fixed-order
+ * double sum: deterministic, no float atomics. 1 <= R < 2^31 (rsx_binary_eval_workspace_bytes
+ * returns -1 outside it); ws 16-byte aligned, counts / loss_sum 8-byte aligned; the outputs need no
+ * zeroing by the caller. */
+int64_t rsx_binary_eval_workspace_bytes(int64_t R);
+int rsx_binary_eval(const float* logit, const float* y, int64_t R, void* ws, int64_t ws_bytes, int64_t* counts,
+                    double* loss_sum, int* flag, void* stream);
+
 /* ---- §8f #3: GDCN reranker batch (utils/data_preprocessing/feature_processor.py:144-195) ----
  * rsx_reranker_batch replaces RerankerDataset.__getitem__ (:156-181) + reranker_collate_fn
  * (:184-191) for a batch of (user row uidx[b], item row iidx[b]) on device tables:

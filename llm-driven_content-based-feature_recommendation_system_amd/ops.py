@@ -2074,6 +2074,71 @@ def deepfm_train_step(x, y, emb_tables, lin_tables, emb_m, emb_v, lin_m, lin_v, 
 
 
 # ----------------------------------------------------------------------------------------
+# A16 validation: exact AUC and Logloss of a binary ranker (csrc/binary_eval.hip)
+_BINARY_EVAL_WS = {}   # R -> workspace bytes (a host-side size computation, the same for every call)
+
+
+class BinaryEval:
+    """What binary_eval returns. The outputs stay on the device until result(): counts (int64 [3]:
+    positives P, negatives N, U2 = twice the tie-aware Mann-Whitney U), loss_sum (float64 [1]) and
+    flag (int32 [1]) are views of one 40-byte allocation, fetched by one copy."""
+
+    def __init__(self, buf, rows):
+        self._buf, self.rows = buf, rows
+        self.counts, self.loss_sum, self.flag = buf[:3], buf[3:4].view(torch.float64), buf[4:5].view(torch.int32)[:1]
+
+    def result(self, also=None):
+        """The one host read: {"auc", "logloss", "positives", "negatives"}. auc = U2 / (2 P N) in
+        double (NaN when one class is absent), logloss = loss_sum / R. ValueError for a non-finite
+        logit or a label that is neither 0 nor 1. also: a float64 device tensor fetched by the same
+        copy (its bits untouched); the return value is then (the dict, its values as a list)."""
+        if also is None:
+            host = self._buf.cpu()
+        else:
+            host = torch.cat([self._buf, also.detach().reshape(-1).view(torch.int64)]).cpu()
+        out = self._result(host)
+        return out if also is None else (out, host[5:].view(torch.float64).tolist())
+
+    def _result(self, host):
+        flag = int(host[4:5].view(torch.int32)[0])
+        if flag:
+            why = [w for b, w in ((1, "a logit is NaN or infinite"), (2, "a label is neither 0 nor 1")) if flag & b]
+            raise ValueError("binary_eval: " + " and ".join(why))
+        p, n, u2 = (int(v) for v in host[:3])
+        loss = float(host[3:4].view(torch.float64)[0])
+        return {"auc": u2 / (2 * p * n) if p and n else float("nan"), "logloss": loss / self.rows,
+                "positives": p, "negatives": n}
+
+
+def binary_eval(logit, y):
+    """Exact tie-aware ROC-AUC and Logloss of the scores logit [R] (fp32, device) against the labels
+    y [R] (any dtype, values 0 / 1), without a host synchronisation: rsx_binary_eval on the current
+    stream. Returns a BinaryEval; its result() does the one host read."""
+    N.ensure_device(logit)
+    if logit.dtype != torch.float32:
+        raise ValueError(f"binary_eval: logits must be float32 (got {logit.dtype})")
+    z = _c(logit.detach().reshape(-1))
+    R = z.numel()
+    if R < 1:
+        raise ValueError("binary_eval needs at least one row")
+    y = _c(torch.as_tensor(y).detach().to(device=z.device, dtype=torch.float32).reshape(-1))
+    if y.numel() != R:
+        raise ValueError(f"binary_eval: {y.numel()} labels for {R} scores")
+    lib = N.lib()
+    nws = _BINARY_EVAL_WS.get(R)
+    if nws is None:
+        nws = _BINARY_EVAL_WS[R] = int(lib.rsx_binary_eval_workspace_bytes(R))
+        if nws < 0:
+            N.check(1, "binary_eval_workspace_bytes")
+    ws = torch.empty(nws, device=z.device, dtype=torch.uint8)
+    out = BinaryEval(torch.empty(5, device=z.device, dtype=torch.int64), R)
+    with timed("binary_eval"):
+        N.check(lib.rsx_binary_eval(N.ptr(z), N.ptr(y), R, N.ptr(ws), nws, N.ptr(out.counts), N.ptr(out.loss_sum),
+                                    N.ptr(out.flag), N.stream()), "binary_eval")
+    return out
+
+
+# ----------------------------------------------------------------------------------------
 # §8f #3: GDCN reranker batch (utils/data_preprocessing/feature_processor.py:144-195)
 def reranker_batch(uidx, iidx, tables, max_len=50):
     """(dense [B,12] f32, cat [B], seq_ids [B,L], seq_mask [B,L], target [B]) of the batch rows

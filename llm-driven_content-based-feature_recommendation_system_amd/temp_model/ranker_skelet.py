@@ -9,7 +9,9 @@ Reference (temp_model/ranker_skelet.py):
     as a second neural reranker with the same parameter names and init.
 Compute: DeepFM forward = rsx_deepfm_embed + rsx_linear_fwd + rsx_linear_dot_fwd; DeepFM training
 (the reference trains its ranker before use, RecommendationRanker.train :114-137, Logloss) =
-ops.deepfm_train_step (DeepFM.make_trainer / DeepFM.fit); retrieval
+ops.deepfm_train_step (DeepFM.make_trainer / DeepFM.fit); its validation (eval_set, eval_metric='AUC',
+early_stopping_rounds, use_best_model, :98-108 and :123-135) = DeepFM.evaluate / DeepFM.fit(eval_set=...)
+over ops.binary_eval (rsx_binary_eval: exact tie-aware AUC and Logloss on the device); retrieval
 (user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk).
 """
 from __future__ import annotations
@@ -104,18 +106,128 @@ class DeepFM(nn.Module):
         not cover (embed_dim 16, dnn_hidden_units (256, 128), 1 <= F <= 64)."""
         return DeepFMTrainer(self, lr, betas, eps, reduction, max_grad_norm)
 
-    def fit(self, X, y, batch_size, epochs=1, shuffle=True, seed=0, **trainer_kw):
-        """Train on X [R, F] int64 / y [R] in {0, 1} (the slot of RecommendationRanker.train :114-137)
-        for `epochs` passes in batches of batch_size (the last short batch included; row order
-        shuffled per epoch from `seed`). Returns the per-epoch mean row losses (one host read per
-        epoch). trainer_kw: make_trainer's arguments."""
-        tr = self.make_trainer(**trainer_kw)
+    def _rows_on_device(self, X, y):
         dev = next(self.parameters()).device
         X = torch.as_tensor(np.asarray(X) if not torch.is_tensor(X) else X).to(dev, torch.int64)
         y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(dev, torch.float32).reshape(-1)
+        if X.dim() != 2 or y.numel() != X.shape[0]:
+            raise ValueError(f"need X [R, F] and y [R] (got {tuple(X.shape)} and {y.numel()} labels)")
+        return X, y
+
+    @torch.no_grad()
+    def _evaluate_on_device(self, X, y, batch_size):
+        """forward_logits over X in batches into one [R] buffer, then one ops.binary_eval: nothing is
+        read back here (forward_logits itself re-reads out.bias, 4 bytes, once after the weights changed)."""
+        R = X.shape[0]
+        logits = torch.empty(R, device=X.device, dtype=torch.float32)
+        for s in range(0, R, batch_size):
+            logits[s:s + batch_size].copy_(self.forward_logits(X[s:s + batch_size])[0])
+        return ops.binary_eval(logits, y)
+
+    def evaluate(self, X, y, batch_size=65536):
+        """{"Logloss", "AUC"} of the model on X [R, F] / y [R] in {0, 1} (tensors or array-likes): the
+        fused inference kernel over batches of batch_size (the last short batch included) and one
+        device-side evaluation (ops.binary_eval: exact tie-aware ROC-AUC, mean Logloss), one host
+        read. AUC is NaN when y holds a single class."""
+        X, y = self._rows_on_device(X, y)
+        res = self._evaluate_on_device(X, y, int(batch_size)).result()
+        return {"Logloss": res["logloss"], "AUC": res["auc"]}
+
+    def fit(self, X, y, batch_size, epochs=1, shuffle=True, seed=0, eval_set=None, eval_metric="AUC",
+            early_stopping_rounds=None, use_best_model=None, eval_every=None, **trainer_kw):
+        """Train on X [R, F] int64 / y [R] in {0, 1} (the slot of RecommendationRanker.train :114-137)
+        for `epochs` passes in batches of batch_size (the last short batch included; row order
+        shuffled per epoch from `seed`). Returns the completed epochs' mean row losses (one host read
+        per epoch). trainer_kw: make_trainer's arguments.
+
+        eval_set=(X_val, y_val) adds the reference's validation (CatBoost's eval_set / eval_metric /
+        early_stopping_rounds / use_best_model, :98-108, :123-135): the validation rows are moved to
+        the device once and evaluated (as evaluate does) after every epoch, or after every
+        eval_every-th training step instead when eval_every is given. eval_metric "AUC" (larger is
+        better) or "Logloss" (smaller is better) picks the best evaluation: only a strictly better
+        one replaces it. early_stopping_rounds=k stops after k consecutive evaluations without an
+        improvement. use_best_model (default True with an eval_set) leaves the model with the
+        parameters of the best evaluation: they are copied into a device snapshot at every
+        improvement (allocated once, overwritten in place, on the stream) and copied back into the
+        same Parameter objects at the end, so the trainer and the inference caches see them. The
+        snapshot doubles the model's footprint (2.5 GB more at configuration 3: 39 fields of 10^6
+        rows); the optimizer moments are not snapshotted. One host read per evaluation (the metrics,
+        with the epoch's mean loss in the same copy) besides forward_logits' 4-byte refresh of
+        out.bias; none per step. Records evals_result_ = {"learn": {"Logloss": [...]}, "validation":
+        {"Logloss": [...], "AUC": [...]}} (learn: the mean training loss since the previous
+        evaluation), best_iteration_ (0-based index of the best evaluation) and best_score_ =
+        {"validation": {"Logloss", "AUC"}} at it. ValueError before the first step for an unknown
+        eval_metric, validation labels outside {0, 1}, or a single class with eval_metric "AUC"."""
+        if eval_metric not in ("AUC", "Logloss"):
+            raise ValueError(f'eval_metric must be "AUC" or "Logloss" (got {eval_metric!r})')
+        if eval_set is None:
+            if early_stopping_rounds is not None or eval_every is not None or use_best_model:
+                raise ValueError("early_stopping_rounds, eval_every and use_best_model need an eval_set")
+        else:
+            if early_stopping_rounds is not None and early_stopping_rounds < 1:
+                raise ValueError("early_stopping_rounds must be >= 1")
+            if eval_every is not None and eval_every < 1:
+                raise ValueError("eval_every must be >= 1")
+            Xv, yv = self._rows_on_device(*eval_set)
+            n_pos, n_neg = (int(v) for v in torch.stack([(yv == 1).sum(), (yv == 0).sum()]).tolist())
+            if n_pos + n_neg != yv.numel():
+                raise ValueError("eval_set labels must be 0 or 1")
+            if eval_metric == "AUC" and (n_pos == 0 or n_neg == 0):
+                raise ValueError('eval_set holds a single class: eval_metric="AUC" is undefined')
+            if use_best_model is None:
+                use_best_model = True
+        tr = self.make_trainer(**trainer_kw)
+        X, y = self._rows_on_device(X, y)
+        dev = X.device
         R = X.shape[0]
         gen = torch.Generator().manual_seed(seed)
         means = []
+        if eval_set is None:
+            for _ in range(epochs):
+                order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
+                total = torch.zeros((), device=dev, dtype=torch.float64)
+                for s in range(0, R, batch_size):
+                    e = min(R, s + batch_size)
+                    xb, yb = (X[s:e], y[s:e]) if order is None else (X[order[s:e]], y[order[s:e]])
+                    loss = tr.step(xb, yb)
+                    total += loss * (e - s) if tr.reduction == "mean" else loss
+                means.append(float((total / R).item()))
+            tr.check_ids()
+            return means
+
+        self.evals_result_ = {"learn": {"Logloss": []}, "validation": {"Logloss": [], "AUC": []}}
+        self.best_iteration_, self.best_score_ = None, None
+        params = list(self.parameters())
+        snapshot, stale = None, False      # stale: steps were taken since the snapshot was written
+        state = {"best": None, "since": 0}
+        val_bs = 65536
+
+        def evaluate_now(learn_mean):
+            """One evaluation; learn_mean: 0-d float64 device tensor. True when training should stop."""
+            nonlocal snapshot, stale
+            res, (learn,) = self._evaluate_on_device(Xv, yv, val_bs).result(also=learn_mean)
+            ev = self.evals_result_
+            ev["learn"]["Logloss"].append(learn)
+            ev["validation"]["Logloss"].append(res["logloss"])
+            ev["validation"]["AUC"].append(res["auc"])
+            score = res["auc"] if eval_metric == "AUC" else -res["logloss"]
+            if state["best"] is None or score > state["best"]:
+                state["best"], state["since"] = score, 0
+                self.best_iteration_ = len(ev["validation"]["AUC"]) - 1
+                self.best_score_ = {"validation": {"Logloss": res["logloss"], "AUC": res["auc"]}}
+                if use_best_model:
+                    with torch.no_grad():
+                        if snapshot is None:
+                            snapshot = [torch.empty_like(p) for p in params]
+                        torch._foreach_copy_(snapshot, params)
+                    stale = False
+            else:
+                state["since"] += 1
+            return early_stopping_rounds is not None and state["since"] >= early_stopping_rounds
+
+        stop, gstep = False, 0
+        since_total = torch.zeros((), device=dev, dtype=torch.float64)
+        since_rows = 0
         for _ in range(epochs):
             order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
             total = torch.zeros((), device=dev, dtype=torch.float64)
@@ -123,9 +235,38 @@ class DeepFM(nn.Module):
                 e = min(R, s + batch_size)
                 xb, yb = (X[s:e], y[s:e]) if order is None else (X[order[s:e]], y[order[s:e]])
                 loss = tr.step(xb, yb)
-                total += loss * (e - s) if tr.reduction == "mean" else loss
-            means.append(float((total / R).item()))
+                row_loss = loss * (e - s) if tr.reduction == "mean" else loss
+                total += row_loss
+                stale = True
+                gstep += 1
+                if eval_every is not None:
+                    since_total += row_loss
+                    since_rows += e - s
+                    if gstep % eval_every == 0:
+                        stop = evaluate_now(since_total / since_rows)
+                        since_total.zero_()
+                        since_rows = 0
+                        if stop:
+                            break
+            if stop:
+                break       # the epoch was cut short: no mean for it
+            mean = total / R
+            if eval_every is None:
+                stop = evaluate_now(mean)
+                means.append(self.evals_result_["learn"]["Logloss"][-1])
+                if stop:
+                    break
+            else:
+                means.append(float(mean.item()))
         tr.check_ids()
+        if use_best_model and snapshot is not None and stale:
+            before = [p._version for p in params]
+            with torch.no_grad():
+                for p, s in zip(params, snapshot):
+                    p.copy_(s)
+            for p, v in zip(params, before):     # the caches of forward_logits key on the version counters
+                if p._version == v:
+                    torch.autograd.graph.increment_version(p)
         return means
 
 
@@ -135,7 +276,10 @@ class DeepFMTrainer:
     (torch.optim.SparseAdam semantics, one step count shared by all tables) and Adam on the dense
     parameters (a torch.optim.AdamW(weight_decay=0) stepped by ops.clip_adamw_step, with
     clip_grad_norm_ over the dense parameters when max_grad_norm is given), without a host
-    synchronisation. Embedding L2 regularisation is not applied."""
+    synchronisation. Embedding L2 regularisation is not applied. The trainer holds no validation
+    logic: DeepFM.fit(eval_set=...) evaluates between steps (DeepFM.evaluate), stops early and
+    restores the best parameters into the same Parameter objects this trainer updates; the moments
+    (state_dict) stay those of the last step taken."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, reduction="mean", max_grad_norm=None):
         hidden = [m.out_features for m in model.dnn.linears]
