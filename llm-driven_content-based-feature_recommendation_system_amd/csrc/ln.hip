@@ -374,12 +374,13 @@ __global__ __launch_bounds__(256) void dropout_bwd_k(const float* __restrict__ d
 RSX_API int rsx_ln_fwd(const float* x, const float* res, float p_drop, uint64_t seed, const float* w, const float* b,
                        float eps, int act, int64_t T, int64_t D, float* sum_out, float* y, float* mean, float* rstd,
                        void* stream) {
-  RSX_ARG(x && (y || (res && sum_out)), "null tensor (y may be null only for the add-only form)");
   RSX_ARG(D == 64 || D == 128 || D == 256 || D == 512 || D == 768 || D == 1024 || D == 2048,
           "D must be 64, 128, 256, 512, 768, 1024 or 2048");
   RSX_ARG(act == 0 || act == 2, "act must be 0 (none) or 2 (gelu)");
   RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
-  if (T == 0) return 0;
+  RSX_ARG(T >= 0, "negative row count");
+  if (T == 0) return 0;  // before the pointer check: an empty tensor's data pointer is null
+  RSX_ARG(x && (y || (res && sum_out)), "null tensor (y may be null only for the add-only form)");
   FArgs a;
   a.x = x; a.res = res; a.w = w; a.b = b; a.sum_out = sum_out; a.y = y; a.mean = mean; a.rstd = rstd;
   a.T = T; a.eps = eps; a.act = act;
@@ -415,10 +416,11 @@ RSX_API int64_t rsx_ln_bwd_workspace_floats(int64_t T, int64_t D) {
 RSX_API int rsx_ln_bwd(const float* s, const float* mean, const float* rstd, const float* w, const float* b, int act,
                        const float* dy, const float* ds_in, float p_drop, uint64_t seed, int64_t T, int64_t D,
                        float* ds_out, float* dres, float* dw, float* db, float* ws, int64_t ws_floats, void* stream) {
-  RSX_ARG(s && mean && rstd && dy, "null tensor");
   RSX_ARG(D == 64 || D == 128 || D == 256 || D == 512 || D == 768 || D == 1024 || D == 2048,
           "D must be 64, 128, 256, 512, 768, 1024 or 2048");
   RSX_ARG(act == 0 || act == 2, "act must be 0 (none) or 2 (gelu)");
+  RSX_ARG(T >= 0, "negative row count");
+  RSX_ARG(T == 0 || (s && mean && rstd && dy), "null tensor");  // T = 0: empty tensors have null pointers
   RSX_ARG(!(dw || db) || (ws && ws_floats >= rsx_ln_bwd_workspace_floats(T, D)), "workspace too small");
   RSX_ARG(act == 0 || w, "gelu needs the LayerNorm weight");
   hipStream_t st = (hipStream_t)stream;
@@ -455,10 +457,11 @@ RSX_API int rsx_ln_bwd(const float* s, const float* mean, const float* rstd, con
 // `x + F.dropout(f, p)` after the encoder's last layer (v1_refine_usertower.py:343-352).
 RSX_API int rsx_dropout_bwd(const float* ds, int64_t T, int64_t D, float p_drop, uint64_t seed, float* dres,
                             void* stream) {
-  RSX_ARG(ds && dres, "null tensor");
   RSX_ARG(D % 4 == 0, "D must be a multiple of 4");
   RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  RSX_ARG(T >= 0, "negative row count");
   if (T == 0) return 0;
+  RSX_ARG(ds && dres, "null tensor");
   const int64_t n4 = T * D / 4;
   int64_t blocks = (n4 + 255) / 256;
   if (blocks > 8192) blocks = 8192;

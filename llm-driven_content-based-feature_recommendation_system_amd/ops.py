@@ -59,6 +59,66 @@ def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
 
 
+# Host-side argument checks of the raw-pointer wrappers: attribute comparisons only (no tensor
+# op, no synchronisation), run before ensure_device so that a bad call never reaches a kernel.
+# TypeError: wrong dtype; ValueError: wrong shape / length; RuntimeError: wrong device.
+_INT_DTYPES = (torch.int32, torch.int16, torch.int8, torch.uint8)
+
+
+def _f32(fn, name, t, ref=None):
+    """t is an fp32 tensor (on ref's device)."""
+    if t.dtype != torch.float32:
+        raise TypeError(f"{fn}: {name} must be float32, got {t.dtype}")
+    if ref is not None and t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+
+
+def _f32_vec(fn, name, t, n, ref):
+    """t (None allowed) is an fp32 tensor of n elements on ref's device."""
+    if t is None:
+        return
+    _f32(fn, name, t, ref)
+    if t.numel() != n:
+        raise ValueError(f"{fn}: {name} has {t.numel()} elements, expected {n}")
+
+
+def _index(fn, name, t, ref=None, n=None):
+    """t as the int64 index tensor the kernels read (another integer dtype is converted;
+    anything else refused), on ref's device, of n elements."""
+    if t.dtype != torch.int64:
+        if t.dtype not in _INT_DTYPES:
+            raise TypeError(f"{fn}: {name} must be an integer tensor, got {t.dtype}")
+        t = t.long()
+    if ref is not None and t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+    if n is not None and t.numel() != n:
+        raise ValueError(f"{fn}: {name} has {t.numel()} elements, expected {n}")
+    return t
+
+
+def _rows2(fn, name, t):
+    """t is an fp32 [rows, D] matrix; returns D."""
+    _f32(fn, name, t)
+    if t.dim() != 2:
+        raise ValueError(f"{fn}: {name} must be 2-D, got shape {tuple(t.shape)}")
+    return t.shape[1]
+
+
+def _ln_args(fn, x, res, weight, bias):
+    """LayerNorm family: x (and res, same shape / dtype / device) fp32 rows of D = last dim,
+    weight / bias of D elements on x's device."""
+    _f32(fn, "x", x)
+    if x.dim() < 1:
+        raise ValueError(f"{fn}: x must have a last dimension")
+    if res is not None:
+        _f32(fn, "res", res, x)
+        if res.shape != x.shape:
+            raise ValueError(f"{fn}: res has shape {tuple(res.shape)}, x {tuple(x.shape)}")
+    D = x.shape[-1]
+    _f32_vec(fn, "weight", weight, D, x)
+    _f32_vec(fn, "bias", bias, D, x)
+
+
 def _tensor_key(ts):
     """Cache key of derived device images: the tensor OBJECTS (held, so their storage cannot be
     recycled under a stale key), their storage pointers and in-place version counters."""
@@ -398,7 +458,9 @@ class _GatherRows(torch.autograd.Function):
         for s in ctx.src_shape[:-1]:
             rows *= s
         if idx is None:
-            dsrc = torch.empty(rows, D, device=dy.device, dtype=torch.float32)
+            # plain store of every row but skip_idx, which the kernel leaves untouched: zero it
+            alloc = torch.zeros if 0 <= skip_idx < rows else torch.empty
+            dsrc = alloc(rows, D, device=dy.device, dtype=torch.float32)
             mode = 0
         else:
             dsrc = torch.zeros(rows, D, device=dy.device, dtype=torch.float32)
@@ -411,11 +473,14 @@ class _GatherRows(torch.autograd.Function):
 
 def gather_rows(src, idx=None, normalize=False, eps=1e-12, unique=False, skip_idx=-1):
     """out[r] = src.view(-1, D)[idx[r]] (idx None => all rows), optionally L2-normalised. The kernel
-    reads fp32 rows: another floating dtype is cast first (autograd-aware), anything else refused."""
+    reads fp32 rows: another floating dtype is cast first (autograd-aware), anything else refused;
+    idx: int64 on src's device (another integer dtype is converted, anything else refused)."""
     if src.dtype != torch.float32:
         if not src.is_floating_point():
             raise TypeError(f"gather_rows: floating-point rows expected, got {src.dtype}")
         src = src.float()
+    if idx is not None:
+        idx = _index("gather_rows", "idx", idx, src)
     return _GatherRows.apply(src, idx, bool(normalize), float(eps), bool(unique), int(skip_idx))
 
 
@@ -465,7 +530,8 @@ class _GatherRowsMulti(torch.autograd.Function):
 def gather_rows_multi(src, specs, eps=1e-12):
     """[gather_rows(src, idx, normalize=nz, unique=True) for idx, nz in specs] as one autograd
     node (one source gradient buffer; each idx must be duplicate-free)."""
-    idxs = [i for i, _ in specs]
+    _rows2("gather_rows_multi", "src", src)
+    idxs = [_index("gather_rows_multi", f"idx[{k}]", i, src) for k, (i, _) in enumerate(specs)]
     norms = [bool(nz) for _, nz in specs]
     return list(_GatherRowsMulti.apply(src, norms, float(eps), *idxs))
 
@@ -807,6 +873,13 @@ def loss_combine(s_main, s_un, s_sup, cnt, n, b, lambda_sup, lambda_cl):
     """(objective, detached [total, main, cl]) of the contrastive step from device scalars:
     s_main / n + lambda_cl * (s_un / b + lambda_sup * s_sup / max(cnt, 1)); s_main / s_sup may be
     None (no valid step / lambda_sup = 0), cnt is not differentiated."""
+    if s_un is None:
+        raise ValueError("loss_combine: s_un is required")
+    _f32_vec("loss_combine", "s_un", s_un, 1, None)
+    _f32_vec("loss_combine", "s_main", s_main, 1, s_un)
+    _f32_vec("loss_combine", "s_sup", s_sup, 1, s_un)
+    _f32_vec("loss_combine", "cnt", cnt, 1, s_un)
+    N.ensure_device(s_un)
     consts = (1.0 / float(n) if n else 0.0, 1.0 / float(b), float(lambda_sup), float(lambda_cl))
     cnt = None if cnt is None else _c(cnt.detach().reshape(1))
     return _LossCombine.apply(s_main, s_un, s_sup, cnt, consts)
@@ -1186,6 +1259,7 @@ class _LayerNormPass(torch.autograd.Function):
 
 def layer_norm_pass(x, weight, bias, eps=1e-5):
     """(x, LayerNorm(x)) with the residual gradient of x folded into the LayerNorm backward."""
+    _ln_args("layer_norm_pass", x, None, weight, bias)
     shp = x.shape
     x2, y = _LayerNormPass.apply(_c(x.reshape(-1, shp[-1])), weight, bias, float(eps))
     return x2.reshape(shp), y.reshape(shp)
@@ -1220,6 +1294,7 @@ class _AddDropout(torch.autograd.Function):
 
 def add_dropout(x, res, p_drop=0.0, training=True):
     """x + F.dropout(res, p_drop, training) as one kernel (counter-hash mask; p = 0 in eval)."""
+    _ln_args("add_dropout", x, res, None, None)
     p = float(p_drop) if training else 0.0
     shp = x.shape
     seed = next_seed() if p > 0 else 0
@@ -1229,6 +1304,7 @@ def add_dropout(x, res, p_drop=0.0, training=True):
 
 def layer_norm(x, weight, bias, eps=1e-5, act=0):
     """act(LayerNorm(x)) over the last dim (act 0 none / ACT_GELU_ERF)."""
+    _ln_args("layer_norm", x, None, weight, bias)
     shp = x.shape
     y = _LayerNorm.apply(x.reshape(-1, shp[-1]), weight, bias, float(eps), int(act))
     return y.reshape(shp)
@@ -1238,6 +1314,9 @@ def layer_norm(x, weight, bias, eps=1e-5, act=0):
 def add_layer_norm_infer(x, res, weight, bias, eps=1e-5):
     """LayerNorm(x + res) forward only (no statistics saved, the sum not written): inference,
     e.g. BERT's post-norm residuals in item_tower.bert_cls_packed. Hidden up to 1024."""
+    _ln_args("add_layer_norm_infer", x, res, weight, bias)
+    if x.dim() != 2:
+        raise ValueError(f"add_layer_norm_infer: x must be [T, D], got shape {tuple(x.shape)}")
     N.ensure_device(x)
     x = _c(x)
     res = _c(res)
@@ -1252,6 +1331,7 @@ def add_layer_norm_infer(x, res, weight, bias, eps=1e-5):
 def add_layer_norm(x, res, weight, bias, eps=1e-5, p_drop=0.0):
     """(s, LayerNorm(s)) with s = x + dropout(res): the residual add of a norm_first encoder
     layer fused with the next LayerNorm."""
+    _ln_args("add_layer_norm", x, res, weight, bias)
     shp = x.shape
     seed = next_seed() if p_drop > 0 else 0
     s, y = _AddLayerNorm.apply(x.reshape(-1, shp[-1]), res.reshape(-1, shp[-1]), weight, bias, float(eps),
@@ -1718,8 +1798,10 @@ def tower_packed(model, packed, pv_tok, tok_ids, s_g, profile, p_drop, params=No
 def bert_embed_packed(embeddings, ids, tok_pos):
     """BertEmbeddings(input_ids) rows for a packed token list (ids [T], positions tok_pos [T],
     token type 0) via rsx_embed3_ln; dropout as the module's (active only in training)."""
-    N.ensure_device(ids)
     word = embeddings.word_embeddings.weight
+    ids = _index("bert_embed_packed", "ids", ids, word)
+    tok_pos = _index("bert_embed_packed", "tok_pos", tok_pos, word, ids.numel())
+    N.ensure_device(ids)
     D = word.shape[1]
     T = ids.numel()
     out = torch.empty(T, D, device=ids.device, dtype=torch.float32)
@@ -1758,6 +1840,12 @@ class _SegmentMean(torch.autograd.Function):
 def segment_mean(x, seg, tok_seg, counts):
     """x [T, D] packed rows (segments contiguous), seg [U+1] int64 offsets, tok_seg [T] int64,
     counts [U] float -> [U, D] means (a zero-count segment gives 0, as the clamp does)."""
+    _rows2("segment_mean", "x", x)
+    if counts.device != x.device:
+        raise RuntimeError(f"segment_mean: counts is on {counts.device}, expected {x.device}")
+    seg = _index("segment_mean", "seg", seg, x, counts.numel() + 1)
+    tok_seg = _index("segment_mean", "tok_seg", tok_seg, x, x.shape[0])
+    N.ensure_device(x)
     inv = 1.0 / torch.clamp(counts, min=1e-9)
     return _SegmentMean.apply(_c(x), _c(seg), _c(tok_seg), inv.float())
 
@@ -1766,6 +1854,13 @@ def segment_mean(x, seg, tok_seg, counts):
 # DCN-V2 reranker: cross network + the cross half of the final head
 def crossnet(x, kernels, biases, w_head=None, want_x=False):
     """rsx_crossnet: x [B, D] -> (x_L [B, D] or None, head_part [B] = x_L . w_head or None)."""
+    D = _rows2("crossnet", "x", x)
+    if len(kernels) != len(biases):
+        raise ValueError(f"crossnet: {len(kernels)} kernels but {len(biases)} biases")
+    for l, (k, b) in enumerate(zip(kernels, biases)):
+        _f32_vec("crossnet", f"kernels[{l}]", k, D, x)
+        _f32_vec("crossnet", f"biases[{l}]", b, D, x)
+    _f32_vec("crossnet", "w_head", w_head, D, x)
     N.ensure_device(x)
     x = _c(x)
     B, D = x.shape
@@ -1787,6 +1882,11 @@ ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
 def linear(x, weight, bias=None, act=ACT_NONE):
     """act(x @ weight.T + bias) on the fp32 MFMA (forward only). x [M, K], weight [N<=256, K]."""
+    K = _rows2("linear", "x", x)
+    _f32("linear", "weight", weight, x)
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise ValueError(f"linear: weight has shape {tuple(weight.shape)}, expected [N, {K}]")
+    _f32_vec("linear", "bias", bias, weight.shape[0], x)
     N.ensure_device(x)
     x = _c(x)
     M, K = x.shape

@@ -1,8 +1,13 @@
 """Kernel-level parity: librecsys_amd.so (cuda:0) vs the CPU oracle / float64 restatements.
 
-Tolerances (fp32 kernels vs CPU): gathers bit-exact; LayerNorm outputs 1e-6 abs;
-logits / losses 1e-4 abs (north-star bound: fp32 logits within 1e-4); gradients 1e-5 abs
-+ 1e-4 rel unless stated.
+Tolerances, as asserted below (each test's docstring states its own): plain gathers bit-exact;
+the sequence embedding's LayerNorm output 2e-6 abs and its gradients 2e-5 abs + 1e-4 rel against
+float64; the stand-alone LayerNorm tests (layer_norm, add_layer_norm, linear_add_layer_norm)
+2e-4 abs + 1e-4 rel against torch fp32 on the device, forward and gradients, which is ~100x
+what a correct fp32 LayerNorm needs: tests/test_gpu_glue.py holds the same kernels to a bound
+derived from fp32's own error against float64. Logits / losses 1e-4 abs (north-star bound: fp32
+logits within 1e-4); NCE gradients 2e-6 abs + 1e-4 rel; the bf16x3 GEMM paths 2e-5 of the
+absolute-value product (or 2e-4 + 2e-5 max|ref| through a layer).
 """
 import math
 
