@@ -541,6 +541,36 @@ int rsx_embed3_ln(const float* word, int64_t ld_word, const float* pos, const fl
  * (the cross half of RankingModel.final_head, :313-338). D % 4 == 0, D <= 512, L <= 8. */
 int rsx_crossnet(const float* x, int64_t ldx, int64_t B, int D, int L, const float* const* kernels,
                  const float* const* biases, const float* w_head, float* x_out, float* head_part, void* stream);
+/* Backward of rsx_crossnet: replaces autograd through CrossNet.forward (:258-272) and the cross
+ * half of final_head when the RankingModel is trained (the reference never trains it: dead code
+ * there; arithmetic pinned by the closed form in tests/dcn_train_ref.py). Upstream: dhead [B], the
+ * gradient of head_part (with w_head [D]; together with dw_head [D] or all three NULL), and / or
+ * dx_out [B, D], the gradient of x_L; both given means their sum. Per row, G = dx_{l+1}, l going
+ * down: db_l += G x_0; ds = <G, x_0>; dk_l += ds x_l; dx_0 += G (s_l + b_l); G += ds k_l; dx =
+ * dx_0 + G. Writes dk[l] [D], db[l] [D], dw_head [D] = sum_r dhead_r x_L and dx [B, D] (nullable:
+ * training the ranker alone does not need it). One wave per row, the x_l recomputed in registers
+ * (no [L, B, D] activations; x read once, dx written once); the parameter gradients as
+ * per-workgroup partials in ws (>= rsx_crossnet_bwd_workspace_bytes, -1 for a refused shape), added
+ * in workgroup order by a second launch: no atomics, the same bits every run. max_blocks: 0 = the
+ * default grid cap (1024 workgroups of 4 rows), else a smaller cap (tests). Limits as rsx_crossnet;
+ * B = 0 returns 0 and writes nothing. */
+int64_t rsx_crossnet_bwd_workspace_bytes(int64_t B, int D, int L, int max_blocks);
+int rsx_crossnet_bwd(const float* x, int64_t ldx, int64_t B, int D, int L, const float* const* kernels,
+                     const float* const* biases, const float* w_head, const float* dhead, const float* dx_out,
+                     float* const* dk, float* const* db, float* dw_head, float* dx, void* ws, int64_t ws_bytes,
+                     int max_blocks, void* stream);
+/* Logloss head of the RankingModel's training step (csrc/dcn_train.hip; replaces
+ * binary_cross_entropy_with_logits on final_head(cat(cross, deep)) and its autograd, :313-338):
+ * h2 [R, H = 128], w_d [128] = final_head.weight[D:], head_part [R] (rsx_crossnet's), bias [1]
+ * (device: the host never reads it), y [R] -> logit [R] = head_part + <h2, w_d> + bias, g [R] =
+ * (sigmoid(logit) - y) * (mean ? 1/R : 1), dh2 [R, 128] = g w_d (no ReLU mask: h2 is a GELU
+ * output), dw_d [128] = sum_r g_r h2_r, dbias[0] = sum g, loss[0] (double) with
+ * rsx_deepfm_train_head's row expression and fixed-order partials (ws >=
+ * rsx_dcn_train_head_workspace_bytes(R)). */
+int64_t rsx_dcn_train_head_workspace_bytes(int64_t R);
+int rsx_dcn_train_head(const float* h2, int64_t H, const float* w_d, const float* head_part, const float* bias,
+                       const float* y, int64_t R, int mean, float* logit, float* g, float* dh2, void* ws,
+                       int64_t ws_bytes, double* loss, float* dbias, float* dw_d, void* stream);
 
 /* ---- row gather / scatter / L2 normalise ---------------------------------------------
  * out[r] = src[idx[r]] (idx NULL => r), optionally F.normalize'd (eps) with norms saved:

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 7 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 8  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -132,6 +132,12 @@ _SIGS = {
     "rsx_gather_rows": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i, c_f, c_p, c_p, c_p]),
     "rsx_embed3_ln": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_i64, c_i64, c_p, c_p]),
     "rsx_crossnet": (c_i, [c_p, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_crossnet_bwd_workspace_bytes": (c_i64, [c_i64, c_i, c_i, c_i]),
+    "rsx_crossnet_bwd": (c_i, [c_p, c_i64, c_i64, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i,
+                               c_p]),
+    "rsx_dcn_train_head_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_dcn_train_head": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p,
+                                 c_p]),
     "rsx_segment_sum_rows": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p]),
     "rsx_scatter_rows": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_f, c_i, c_i64, c_p, c_i64, c_p]),
     "rsx_hnm_mine": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, ctypes.c_size_t, c_p, c_p, c_p, c_p]),

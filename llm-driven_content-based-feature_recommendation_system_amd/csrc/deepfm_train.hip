@@ -96,7 +96,10 @@ struct HeadArgs {
   double* pl;        // [blocks]
 };
 
-// 64 rows per workgroup, 4 lanes per row (32 columns each).
+// 64 rows per workgroup, 4 lanes per row (32 columns each). kReluMask: dh2 = g wo [h2 > 0] (the
+// DeepFM DNN ends in a ReLU); without it dh2 = g wo (the DCN-V2 ranker's h2 is a GELU output, whose
+// derivative the LayerNorm backward applies).
+template <bool kReluMask>
 __global__ __launch_bounds__(256) void head_k(HeadArgs a) {
   __shared__ float sG[64];
   __shared__ double sL[64];
@@ -140,10 +143,10 @@ __global__ __launch_bounds__(256) void head_k(HeadArgs a) {
     for (int j = 0; j < 8; ++j) {
       const float4 w = wp[j];
       float4 o;
-      o.x = hv[j].x > 0.0f ? gr * w.x : 0.0f;
-      o.y = hv[j].y > 0.0f ? gr * w.y : 0.0f;
-      o.z = hv[j].z > 0.0f ? gr * w.z : 0.0f;
-      o.w = hv[j].w > 0.0f ? gr * w.w : 0.0f;
+      o.x = !kReluMask || hv[j].x > 0.0f ? gr * w.x : 0.0f;
+      o.y = !kReluMask || hv[j].y > 0.0f ? gr * w.y : 0.0f;
+      o.z = !kReluMask || hv[j].z > 0.0f ? gr * w.z : 0.0f;
+      o.w = !kReluMask || hv[j].w > 0.0f ? gr * w.w : 0.0f;
       dp[j] = o;
     }
   }
@@ -423,6 +426,26 @@ RSX_API int64_t rsx_deepfm_train_head_workspace_bytes(int64_t R) {
   return blocks * (kHeadSlot * (int64_t)sizeof(float) + (int64_t)sizeof(double));
 }
 
+// The two launches of the Logloss head, shared with rsx_dcn_train_head (csrc/dcn_train.hip), which
+// checks its own arguments: ws holds rsx_deepfm_train_head_workspace_bytes(R) bytes.
+int rsx::train_head_launch(const float* h2, const float* wo, const float* lin, const float* bias, const float* y,
+                           int64_t R, int mean, bool relu_mask, float* logit, float* g, float* dh2, void* ws,
+                           double* loss, float* dbias, float* dwo, void* stream) {
+  const int64_t blocks = (R + 63) / 64;
+  HeadArgs a = {};
+  a.h2 = h2; a.wo = wo; a.lin = lin; a.bias = bias; a.y = y; a.R = R;
+  a.scale = mean ? (float)(1.0 / (double)R) : 1.0f;
+  a.logit = logit; a.g = g; a.dh2 = dh2;
+  a.pl = reinterpret_cast<double*>(ws);  // doubles first: 8-byte aligned
+  a.pf = reinterpret_cast<float*>(a.pl + blocks);
+  if (relu_mask) hipLaunchKernelGGL(head_k<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(head_k<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(head_sum_k, dim3(kHeadCols + 2), dim3(64), 0, (hipStream_t)stream, a.pf, a.pl, blocks,
+                     mean ? 1.0 / (double)R : 1.0, loss, dbias, dwo);
+  RSX_LAUNCHED();
+  return 0;
+}
+
 RSX_API int rsx_deepfm_train_head(const float* h2, int64_t H, const float* wo, const float* lin, const float* bias,
                                   const float* y, int64_t R, int mean, float* logit, float* g, float* dh2, void* ws, int64_t ws_bytes,
                                   double* loss, float* dbias, float* dwo, void* stream) {
@@ -432,18 +455,7 @@ RSX_API int rsx_deepfm_train_head(const float* h2, int64_t H, const float* wo, c
   RSX_ARG(R >= 1, "R must be positive");
   RSX_ARG(mean == 0 || mean == 1, "mean must be 0 (sum) or 1 (mean)");
   RSX_ARG(ws_bytes >= rsx_deepfm_train_head_workspace_bytes(R), "workspace too small");
-  const int64_t blocks = (R + 63) / 64;
-  HeadArgs a = {};
-  a.h2 = h2; a.wo = wo; a.lin = lin; a.bias = bias; a.y = y; a.R = R;
-  a.scale = mean ? (float)(1.0 / (double)R) : 1.0f;
-  a.logit = logit; a.g = g; a.dh2 = dh2;
-  a.pl = reinterpret_cast<double*>(ws);  // doubles first: 8-byte aligned
-  a.pf = reinterpret_cast<float*>(a.pl + blocks);
-  hipLaunchKernelGGL(head_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(head_sum_k, dim3(kHeadCols + 2), dim3(64), 0, (hipStream_t)stream, a.pf, a.pl, blocks,
-                     mean ? 1.0 / (double)R : 1.0, loss, dbias, dwo);
-  RSX_LAUNCHED();
-  return 0;
+  return rsx::train_head_launch(h2, wo, lin, bias, y, R, mean, true, logit, g, dh2, ws, loss, dbias, dwo, stream);
 }
 
 RSX_API int rsx_relu_bwd(float* dx, const float* h, int64_t n, void* stream) {

@@ -72,6 +72,12 @@ inline int cu_count() {
   return n;
 }
 
+// The Logloss head of the rerankers' training steps (csrc/deepfm_train.hip: head_k + head_sum_k),
+// arguments as rsx_deepfm_train_head after its checks; relu_mask: dh2 = g wo [h2 > 0], else g wo.
+int train_head_launch(const float* h2, const float* wo, const float* lin, const float* bias, const float* y,
+                      int64_t R, int mean, bool relu_mask, float* logit, float* g, float* dh2, void* ws, double* loss,
+                      float* dbias, float* dwo, void* stream);
+
 }  // namespace rsx
 
 #define RSX_ARG(cond, msg)                                   \

@@ -1875,6 +1875,226 @@ def crossnet(x, kernels, biases, w_head=None, want_x=False):
     return x_out, part
 
 
+def _cross_params(fn, x, kernels, biases, w_head):
+    """Shared checks of crossnet_bwd / dcn_train_step: x fp32 [B, >= D], L kernels / biases of D
+    elements, w_head (None allowed) of D elements, all on x's device. Returns D = the kernels' length
+    (x's width when there is no layer)."""
+    width = _rows2(fn, "x", x)
+    if len(kernels) != len(biases):
+        raise ValueError(f"{fn}: {len(kernels)} kernels but {len(biases)} biases")
+    D = kernels[0].numel() if len(kernels) else width
+    for l, (k, b) in enumerate(zip(kernels, biases)):
+        _f32_vec(fn, f"kernels[{l}]", k, D, x)
+        _f32_vec(fn, f"biases[{l}]", b, D, x)
+    _f32_vec(fn, "w_head", w_head, D, x)
+    return D
+
+
+def _row_view(x):
+    """x [B, W] as the kernels read rows: unit column stride, row stride a multiple of 4."""
+    return x if x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.stride(0) >= x.shape[1] else x.contiguous()
+
+
+def crossnet_bwd(x, kernels, biases, w_head=None, dhead=None, dx_out=None, want_dx=False, dw_head_out=None,
+                 max_blocks=0):
+    """rsx_crossnet_bwd: the gradients of ops.crossnet's sweep over x [B, D] (a [B, D] view of a
+    wider buffer is read in place) for the upstream dhead [B] (gradient of head_part; needs w_head)
+    and / or dx_out [B, D] (gradient of x_L); both mean their sum. Returns (dk: L tensors shaped as
+    the kernels, db: L tensors [D], dw_head [D] or None, dx [B, D] or None (want_dx)). dw_head_out:
+    a contiguous [D] buffer to receive dw_head (a slice of final_head.weight's gradient).
+    max_blocks: a smaller grid cap than the kernel's 1024 workgroups (tests). Deterministic."""
+    fn = "crossnet_bwd"
+    D = _cross_params(fn, x, kernels, biases, w_head)
+    if x.shape[1] != D:
+        raise ValueError(f"{fn}: x has {x.shape[1]} columns, the layers {D}")
+    B = x.shape[0]
+    if (w_head is None) != (dhead is None):
+        raise ValueError(f"{fn}: w_head and dhead go together")
+    if dhead is None and dx_out is None:
+        raise ValueError(f"{fn}: no upstream gradient (give w_head and dhead, and / or dx_out)")
+    _f32_vec(fn, "dhead", dhead, B, x)
+    if dx_out is not None:
+        _f32(fn, "dx_out", dx_out, x)
+        if tuple(dx_out.shape) != (B, D):
+            raise ValueError(f"{fn}: dx_out has shape {tuple(dx_out.shape)}, expected {(B, D)}")
+    if dw_head_out is not None:
+        _f32_vec(fn, "dw_head_out", dw_head_out, D, x)
+        if w_head is None or not dw_head_out.is_contiguous():
+            raise ValueError(f"{fn}: dw_head_out must be contiguous and needs w_head")
+    N.ensure_device(x)
+    x = _row_view(x)
+    L, dev, lib = len(kernels), x.device, N.lib()
+    ks = [_c(k.reshape(-1)) for k in kernels]
+    bs = [_c(b.reshape(-1)) for b in biases]
+    # rows: dk_0.., db_0.., dw_head (an empty batch launches nothing: its sums are zero)
+    flat = (torch.empty if B else torch.zeros)(2 * L + 1, D, device=dev, dtype=torch.float32)
+    if B == 0 and dw_head_out is not None:
+        dw_head_out.zero_()
+    dk, db = [flat[l] for l in range(L)], [flat[L + l] for l in range(L)]
+    dwh = None if w_head is None else (dw_head_out if dw_head_out is not None else flat[2 * L])
+    dx = torch.empty(B, D, device=dev, dtype=torch.float32) if want_dx else None
+    nws = lib.rsx_crossnet_bwd_workspace_bytes(B, D, L, int(max_blocks))
+    ws = torch.empty(max(nws, 0), device=dev, dtype=torch.uint8)
+    with timed("crossnet_bwd"):
+        rc = lib.rsx_crossnet_bwd(N.ptr(x), x.stride(0), B, D, L, N.ptr_array(ks), N.ptr_array(bs),
+                                  N.ptr(None if w_head is None else _c(w_head.reshape(-1))),
+                                  N.ptr(None if dhead is None else _c(dhead.reshape(-1))), N.ptr(_c(dx_out)),
+                                  N.ptr_array(dk), N.ptr_array(db), N.ptr(dwh), N.ptr(dx), N.ptr(ws), max(nws, 0),
+                                  int(max_blocks), N.stream())
+    N.check(rc, "crossnet_bwd")
+    return [g.view(k.shape) for g, k in zip(dk, kernels)], db, dwh, dx
+
+
+# ----------------------------------------------------------------------------------------
+# DCN-V2 reranker training: one step of the RankingModel (csrc/dcn.hip, csrc/dcn_train.hip)
+def dcn_train_supported(D, hidden):
+    """None when the training kernels cover the shape, else the text naming the limit."""
+    if tuple(hidden) != (256, 128):
+        return f"RankingModel training needs the deep net's widths (256, 128) (got {tuple(hidden)})"
+    if D % 4 or not 4 <= D <= 512:
+        return f"RankingModel training needs an input width that is a multiple of 4 in [4, 512] (got {D})"
+    return None
+
+
+class DCNStep:
+    """What dcn_train_step returns: loss (0-d float64 device tensor), logit [B], grads (in the order
+    of its parameters: the L kernels, the L biases, W1, b1, LN1 weight / bias, W2, b2, LN2 weight /
+    bias, final_head.weight [1, D + 128], final_head.bias [1]) and, with return_acts, h1 (after the
+    dropout) and x_L."""
+
+    def __init__(self, loss, logit, grads, h1=None, x_L=None):
+        self.loss, self.logit, self.grads, self.h1, self.x_L = loss, logit, grads, h1, x_L
+
+
+def dcn_train_step(x, y, kernels, biases, w1, b1, ln1_w, ln1_b, w2, b2, ln2_w, ln2_b, w_head, head_bias,
+                   eps1=1e-5, eps2=1e-5, p_drop=0.0, seed=0, reduction="mean", return_acts=False):
+    """Forward, Logloss and backward of the DCN-V2 RankingModel over raw tensors, no host
+    synchronisation: x [B, D] fp32 (or the list of its column blocks: user, item[, context]), y [B];
+    cross network (kernels / biases, L of [D(, 1)]) and deep net Linear(D, 256) + LayerNorm + GELU +
+    dropout(p_drop, seed) + Linear(256, 128) + LayerNorm + GELU, final_head weight w_head [1, D + 128]
+    and bias head_bias [1] (read on the device). Binary cross-entropy on the logit, reduction "mean"
+    | "sum". The step's input lives in a [B, Dp] buffer, Dp = D rounded up to 16 with zero pad
+    columns: row stride Dp for the cross network and the first linear, K = Dp for its weight gradient
+    (rsx_linear_wgrad needs K % 16 == 0). Returns a DCNStep; the caller applies the update."""
+    fn = "dcn_train_step"
+    parts = list(x) if isinstance(x, (list, tuple)) else [x]
+    for i, t in enumerate(parts):
+        _rows2(fn, f"x[{i}]" if len(parts) > 1 else "x", t)
+        if t.shape[0] != parts[0].shape[0]:
+            raise ValueError(f"{fn}: x[{i}] has {t.shape[0]} rows, x[0] {parts[0].shape[0]}")
+        if t.device != parts[0].device:
+            raise RuntimeError(f"{fn}: x[{i}] is on {t.device}, expected {parts[0].device}")
+    x0 = parts[0]
+    B, D = x0.shape[0], sum(t.shape[1] for t in parts)
+    if reduction not in ("mean", "sum"):
+        raise ValueError('reduction must be "mean" or "sum"')
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError(f"{fn}: p_drop must be in [0, 1) (got {p_drop})")
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one row")
+    if len(kernels) != len(biases):
+        raise ValueError(f"{fn}: {len(kernels)} kernels but {len(biases)} biases")
+    for l, (k, b) in enumerate(zip(kernels, biases)):
+        _f32_vec(fn, f"kernels[{l}]", k, D, x0)
+        _f32_vec(fn, f"biases[{l}]", b, D, x0)
+    for name, t, shape in (("w1", w1, (256, D)), ("w2", w2, (128, 256))):
+        _f32(fn, name, t, x0)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{fn}: {name} has shape {tuple(t.shape)}, expected {shape}")
+    for name, t, n in (("b1", b1, 256), ("ln1_w", ln1_w, 256), ("ln1_b", ln1_b, 256), ("b2", b2, 128),
+                       ("ln2_w", ln2_w, 128), ("ln2_b", ln2_b, 128), ("w_head", w_head, D + 128),
+                       ("head_bias", head_bias, 1)):
+        if t is None:
+            raise ValueError(f"{fn}: {name} is missing")
+        _f32_vec(fn, name, t, n, x0)
+    if not torch.is_tensor(y):
+        raise TypeError(f"{fn}: y must be a tensor")
+    if y.numel() != B:
+        raise ValueError(f"{fn}: {y.numel()} labels for {B} rows")
+    if y.device != x0.device:
+        raise RuntimeError(f"{fn}: y is on {y.device}, expected {x0.device}")
+    why = dcn_train_supported(D, (w1.shape[0], w2.shape[0]))
+    if why:
+        raise NotImplementedError(why)
+    N.ensure_device(x0)
+    dev, lib, st = x0.device, N.lib(), N.stream()
+    L = len(kernels)
+    y = _c(y.to(torch.float32).reshape(-1))
+    Dp = (D + 15) // 16 * 16
+    if len(parts) == 1 and Dp == D:
+        xp = _row_view(x0)
+    else:
+        xp = torch.empty(B, Dp, device=dev, dtype=torch.float32)
+        o = 0
+        for t in parts:
+            xp[:, o:o + t.shape[1]].copy_(t)
+            o += t.shape[1]
+        if Dp > D:
+            xp[:, D:].zero_()
+    ldx = xp.stride(0)
+    ks, bs = [_c(k.reshape(-1)) for k in kernels], [_c(b.reshape(-1)) for b in biases]
+    kp, bp = N.ptr_array(ks), N.ptr_array(bs)
+    w1, w2, wh = _c(w1), _c(w2), _c(w_head.reshape(-1))
+    f32 = dict(device=dev, dtype=torch.float32)
+
+    def ln_gelu(z, w, b, eps):
+        h = torch.empty_like(z)
+        mean, rstd = torch.empty(B, **f32), torch.empty(B, **f32)
+        N.check(lib.rsx_ln_fwd(N.ptr(z), None, 0.0, 0, N.ptr(w), N.ptr(b), float(eps), ACT_GELU_ERF, B, z.shape[1],
+                               None, N.ptr(h), N.ptr(mean), N.ptr(rstd), st), "ln_fwd")
+        return h, mean, rstd
+
+    def mask(t):
+        """dropout's keep-mask / (1 - p) of (seed, row * 256 + col) applied to t [B, 256]; t itself at p = 0."""
+        if p_drop == 0.0:
+            return t
+        out = torch.empty_like(t)
+        N.check(lib.rsx_dropout_bwd(N.ptr(t), B, 256, float(p_drop), int(seed), N.ptr(out), st), "dropout")
+        return out
+
+    # forward, keeping the LayerNorm inputs and statistics
+    with timed("dcn_train/forward"):
+        head_part = torch.empty(B, **f32)
+        x_L = torch.empty(B, D, **f32) if return_acts else None
+        N.check(lib.rsx_crossnet(N.ptr(xp), ldx, B, D, L, kp, bp, N.ptr(wh), N.ptr(x_L), N.ptr(head_part), st),
+                "crossnet")
+        z1 = torch.empty(B, 256, **f32)
+        N.check(lib.rsx_linear_fwd(N.ptr(xp), ldx, N.ptr(w1), N.ptr(_c(b1)), B, 256, D, ACT_NONE, N.ptr(z1), st),
+                "linear_fwd")
+        a1, mean1, rstd1 = ln_gelu(z1, ln1_w, ln1_b, eps1)
+        h1 = mask(a1)
+        z2 = linear(h1, w2, b2)
+        h2, mean2, rstd2 = ln_gelu(z2, ln2_w, ln2_b, eps2)
+        logit, g, dh2 = torch.empty(B, **f32), torch.empty(B, **f32), torch.empty(B, 128, **f32)
+        loss = torch.empty((), device=dev, dtype=torch.float64)
+        gwh = torch.empty(1, D + 128, **f32)     # final_head.weight's gradient: [cross | deep] slices
+        gbias = torch.empty(1, **f32)
+        nws = lib.rsx_dcn_train_head_workspace_bytes(B)
+        ws = torch.empty(nws, device=dev, dtype=torch.uint8)
+        N.check(lib.rsx_dcn_train_head(N.ptr(h2), 128, N.ptr(wh) + 4 * D, N.ptr(head_part), N.ptr(_c(head_bias)),
+                                       N.ptr(y), B, 1 if reduction == "mean" else 0, N.ptr(logit), N.ptr(g),
+                                       N.ptr(dh2), N.ptr(ws), nws, N.ptr(loss), N.ptr(gbias), N.ptr(gwh) + 4 * D, st),
+                "dcn_train_head")
+
+    # deep half backward: exact fp32 products for the weight gradients, as the DeepFM step
+    with timed("dcn_train/deep_bwd"):
+        dz2, _, dln2w, dln2b = _ln_bwd(z2, mean2, rstd2, ln2_w, ln2_b, ACT_GELU_ERF, dh2, None, 0.0, 0, True, False,
+                                       True, True)
+        dw2, db2 = linear_wgrad(dz2, h1, (128, 256), True, tag="dcn_train/dw2", precision="fp32")
+        dh1 = mask(gemm_x3_tn(dz2, w2, tag="dcn_train/dh1"))
+        dz1, _, dln1w, dln1b = _ln_bwd(z1, mean1, rstd1, ln1_w, ln1_b, ACT_GELU_ERF, dh1, None, 0.0, 0, True, False,
+                                       True, True)
+        dw1, db1 = linear_wgrad(dz1, xp, (256, Dp), True, tag="dcn_train/dw1", precision="fp32")
+        if Dp > D:
+            dw1 = dw1[:, :D].contiguous()
+
+    # cross network backward from g (dx is not needed to train the ranker alone)
+    dk, dbs, _, _ = crossnet_bwd(xp[:, :D], ks, bs, w_head=wh[:D], dhead=g, dw_head_out=gwh[0, :D])
+    grads = ([t.view(k.shape) for t, k in zip(dk, kernels)] + [t.view(b.shape) for t, b in zip(dbs, biases)]
+             + [dw1, db1, dln1w, dln1b, dw2, db2, dln2w, dln2b, gwh, gbias])
+    return DCNStep(loss, logit, grads, h1 if return_acts else None, x_L)
+
+
 # ----------------------------------------------------------------------------------------
 # A16: DeepFM forward (inference)
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2

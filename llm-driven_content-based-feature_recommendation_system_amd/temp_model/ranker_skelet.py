@@ -25,6 +25,127 @@ import torch.nn as nn
 from .. import ops
 
 
+def _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every):
+    """The argument checks of fit (DeepFM.fit documents them) that need no data; returns the
+    effective use_best_model (default True with an eval_set)."""
+    if eval_metric not in ("AUC", "Logloss"):
+        raise ValueError(f'eval_metric must be "AUC" or "Logloss" (got {eval_metric!r})')
+    if eval_set is None:
+        if early_stopping_rounds is not None or eval_every is not None or use_best_model:
+            raise ValueError("early_stopping_rounds, eval_every and use_best_model need an eval_set")
+        return False
+    if early_stopping_rounds is not None and early_stopping_rounds < 1:
+        raise ValueError("early_stopping_rounds must be >= 1")
+    if eval_every is not None and eval_every < 1:
+        raise ValueError("eval_every must be >= 1")
+    return True if use_best_model is None else use_best_model
+
+
+def _fit_eval_labels(yv, eval_metric):
+    """ValueError for validation labels outside {0, 1} or a single class with eval_metric "AUC" (one host read)."""
+    n_pos, n_neg = (int(v) for v in torch.stack([(yv == 1).sum(), (yv == 0).sum()]).tolist())
+    if n_pos + n_neg != yv.numel():
+        raise ValueError("eval_set labels must be 0 or 1")
+    if eval_metric == "AUC" and (n_pos == 0 or n_neg == 0):
+        raise ValueError('eval_set holds a single class: eval_metric="AUC" is undefined')
+
+
+def _fit_loop(model, tr, step, R, dev, batch_size, epochs, shuffle, seed, validate, eval_metric,
+              early_stopping_rounds, use_best_model, eval_every, after_steps=None):
+    """The training loop of DeepFM.fit and RankingModel.fit (semantics: DeepFM.fit's docstring).
+    step(sel) -> the loss of the batch of rows sel (a slice, or an index tensor when shuffled);
+    tr.reduction says how it was reduced. validate: None, or a callable returning the validation
+    rows' ops.BinaryEval. after_steps: called once the last step was taken, before the best
+    parameters are restored. Returns the completed epochs' mean row losses."""
+    gen = torch.Generator().manual_seed(seed)
+    means = []
+    if validate is None:
+        for _ in range(epochs):
+            order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
+            total = torch.zeros((), device=dev, dtype=torch.float64)
+            for s in range(0, R, batch_size):
+                e = min(R, s + batch_size)
+                loss = step(slice(s, e) if order is None else order[s:e])
+                total += loss * (e - s) if tr.reduction == "mean" else loss
+            means.append(float((total / R).item()))
+        if after_steps is not None:
+            after_steps()
+        return means
+
+    model.evals_result_ = {"learn": {"Logloss": []}, "validation": {"Logloss": [], "AUC": []}}
+    model.best_iteration_, model.best_score_ = None, None
+    params = list(model.parameters())
+    snapshot, stale = None, False      # stale: steps were taken since the snapshot was written
+    state = {"best": None, "since": 0}
+
+    def evaluate_now(learn_mean):
+        """One evaluation; learn_mean: 0-d float64 device tensor. True when training should stop."""
+        nonlocal snapshot, stale
+        res, (learn,) = validate().result(also=learn_mean)
+        ev = model.evals_result_
+        ev["learn"]["Logloss"].append(learn)
+        ev["validation"]["Logloss"].append(res["logloss"])
+        ev["validation"]["AUC"].append(res["auc"])
+        score = res["auc"] if eval_metric == "AUC" else -res["logloss"]
+        if state["best"] is None or score > state["best"]:
+            state["best"], state["since"] = score, 0
+            model.best_iteration_ = len(ev["validation"]["AUC"]) - 1
+            model.best_score_ = {"validation": {"Logloss": res["logloss"], "AUC": res["auc"]}}
+            if use_best_model:
+                with torch.no_grad():
+                    if snapshot is None:
+                        snapshot = [torch.empty_like(p) for p in params]
+                    torch._foreach_copy_(snapshot, params)
+                stale = False
+        else:
+            state["since"] += 1
+        return early_stopping_rounds is not None and state["since"] >= early_stopping_rounds
+
+    stop, gstep = False, 0
+    since_total = torch.zeros((), device=dev, dtype=torch.float64)
+    since_rows = 0
+    for _ in range(epochs):
+        order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
+        total = torch.zeros((), device=dev, dtype=torch.float64)
+        for s in range(0, R, batch_size):
+            e = min(R, s + batch_size)
+            loss = step(slice(s, e) if order is None else order[s:e])
+            row_loss = loss * (e - s) if tr.reduction == "mean" else loss
+            total += row_loss
+            stale = True
+            gstep += 1
+            if eval_every is not None:
+                since_total += row_loss
+                since_rows += e - s
+                if gstep % eval_every == 0:
+                    stop = evaluate_now(since_total / since_rows)
+                    since_total.zero_()
+                    since_rows = 0
+                    if stop:
+                        break
+        if stop:
+            break       # the epoch was cut short: no mean for it
+        mean = total / R
+        if eval_every is None:
+            stop = evaluate_now(mean)
+            means.append(model.evals_result_["learn"]["Logloss"][-1])
+            if stop:
+                break
+        else:
+            means.append(float(mean.item()))
+    if after_steps is not None:
+        after_steps()
+    if use_best_model and snapshot is not None and stale:
+        before = [p._version for p in params]
+        with torch.no_grad():
+            for p, s in zip(params, snapshot):
+                p.copy_(s)
+        for p, v in zip(params, before):     # the caches of forward_logits key on the version counters
+            if p._version == v:
+                torch.autograd.graph.increment_version(p)
+    return means
+
+
 class DeepFM(nn.Module):
     """deepctr-torch-style DeepFM over F sparse fields (binary task).
 
@@ -158,116 +279,17 @@ class DeepFM(nn.Module):
         evaluation), best_iteration_ (0-based index of the best evaluation) and best_score_ =
         {"validation": {"Logloss", "AUC"}} at it. ValueError before the first step for an unknown
         eval_metric, validation labels outside {0, 1}, or a single class with eval_metric "AUC"."""
-        if eval_metric not in ("AUC", "Logloss"):
-            raise ValueError(f'eval_metric must be "AUC" or "Logloss" (got {eval_metric!r})')
-        if eval_set is None:
-            if early_stopping_rounds is not None or eval_every is not None or use_best_model:
-                raise ValueError("early_stopping_rounds, eval_every and use_best_model need an eval_set")
-        else:
-            if early_stopping_rounds is not None and early_stopping_rounds < 1:
-                raise ValueError("early_stopping_rounds must be >= 1")
-            if eval_every is not None and eval_every < 1:
-                raise ValueError("eval_every must be >= 1")
+        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every)
+        validate = None
+        if eval_set is not None:
             Xv, yv = self._rows_on_device(*eval_set)
-            n_pos, n_neg = (int(v) for v in torch.stack([(yv == 1).sum(), (yv == 0).sum()]).tolist())
-            if n_pos + n_neg != yv.numel():
-                raise ValueError("eval_set labels must be 0 or 1")
-            if eval_metric == "AUC" and (n_pos == 0 or n_neg == 0):
-                raise ValueError('eval_set holds a single class: eval_metric="AUC" is undefined')
-            if use_best_model is None:
-                use_best_model = True
+            _fit_eval_labels(yv, eval_metric)
+            validate = lambda: self._evaluate_on_device(Xv, yv, 65536)   # noqa: E731
         tr = self.make_trainer(**trainer_kw)
         X, y = self._rows_on_device(X, y)
-        dev = X.device
-        R = X.shape[0]
-        gen = torch.Generator().manual_seed(seed)
-        means = []
-        if eval_set is None:
-            for _ in range(epochs):
-                order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
-                total = torch.zeros((), device=dev, dtype=torch.float64)
-                for s in range(0, R, batch_size):
-                    e = min(R, s + batch_size)
-                    xb, yb = (X[s:e], y[s:e]) if order is None else (X[order[s:e]], y[order[s:e]])
-                    loss = tr.step(xb, yb)
-                    total += loss * (e - s) if tr.reduction == "mean" else loss
-                means.append(float((total / R).item()))
-            tr.check_ids()
-            return means
-
-        self.evals_result_ = {"learn": {"Logloss": []}, "validation": {"Logloss": [], "AUC": []}}
-        self.best_iteration_, self.best_score_ = None, None
-        params = list(self.parameters())
-        snapshot, stale = None, False      # stale: steps were taken since the snapshot was written
-        state = {"best": None, "since": 0}
-        val_bs = 65536
-
-        def evaluate_now(learn_mean):
-            """One evaluation; learn_mean: 0-d float64 device tensor. True when training should stop."""
-            nonlocal snapshot, stale
-            res, (learn,) = self._evaluate_on_device(Xv, yv, val_bs).result(also=learn_mean)
-            ev = self.evals_result_
-            ev["learn"]["Logloss"].append(learn)
-            ev["validation"]["Logloss"].append(res["logloss"])
-            ev["validation"]["AUC"].append(res["auc"])
-            score = res["auc"] if eval_metric == "AUC" else -res["logloss"]
-            if state["best"] is None or score > state["best"]:
-                state["best"], state["since"] = score, 0
-                self.best_iteration_ = len(ev["validation"]["AUC"]) - 1
-                self.best_score_ = {"validation": {"Logloss": res["logloss"], "AUC": res["auc"]}}
-                if use_best_model:
-                    with torch.no_grad():
-                        if snapshot is None:
-                            snapshot = [torch.empty_like(p) for p in params]
-                        torch._foreach_copy_(snapshot, params)
-                    stale = False
-            else:
-                state["since"] += 1
-            return early_stopping_rounds is not None and state["since"] >= early_stopping_rounds
-
-        stop, gstep = False, 0
-        since_total = torch.zeros((), device=dev, dtype=torch.float64)
-        since_rows = 0
-        for _ in range(epochs):
-            order = torch.randperm(R, generator=gen).to(dev) if shuffle else None
-            total = torch.zeros((), device=dev, dtype=torch.float64)
-            for s in range(0, R, batch_size):
-                e = min(R, s + batch_size)
-                xb, yb = (X[s:e], y[s:e]) if order is None else (X[order[s:e]], y[order[s:e]])
-                loss = tr.step(xb, yb)
-                row_loss = loss * (e - s) if tr.reduction == "mean" else loss
-                total += row_loss
-                stale = True
-                gstep += 1
-                if eval_every is not None:
-                    since_total += row_loss
-                    since_rows += e - s
-                    if gstep % eval_every == 0:
-                        stop = evaluate_now(since_total / since_rows)
-                        since_total.zero_()
-                        since_rows = 0
-                        if stop:
-                            break
-            if stop:
-                break       # the epoch was cut short: no mean for it
-            mean = total / R
-            if eval_every is None:
-                stop = evaluate_now(mean)
-                means.append(self.evals_result_["learn"]["Logloss"][-1])
-                if stop:
-                    break
-            else:
-                means.append(float(mean.item()))
-        tr.check_ids()
-        if use_best_model and snapshot is not None and stale:
-            before = [p._version for p in params]
-            with torch.no_grad():
-                for p, s in zip(params, snapshot):
-                    p.copy_(s)
-            for p, v in zip(params, before):     # the caches of forward_logits key on the version counters
-                if p._version == v:
-                    torch.autograd.graph.increment_version(p)
-        return means
+        return _fit_loop(self, tr, lambda sel: tr.step(X[sel], y[sel]), X.shape[0], X.device, batch_size, epochs,
+                         shuffle, seed, validate, eval_metric, early_stopping_rounds, use_best_model, eval_every,
+                         after_steps=tr.check_ids)
 
 
 class DeepFMTrainer:
@@ -516,22 +538,90 @@ class RankingModel(nn.Module):
                                       nn.Linear(256, 128), nn.LayerNorm(128), nn.GELU())
         self.final_head = nn.Linear(total_input_dim + 128, 1)
 
+    def _check_width(self, D):
+        if self.deep_net[0].in_features != D:
+            raise ValueError(f"input width {D} != the model's {self.deep_net[0].in_features} (context given / omitted?)")
+
     @torch.no_grad()
     def forward(self, user_emb, item_emb, context_emb=None):
+        return torch.sigmoid(self.forward_logits(user_emb, item_emb, context_emb)).unsqueeze(1)
+
+    @torch.no_grad()
+    def forward_logits(self, user_emb, item_emb, context_emb=None):
+        """The pre-sigmoid logits [B] of forward (the inference path: dropout inactive)."""
         parts = [user_emb, item_emb] + ([context_emb] if context_emb is not None else [])
         x = torch.cat(parts, dim=1).float().contiguous()
         D = x.shape[1]
         lin1, ln1, lin2, ln2 = self.deep_net[0], self.deep_net[1], self.deep_net[4], self.deep_net[5]
-        if lin1.in_features != D:
-            raise ValueError(f"input width {D} != the model's {lin1.in_features} (context given / omitted?)")
+        self._check_width(D)
         wh = self.final_head.weight.reshape(-1)
         _, head_part = ops.crossnet(x, list(self.cross_net.kernels), list(self.cross_net.biases), w_head=wh[:D])
         h = ops.layer_norm(ops.linear(x, lin1.weight, lin1.bias), ln1.weight, ln1.bias, ln1.eps,
                            act=ops.ACT_GELU_ERF)
         h = ops.layer_norm(ops.linear(h, lin2.weight, lin2.bias), ln2.weight, ln2.bias, ln2.eps,
                            act=ops.ACT_GELU_ERF)
-        logits = head_part + h @ wh[D:] + self.final_head.bias
-        return torch.sigmoid(logits).unsqueeze(1)
+        return head_part + h @ wh[D:] + self.final_head.bias
+
+    def make_trainer(self, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, reduction="mean",
+                     max_grad_norm=None, dropout=None, seed=0):
+        """A RankingModelTrainer over this model's parameters (Logloss, AdamW). dropout: the rate after
+        the first GELU (default: the module's, nn.Dropout(0.2)); seed: of its masks. Raises
+        NotImplementedError for widths the training kernels do not cover (ops.dcn_train_supported)."""
+        return RankingModelTrainer(self, lr, betas, eps, weight_decay, reduction, max_grad_norm, dropout, seed)
+
+    def _rows_on_device(self, user, item, context, y):
+        dev = self.final_head.weight.device
+        parts = [torch.as_tensor(t).to(dev, torch.float32) for t in (user, item, context) if t is not None]
+        y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(dev, torch.float32).reshape(-1)
+        if any(t.dim() != 2 or t.shape[0] != y.numel() for t in parts):
+            raise ValueError(f"need [R, d] feature blocks and y [R] (got {[tuple(t.shape) for t in parts]} and "
+                             f"{y.numel()} labels)")
+        self._check_width(sum(t.shape[1] for t in parts))
+        return parts, y
+
+    @torch.no_grad()
+    def _evaluate_on_device(self, parts, y, batch_size):
+        """forward_logits over the rows in batches into one [R] buffer, then one ops.binary_eval."""
+        R = y.numel()
+        logits = torch.empty(R, device=y.device, dtype=torch.float32)
+        ctx = parts[2] if len(parts) > 2 else None
+        for s in range(0, R, batch_size):
+            e = s + batch_size
+            logits[s:e].copy_(self.forward_logits(parts[0][s:e], parts[1][s:e], None if ctx is None else ctx[s:e]))
+        return ops.binary_eval(logits, y)
+
+    def evaluate(self, user, item, context, y, batch_size=65536):
+        """{"Logloss", "AUC"} of the model on the rows (user [R, du], item [R, di], context [R, dc] or
+        None) against y [R] in {0, 1}: the inference path over batches of batch_size and one
+        device-side evaluation (ops.binary_eval), one host read. AUC is NaN when y holds one class."""
+        parts, y = self._rows_on_device(user, item, context, y)
+        res = self._evaluate_on_device(parts, y, int(batch_size)).result()
+        return {"Logloss": res["logloss"], "AUC": res["auc"]}
+
+    def fit(self, user, item, context, y, batch_size, epochs=1, shuffle=True, seed=0, eval_set=None,
+            eval_metric="AUC", early_stopping_rounds=None, use_best_model=None, eval_every=None, **trainer_kw):
+        """Train on the rows (user, item, context or None) / y [R] in {0, 1} with exactly the semantics
+        documented on DeepFM.fit (one shared loop): batches of batch_size, the row order shuffled per
+        epoch from `seed`, the completed epochs' mean row losses returned; eval_set = (user, item,
+        context, y) with eval_metric, early_stopping_rounds, use_best_model (the device snapshot
+        restored into the same Parameter objects) and eval_every; evals_result_, best_iteration_,
+        best_score_; the same ValueErrors. trainer_kw: make_trainer's other arguments (`seed` also seeds
+        the trainer's dropout masks, so one seed reproduces a fit)."""
+        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every)
+        validate = None
+        if eval_set is not None:
+            pv, yv = self._rows_on_device(*eval_set)
+            _fit_eval_labels(yv, eval_metric)
+            validate = lambda: self._evaluate_on_device(pv, yv, 65536)   # noqa: E731
+        tr = self.make_trainer(seed=seed, **trainer_kw)
+        parts, y = self._rows_on_device(user, item, context, y)
+        ctx = parts[2] if len(parts) > 2 else None
+
+        def step(sel):
+            return tr.step(parts[0][sel], parts[1][sel], None if ctx is None else ctx[sel], y[sel])
+
+        return _fit_loop(self, tr, step, y.numel(), y.device, batch_size, epochs, shuffle, seed, validate, eval_metric,
+                         early_stopping_rounds, use_best_model, eval_every)
 
     @torch.no_grad()
     def predict_for_user(self, user_vec, item_vecs, context_vec=None):
@@ -543,3 +633,70 @@ class RankingModel(nn.Module):
         if context_vec is not None:
             ctx = (context_vec.unsqueeze(0) if context_vec.dim() == 1 else context_vec).expand(n, -1)
         return self.forward(user_vec.expand(n, -1), item_vecs, ctx).squeeze()
+
+
+class RankingModelTrainer:
+    """One-call training steps for a RankingModel on the device (ops.dcn_train_step): step(user, item,
+    context, y) runs the forward (dropout after the first GELU active: a counter-hash mask of (seed,
+    step count) that the backward regenerates), the Logloss, the backward (the cross network's on
+    rsx_crossnet_bwd) and one torch.optim.AdamW over all parameters (the cross kernels and biases,
+    both linears, both LayerNorms, final_head), stepped by ops.clip_adamw_step with clip_grad_norm_
+    over them when max_grad_norm is given, without a host synchronisation. The gradient of the
+    towers' outputs (user / item / context) is not formed. Validation lives in RankingModel.fit."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, reduction="mean",
+                 max_grad_norm=None, dropout=None, seed=0):
+        d = model.deep_net
+        why = ops.dcn_train_supported(d[0].in_features, (d[0].out_features, d[4].out_features))
+        if why:
+            raise NotImplementedError(why)
+        if reduction not in ("mean", "sum"):
+            raise ValueError('reduction must be "mean" or "sum"')
+        self.p_drop = float(d[3].p if dropout is None else dropout)
+        if not 0.0 <= self.p_drop < 1.0:
+            raise ValueError(f"dropout must be in [0, 1) (got {self.p_drop})")
+        self.model = model
+        self.reduction, self.max_grad_norm, self.seed = reduction, max_grad_norm, int(seed)
+        self.step_count = 0
+        self.params = (list(model.cross_net.kernels) + list(model.cross_net.biases)
+                       + [d[0].weight, d[0].bias, d[1].weight, d[1].bias, d[4].weight, d[4].bias, d[5].weight,
+                          d[5].bias, model.final_head.weight, model.final_head.bias])
+        self.optimizer = torch.optim.AdamW(self.params, lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
+
+    def _mask_seed(self):
+        """The dropout seed of the current step: a function of (seed, step count) only."""
+        return (self.seed + self.step_count * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+
+    @torch.no_grad()
+    def step(self, user, item, context, y, return_step=False):
+        """One step on the batch (user [B, du], item [B, di], context [B, dc] or None, y [B]); returns
+        the loss (0-d device tensor), or the whole ops.DCNStep with return_step."""
+        m = self.model
+        parts = [t.float() for t in (user, item, context) if t is not None]
+        m._check_width(sum(t.shape[1] for t in parts))
+        d, L = m.deep_net, len(m.cross_net.kernels)
+        self.step_count += 1
+        res = ops.dcn_train_step(parts, y, self.params[:L], self.params[L:2 * L], d[0].weight, d[0].bias, d[1].weight,
+                                 d[1].bias, d[4].weight, d[4].bias, d[5].weight, d[5].bias, m.final_head.weight,
+                                 m.final_head.bias, eps1=d[1].eps, eps2=d[5].eps, p_drop=self.p_drop,
+                                 seed=self._mask_seed(), reduction=self.reduction)
+        for p, g in zip(self.params, res.grads):
+            p.grad = g.view(p.shape)
+        clip = self.params if self.max_grad_norm is not None else []
+        if ops.clip_adamw_step(self.optimizer, clip, self.max_grad_norm or 0.0) is None:
+            if self.max_grad_norm is not None:
+                torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+            self.optimizer.step()
+        for p in self.params:
+            p.grad = None
+            torch.autograd.graph.increment_version(p)   # rsx_clip_adamw writes through raw pointers
+        return res if return_step else res.loss
+
+    def state_dict(self):
+        """A snapshot (copies): the step count (it seeds the dropout masks) and the optimizer's state."""
+        import copy
+        return {"step": self.step_count, "seed": self.seed, "optimizer": copy.deepcopy(self.optimizer.state_dict())}
+
+    def load_state_dict(self, sd):
+        self.step_count, self.seed = int(sd["step"]), int(sd["seed"])
+        self.optimizer.load_state_dict(sd["optimizer"])
