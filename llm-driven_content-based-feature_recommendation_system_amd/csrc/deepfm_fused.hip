@@ -693,20 +693,17 @@ __global__ __launch_bounds__(256) void deepfm_pack_k(const float* V, const float
 // the third (tools/probe/gather_pieces.hip). The lane's eight values are the B fragment of
 // v_mfma_f32_32x32x16_bf16 for k-slots 8h..8h+7 <-> V[kperm(slot)], kperm = {0-3, 8-11, 4-7,
 // 12-15} (the W1 image uses the same order). W1 (the A operand, [256][16] per field, hi / lo)
-// streams through a two-slot LDS ring: each wave register-loads a quarter of field f + R's
-// image along with its own gathers for f + R, writes it at field f, one barrier per field (no
-// glds: beside it hipcc drains ordinary loads with vmcnt(0)). The field loop is fully unrolled
+// streams through an LDS ring, one barrier per field. The field loop is fully unrolled
 // (F is a template parameter) so the R-deep register ring is straight-line code: loop-carried
 // load registers make hipcc drain the loads at the loop header. Layer 2 takes its B fragments
 // from the layer-1 accumulators (the deepfm_fused_k order; W2 image of deepfm_prep_k).
 constexpr int kRowsF = 39;
-constexpr int kRowsR = 8;           // fields of loads in flight ahead of the one computed
 constexpr int kW1Field = 8192;      // bf16 per field image: hi [256][16] then lo [256][16]
 
 struct RArgs {
   const int64_t* x;          // [R, F]
   const float* P[kMaxF];     // packed [vocab][32]: V[16], W, pad
-  const float* V[kMaxF];     // unpacked form (deepfm_rows5_k<F, false>): V [vocab][16], W [vocab] or null
+  const float* V[kMaxF];     // unpacked form (deepfm_rows5_k): V [vocab][16], W [vocab] or null
   const float* W[kMaxF];
   int64_t R;
   int64_t nit;               // task rounds (4 tasks of 64 rows per workgroup per round)
@@ -727,235 +724,15 @@ __device__ __host__ __forceinline__ int w1_idx(int n, int slot) {
   return n * 16 + 8 * ((slot >> 3) ^ ((n >> 3) & 1)) + (slot & 7);
 }
 
-// ABL (timing ablations, results wrong; RSX_DEEPFM_ABL): 1 no per-field barrier, 2 no W1 LDS
-// writes, 4 no layer-1 MFMAs, 8 no layer 2
-template <int F, int ABL = 0>
-__global__ __launch_bounds__(256, 1) void deepfm_rows_k(RArgs a) {
-  constexpr int R = kRowsR, NB = R + 1;
-  __shared__ __attribute__((aligned(16))) __bf16 w1s[2][kW1Field];
-  __shared__ int ids_s[4][32 * F];
-  // b1 / b2 / w_o via LDS: a global load in layer 2 would wait out its W2 prefetch
-  __shared__ __attribute__((aligned(16))) float b1s[kN1], b2s[kN2], wos[kN2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int c = lane & 31, h = lane >> 5;
-  b1s[tid] = a.b1[tid];  // visible after barrier 0
-  if (tid < kN2) b2s[tid] = a.b2[tid];
-  else wos[tid - kN2] = a.wo[tid - kN2];
-  int* my_ids = ids_s[wave];
-  const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 32;  // this wave's 32 rows
-  const uint4* w1g = reinterpret_cast<const uint4*>(a.w1);
-  uint4* w1l0 = reinterpret_cast<uint4*>(w1s[0]);
-  uint4* w1l1 = reinterpret_cast<uint4*>(w1s[1]);
-
-  // ---- ids of the 32 rows -> LDS (int32); rows past R re-read the last row, never stored
-  {
-    const int64_t last = a.R - 1;
-    constexpr int NT = (32 * F + 63) / 64;
-    int64_t v[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int e = lane + 64 * t;
-      const int row = e / F, f = e - row * F;
-      const int64_t gr = m0 + row <= last ? m0 + row : last;
-      v[t] = e < 32 * F ? a.x[gr * F + f] : 0;
-    }
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-      if (lane + 64 * t < 32 * F) my_ids[lane + 64 * t] = (int)v[t];
-  }
-  // ---- layer 1 over the fields: the gathers of fields f+1..f+R and this wave's quarter of
-  // their W1 images in flight (one register ring: both are waited for at the same depth, so the
-  // in-order vmcnt never waits on a younger field)
-  float4 xa[NB], xb[NB], xw[NB];
-  uint4 wq[NB][4];
-  f32x16 acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
-  float fs[8], fq = 0.0f, fw = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) fs[k] = 0.0f;
-  auto issue = [&](int f, int sl) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) wq[sl][k] = w1g[f * (kW1Field / 8) + 256 * wave + lane + 64 * k];
-    const int id = my_ids[c * F + f];
-    const float4* line = reinterpret_cast<const float4*>(a.P[f] + (int64_t)id * 32);
-    xa[sl] = line[h];
-    xb[sl] = line[2 + h];
-    xw[sl] = line[4 + h];
-  };
-#pragma unroll
-  for (int f = 0; f < R; ++f) issue(f, f);
-#pragma unroll
-  for (int f = 0; f < F; ++f) {
-    const int sl = f % NB;
-    if (f + R < F) issue(f + R, (f + R) % NB);
-    __builtin_amdgcn_sched_barrier(0);
-    // field f's registers "redefined" here: left alone, hipcc consumes each field's loads right
-    // after issuing them (fewer live registers) and so waits on them at once
-    asm volatile("" : "+v"(wq[sl][0].x), "+v"(wq[sl][0].y), "+v"(wq[sl][0].z), "+v"(wq[sl][0].w),
-                 "+v"(wq[sl][1].x), "+v"(wq[sl][1].y), "+v"(wq[sl][1].z), "+v"(wq[sl][1].w));
-    asm volatile("" : "+v"(wq[sl][2].x), "+v"(wq[sl][2].y), "+v"(wq[sl][2].z), "+v"(wq[sl][2].w),
-                 "+v"(wq[sl][3].x), "+v"(wq[sl][3].y), "+v"(wq[sl][3].z), "+v"(wq[sl][3].w));
-    uint4* slot = (f & 1) ? w1l1 : w1l0;
-    if (!(ABL & 2)) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) slot[256 * wave + lane + 64 * k] = wq[sl][k];
-    } else {
-      asm volatile("" :: "v"(wq[sl][0].x), "v"(wq[sl][1].x), "v"(wq[sl][2].x), "v"(wq[sl][3].x));
-    }
-    if (!(ABL & 1)) __syncthreads();  // barrier f: slot f & 1 holds field f (plain global loads survive it)
-    asm volatile("" : "+v"(xa[sl].x), "+v"(xa[sl].y), "+v"(xa[sl].z), "+v"(xa[sl].w), "+v"(xb[sl].x),
-                 "+v"(xb[sl].y), "+v"(xb[sl].z), "+v"(xb[sl].w), "+v"(xw[sl].x), "+v"(xw[sl].y), "+v"(xw[sl].z),
-                 "+v"(xw[sl].w));
-    const __bf16* ws = (f & 1) ? w1s[1] : w1s[0];
-    // W1 fragments of n-tile pair jp + 1 read while pair jp's MFMAs run; pair 0's reads are
-    // issued before the split, whose VALU then covers their latency
-    bf16x8 ah[2][2], al[2][2];
-    auto wread = [&](int jp, int b) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int n = 32 * (2 * jp + q) + c;
-        ah[b][q] = *reinterpret_cast<const bf16x8*>(ws + w1_idx(n, 8 * h));
-        al[b][q] = *reinterpret_cast<const bf16x8*>(ws + 4096 + w1_idx(n, 8 * h));
-      }
-    };
-    wread(0, 0);
-    bf16x8 bh, bl;
-    {
-      const float4 p = xa[sl], q = xb[sl], w = xw[sl];
-      const float v[8] = {p.x, p.y, p.z, p.w, q.x, q.y, q.z, q.w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        fs[k] += v[k];
-        fq += v[k] * v[k];
-        const __bf16 hv = (__bf16)v[k];
-        bh[k] = hv;
-        bl[k] = (__bf16)(v[k] - (float)hv);
-      }
-      // bytes 64..95 of the line: W then zeros (deepfm_pack_k), so the whole 16-B piece sums
-      // to W on h = 0 and to 0 on h = 1 (all four components used: a dword load of the same
-      // line runs at 38 G lines/s in the probe, a 16-B piece at 48 G)
-      fw += (w.x + w.y) + (w.z + w.w);
-    }
-#pragma unroll
-    for (int jp = 0; jp < 4; ++jp) {
-      if (jp + 1 < 4) wread(jp + 1, (jp + 1) & 1);
-      __builtin_amdgcn_sched_barrier(0);
-      const int b = jp & 1;
-      if (ABL & 4) {
-        asm volatile("" :: "v"(al[b][0]), "v"(ah[b][0]), "v"(al[b][1]), "v"(ah[b][1]), "v"(bh), "v"(bl));
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-      }
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int j = 2 * jp + q;
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[b][q], bh, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[b][q], bl, acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[b][q], bh, acc[j], 0, 0, 0);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  // ---- layer 2 in two halves of n2 (64 outputs each: the half's accumulators, the layer-1
-  // accumulators and a 6-deep W2 prefetch ring fit the registers the layer-1 rings leave free).
-  // The 32 (half, k-step) steps are one flat unrolled sequence, so the ring runs across the
-  // halves; B fragments of k-step t = 2j + g2 from acc[j] (deepfm_fused_k order), rebuilt per
-  // half. b1 / b2 / w_o come from LDS: a global load here would wait out the W2 prefetch.
-  float dot = 0.0f;
-  if (ABL & 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(acc[j]));
-  }
-  constexpr int P = 6, NS = 32;
-  bf16x8 w2h[P + 1][2], w2l[P + 1][2];
-  auto w2load = [&](int st) {
-    const int half = st >> 4, t = st & 15, b = st % (P + 1);
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int o = w2_off(t, 32 * (2 * half + q) + c, h);
-      w2h[b][q] = *reinterpret_cast<const bf16x8*>(a.w2hi + o);
-      w2l[b][q] = *reinterpret_cast<const bf16x8*>(a.w2lo + o);
-    }
-  };
-  if (!(ABL & 8)) {
-#pragma unroll
-    for (int st = 0; st < P; ++st) w2load(st);
-  }
-  f32x16 acc2[2];
-#pragma unroll
-  for (int st = 0; st < (ABL & 8 ? 0 : NS); ++st) {
-    const int half = st >> 4, t = st & 15, j = t >> 1, g2 = t & 1, b = st % (P + 1);
-    if (t == 0) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc2[q][r] = 0.0f;
-    }
-    if (st + P < NS) w2load(st + P);
-    __builtin_amdgcn_sched_barrier(0);
-    bf16x8 gh, gl;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const float4 bb = *reinterpret_cast<const float4*>(b1s + 16 * t + 8 * p + 4 * h);
-      const float bv[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = acc[j][4 * (2 * g2 + p) + e] + bv[e];
-        v = v > 0.0f ? v : 0.0f;
-        const __bf16 hv = (__bf16)v;
-        gh[4 * p + e] = hv;
-        gl[4 * p + e] = (__bf16)(v - (float)hv);
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const bf16x8 ah = w2h[b][q], al = w2l[b][q];
-      acc2[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gh, acc2[q], 0, 0, 0);
-      acc2[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gl, acc2[q], 0, 0, 0);
-      acc2[q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gh, acc2[q], 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if (t == 15) {  // relu(H2 + b2) . wo over this half's 64 outputs
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int nb = 32 * (2 * half + q) + 8 * g + 4 * h;
-          const float4 bb = *reinterpret_cast<const float4*>(b2s + nb);
-          const float4 ww = *reinterpret_cast<const float4*>(wos + nb);
-          dot += fmaxf(acc2[q][4 * g + 0] + bb.x, 0.0f) * ww.x;
-          dot += fmaxf(acc2[q][4 * g + 1] + bb.y, 0.0f) * ww.y;
-          dot += fmaxf(acc2[q][4 * g + 2] + bb.z, 0.0f) * ww.z;
-          dot += fmaxf(acc2[q][4 * g + 3] + bb.w, 0.0f) * ww.w;
-        }
-    }
-  }
-  float fm = -fq;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) fm += fs[k] * fs[k];
-  dot += __shfl_xor(dot, 32, 64);
-  fm += __shfl_xor(fm, 32, 64);
-  const float first = fw + __shfl_xor(fw, 32, 64);
-  const int64_t row = m0 + c;
-  if (h == 0 && row < a.R) {
-    const float v = a.bias + first + 0.5f * fm + dot;
-    a.logit[row] = v;
-    if (a.prob) a.prob[row] = 1.0f / (1.0f + expf(-v));
-  }
-}
-
-// deepfm_rows_k with W1 staged by a fifth wave through LDS-DMA instead of the compute waves'
-// register ring + ds_write (timing ablations: the per-field W1 writes and barrier were half of the
-// kernel with L2-resident gathers): the compute waves' only global loads are their gathers.
-// 320 threads (the stager shares a SIMD): 256 registers per wave, so R = 5 and a 3-deep W2 ring.
-// PK = false: the tables as given (V row: two 16-B pieces of its 64 B; W: one dword), for callers
-// without the packed images (rsx_deepfm_fused, or no table cache).
-template <int F, bool PK = true>
+// The row-owning form over the tables as given (V row: two 16-B pieces of its 64 B; W: one dword),
+// for callers without the packed images (rsx_deepfm_fused, or no table cache). Four compute waves
+// of 32 rows; W1 is staged by a fifth wave through LDS-DMA (a register ring + ds_write in the compute
+// waves measured half of the kernel with L2-resident gathers): the compute waves' only global loads
+// are their gathers. 320 threads (the stager shares a SIMD): 256 registers per wave, so R = 4 and a
+// 3-deep W2 ring.
+template <int F>
 __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
-  constexpr int R = 4, NB = R + 1, ABL = 0;
+  constexpr int R = 4, NB = R + 1;
   __shared__ __attribute__((aligned(16))) __bf16 w1s[3][kW1Field];
   __shared__ int ids_s[4][32 * F];
   // b1 / b2 / w_o via LDS: a global load in layer 2 would wait out its W2 prefetch
@@ -1027,18 +804,11 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
   for (int k = 0; k < 8; ++k) fs[k] = 0.0f;
   auto issue = [&](int f, int sl) {
     const int id = my_ids[c * F + f];
-    if constexpr (PK) {
-      const float4* line = reinterpret_cast<const float4*>(a.P[f] + (int64_t)id * 32);
-      xa[sl] = line[h];
-      xb[sl] = line[2 + h];
-      xw[sl] = line[4 + h];
-    } else {
-      const float4* vr = reinterpret_cast<const float4*>(a.V[f] + (int64_t)id * 16);
-      xa[sl] = vr[h];
-      xb[sl] = vr[2 + h];
-      const float wv = (a.W[f] != nullptr && h == 0) ? a.W[f][id] : 0.0f;
-      xw[sl] = make_float4(wv, 0.0f, 0.0f, 0.0f);
-    }
+    const float4* vr = reinterpret_cast<const float4*>(a.V[f] + (int64_t)id * 16);
+    xa[sl] = vr[h];
+    xb[sl] = vr[2 + h];
+    const float wv = (a.W[f] != nullptr && h == 0) ? a.W[f][id] : 0.0f;
+    xw[sl] = make_float4(wv, 0.0f, 0.0f, 0.0f);
   };
 #pragma unroll
   for (int f = 0; f < R; ++f) issue(f, f);
@@ -1078,21 +848,13 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
         bh[k] = hv;
         bl[k] = (__bf16)(v[k] - (float)hv);
       }
-      // bytes 64..95 of the line: W then zeros (deepfm_pack_k), so the whole 16-B piece sums
-      // to W on h = 0 and to 0 on h = 1 (all four components used: a dword load of the same
-      // line runs at 38 G lines/s in the probe, a 16-B piece at 48 G)
-      fw += (w.x + w.y) + (w.z + w.w);
+      fw += (w.x + w.y) + (w.z + w.w);  // W on h = 0, zeros elsewhere (issue)
     }
 #pragma unroll
     for (int jp = 0; jp < 4; ++jp) {
       if (jp + 1 < 4) wread(jp + 1, (jp + 1) & 1);
       __builtin_amdgcn_sched_barrier(0);
       const int b = jp & 1;
-      if (ABL & 4) {
-        asm volatile("" :: "v"(al[b][0]), "v"(ah[b][0]), "v"(al[b][1]), "v"(ah[b][1]), "v"(bh), "v"(bl));
-        __builtin_amdgcn_sched_barrier(0);
-        continue;
-      }
 #pragma unroll
       for (int q = 0; q < 2; ++q) {
         const int j = 2 * jp + q;
@@ -1109,10 +871,6 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
   // halves; B fragments of k-step t = 2j + g2 from acc[j] (deepfm_fused_k order), rebuilt per
   // half. b1 / b2 / w_o come from LDS: a global load here would wait out the W2 prefetch.
   float dot = 0.0f;
-  if (ABL & 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) asm volatile("" :: "v"(acc[j]));
-  }
   constexpr int P = 3, NS = 32;
   bf16x8 w2h[P + 1][2], w2l[P + 1][2];
   auto w2load = [&](int st) {
@@ -1124,13 +882,11 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
       w2l[b][q] = *reinterpret_cast<const bf16x8*>(a.w2lo + o);
     }
   };
-  if (!(ABL & 8)) {
 #pragma unroll
-    for (int st = 0; st < P; ++st) w2load(st);
-  }
+  for (int st = 0; st < P; ++st) w2load(st);
   f32x16 acc2[2];
 #pragma unroll
-  for (int st = 0; st < (ABL & 8 ? 0 : NS); ++st) {
+  for (int st = 0; st < NS; ++st) {
     const int half = st >> 4, t = st & 15, j = t >> 1, g2 = t & 1, b = st % (P + 1);
     if (t == 0) {
 #pragma unroll
@@ -1219,12 +975,10 @@ __device__ __forceinline__ void vm_wait_n(int n) {
 }
 #undef RSX_VMW
 
-// deepfm_rows5_k reorganised around 256-row workgroups (65,536 rows: one round of the grid
-// instead of two) with the layer-1 accumulators in the AGPR file, in two shapes:
-//   MT = 2: four waves of 64 rows (two 32-row m-tiles sharing every W1 fragment read, half the LDS
-//           read traffic per MFMA; 256 accumulator floats, one wave per SIMD);
-//   MT = 1: eight waves of 32 rows (128 accumulator floats, two waves per SIMD).
-// There is no stager wave (no room beside AGPR-holding compute waves): each wave stages its share
+// The row-owning form over the packed tables, around 256-row workgroups (65,536 rows: one round of
+// the grid): 8 / MT waves of MT 32-row m-tiles each. MT = 1 (eight waves of 32 rows, 128 accumulator
+// floats, two waves per SIMD) is the one instantiated; MT = 2 measured slower.
+// There is no stager wave: each wave stages its share
 // of a field's W1 image by LDS-DMA (inline asm: hipcc would drain vmcnt in front of every LDS read
 // if it saw a pending DMA) and waits for it with a counted vmcnt. Field f's work is software-
 // pipelined around barrier B_{f+1}, which sits after its first two n-tile pairs: behind B_{f+1}
@@ -1249,20 +1003,10 @@ __host__ __device__ constexpr int rows2m_after_dma(int g, int R, int iss, int id
 
 constexpr int kRows2mLds = 2 * 16 * kN2 * 16 * 2;  // bytes: the W2 hi + lo images (128 KiB)
 
-#ifndef RSX_DFM_R
-#define RSX_DFM_R 3
-#endif
-#ifndef RSX_DFM_L2PIPE
-#define RSX_DFM_L2PIPE 1  // layer 2: the next step's B fragments built under this step's MFMAs
-#endif
-#ifndef RSX_DFM_ABL
-#define RSX_DFM_ABL 0  // timing probes (wrong results): 1 no field barriers, 2 no W1 DMA in the loop
-#endif
-
-template <int F, int MT, bool L2 = true>
+template <int F, int MT>
 __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
   constexpr int NW = 8 / MT;        // waves per workgroup (256 rows)
-  constexpr int R = RSX_DFM_R, NB = R + 1;  // gather ring: fields in flight ahead of the one computed
+  constexpr int R = 3, NB = R + 1;  // gather ring: fields in flight ahead of the one computed
   constexpr int kIss = 3 * MT;      // global loads per issue() (m-tiles x three 16-B pieces)
   constexpr int kDp = 16 / NW;      // 1-KiB W1 pieces a wave stages per field
   constexpr int kSlots = 4;         // W1 ring
@@ -1276,11 +1020,9 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
   __shared__ __attribute__((aligned(16))) float b1s[kN1], b2s[kN2], wos[kN2];
   __bf16* w1s = reinterpret_cast<__bf16*>(lds);
   int* ids_all = reinterpret_cast<int*>(lds + kSlots * kW1Field * 2);
-  // MT = 2: an AGPR operand anywhere in the kernel keeps hipcc from inferring "no AGPRs", which
-  // selects the VGPR form of every MFMA (the 256 accumulators would then spill). MT = 1: the VGPR
-  // form, 256 architectural registers per wave at two waves per SIMD (with AGPR-form MFMAs the
-  // layer-2 accumulators would not fit beside the layer-1 ones in a 128 / 128 split)
-  if (MT == 2) asm volatile("" ::"a"(0.0f));
+  // MT = 1: the VGPR form of every MFMA, 256 architectural registers per wave at two waves per SIMD
+  // (with AGPR-form MFMAs the layer-2 accumulators would not fit beside the layer-1 ones in a
+  // 128 / 128 split)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 31, h = lane >> 5;
   if (tid < kN1) b1s[tid] = a.b1[tid];
@@ -1307,10 +1049,8 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
 
   const char* w2g = reinterpret_cast<const char*>(a.w2hi);  // w2lo follows w2hi (deepfm_prep_images)
   auto w2dma = [&](int piece) { dma1k(w2g + 1024 * piece, lds_base + 1024 * piece); };
-  if (L2) {
 #pragma unroll
-    for (int k = 0; k < 24 / NW; ++k) w2dma(104 + (24 / NW) * wave_u + k);  // blocks no layer-1 data uses
-  }
+  for (int k = 0; k < 24 / NW; ++k) w2dma(104 + (24 / NW) * wave_u + k);  // blocks no layer-1 data uses
   // ---- ids of the 32 MT rows -> LDS (int32); rows past R re-read the last row, never stored
   {
     const int64_t last = a.R - 1;
@@ -1376,7 +1116,10 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
         bh[st][m][k] = hv;
         bl[st][m][k] = (__bf16)(v[k] - (float)hv);
       }
-      fw[m] += (w.x + w.y) + (w.z + w.w);  // W then zeros (deepfm_pack_k): see deepfm_rows5_k
+      // bytes 64..95 of the line: W then zeros (deepfm_pack_k), so the whole 16-B piece sums
+      // to W on h = 0 and to 0 on h = 1 (all four components used: a dword load of the same
+      // line runs at 38 G lines/s in the probe, a 16-B piece at 48 G)
+      fw[m] += (w.x + w.y) + (w.z + w.w);
       // the FM sums are formed here, field by field: left alone, hipcc sinks the 39-term chains to
       // their use after the field loop and keeps every gathered piece alive until then (spills)
       asm volatile("" : "+v"(fs[m][0]), "+v"(fs[m][1]), "+v"(fs[m][2]), "+v"(fs[m][3]), "+v"(fs[m][4]),
@@ -1410,7 +1153,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
 #pragma unroll
   for (int f = 0; f < R; ++f) issue(f, f);
   __builtin_amdgcn_sched_barrier(0);
-  vm_wait_n(rows2m_after_dma<F>(0, R, kIss, L2 ? kIdp : 0, kDp));  // this wave's quarter of field 0 landed
+  vm_wait_n(rows2m_after_dma<F>(0, R, kIss, kIdp, kDp));  // this wave's quarter of field 0 landed
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // ids, b1 / b2 / w_o stores
   __builtin_amdgcn_s_barrier();  // B_0
   __builtin_amdgcn_sched_barrier(0);
@@ -1422,7 +1165,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
     constexpr int f = decltype(fc)::value;
     constexpr int cs = f & 1;
     if (f + R < F) issue(f + R, (f + R) % NB);
-    if (L2 && f == F - 1 - R) {  // last gather issued: this wave's id region takes W2 pieces
+    if (f == F - 1 - R) {  // last gather issued: this wave's id region takes W2 pieces
 #pragma unroll
       for (int k = 0; k < kIdp; ++k) w2dma(64 + kIdBlk * wave_u + k);
     }
@@ -1437,13 +1180,11 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
     pair_mfma(1, 1, cs);
     __builtin_amdgcn_sched_barrier(0);
     if (f + 1 < F) {
-      if (!(RSX_DFM_ABL & 1)) {
-        vm_wait_n(rows2m_after_dma<F>(f + 1, R, kIss, L2 ? kIdp : 0, kDp));  // this wave's quarter of field f + 1
-        __builtin_amdgcn_s_barrier();                                    // B_{f+1}
-      }
+      vm_wait_n(rows2m_after_dma<F>(f + 1, R, kIss, kIdp, kDp));  // this wave's quarter of field f + 1
+      __builtin_amdgcn_s_barrier();                               // B_{f+1}
       __builtin_amdgcn_sched_barrier(0);
-      if (f + 3 < F && !(RSX_DFM_ABL & 2)) dma(f + 3);
-      if (L2 && f + 1 == F - 1) {  // slots of fields F-4 and F-3 are free: W2 pieces into them
+      if (f + 3 < F) dma(f + 3);
+      if (f + 1 == F - 1) {  // slots of fields F-4 and F-3 are free: W2 pieces into them
         constexpr int s0 = (F - 4) % kSlots, s1 = (F - 3) % kSlots;
 #pragma unroll
         for (int k = 0; k < kDp; ++k) {
@@ -1473,7 +1214,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  if (L2) {  // the last two slots (fields F-2, F-1)
+  {  // the last two slots (fields F-2, F-1)
     constexpr int s0 = (F - 2) % kSlots, s1 = (F - 1) % kSlots;
 #pragma unroll
     for (int k = 0; k < kDp; ++k) {
@@ -1500,12 +1241,6 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
     }
   };
   f32x16 acc2[MT][2];
-  if (!L2) {  // timing ablation (wrong results): layer 1 only (one element per tile kept live)
-#pragma unroll
-    for (int m = 0; m < MT; ++m)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dot[m] += acc[m][j][0] * 1e-30f;
-  }
   // B fragments of step st (relu(H1 + b1) of k-step t = st & 15, split), both m-tiles
   bf16x8 gh[2][MT], gl[2][MT];  // [set][m-tile]
   auto build = [&](int st, int set) {
@@ -1527,10 +1262,8 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
       }
     }
   };
-  if (L2) {
-    w2read(0);
-    if (RSX_DFM_L2PIPE) build(0, 0);
-  }
+  w2read(0);
+  build(0, 0);
   auto step = [&](int st) __attribute__((always_inline)) {
     const int half = st >> 4, t = st & 15, b = st & 1;
     if (t == 0) {
@@ -1542,7 +1275,6 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
           for (int r = 0; r < 16; ++r) acc2[m][q][r] = 0.0f;
     }
     if (st + 1 < NS) w2read(st + 1);
-    if (!RSX_DFM_L2PIPE) build(st, b);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
@@ -1554,7 +1286,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
         acc2[m][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, gh[b][m], acc2[m][q], 0, 0, 0);
       }
     }
-    if (RSX_DFM_L2PIPE && st + 1 < NS) {  // the next step's fragments in this step's MFMA issue gaps
+    if (st + 1 < NS) {  // the next step's fragments in this step's MFMA issue gaps
       build(st + 1, b ^ 1);
 #pragma unroll
       for (int i = 0; i < 6 * MT; ++i) {
@@ -1581,7 +1313,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
     }
   };
 #pragma unroll
-  for (int st = 0; st < (L2 ? NS : 0); ++st) step(st);
+  for (int st = 0; st < NS; ++st) step(st);
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     float fm = -fq[m];
@@ -1620,16 +1352,10 @@ size_t persist_lds_bytes(int id_stride) {
 
 using rsx::cu_count;
 
-bool persist_ok(int F) { return F >= 3 * kFC2 + 1 && F <= kPersistMaxF && getenv("RSX_DEEPFM_PERSIST") == nullptr; }
+bool persist_ok(int F) { return F >= 3 * kFC2 + 1 && F <= kPersistMaxF; }
 
-// row-owning kernel for F = 39 (RSX_DEEPFM_ROWS=0: the persistent kernel, A/B)
-bool rows_ok(int F) {
-  static const bool off = [] {
-    const char* e = getenv("RSX_DEEPFM_ROWS");
-    return e && e[0] == '0';
-  }();
-  return F == kRowsF && !off;
-}
+// row-owning kernels for F = 39
+bool rows_ok(int F) { return F == kRowsF; }
 
 }  // namespace
 
@@ -1706,7 +1432,6 @@ RSX_API int rsx_deepfm_fused_run(const int64_t* x, int64_t R, int F, const float
       r.W[f] = (f < F && W) ? W[f] : nullptr;
     }
     r.R = R;
-    const int64_t grid = (R + 127) / 128;  // 4 compute waves x 32 rows
     r.nit = 1;
     r.bias = bias;
     const int64_t m1 = (int64_t)F * kW1Field, n2 = 16 * kN2 * 16;
@@ -1714,44 +1439,10 @@ RSX_API int rsx_deepfm_fused_run(const int64_t* x, int64_t R, int F, const float
     r.w2hi = wsb + m1;
     r.w2lo = wsb + m1 + n2;
     r.b1 = b1; r.b2 = b2; r.wo = wo; r.logit = logit; r.prob = prob;
-    // RSX_DEEPFM_ROWS (A/B): unset = deepfm_rows2m_k<F, 1> (eight 32-row waves), 2 = <F, 2> (four
-    // 64-row waves), 5 = deepfm_rows5_k, 4 = deepfm_rows_k with RSX_DEEPFM_ABL ablations;
-    // RSX_DEEPFM_ABL with rows2m: layer 1 only (timing, wrong results)
-    static const char mode = [] {
-      const char* e = getenv("RSX_DEEPFM_ROWS");
-      return e && (e[0] == '2' || e[0] == '4' || e[0] == '5') ? e[0] : 'w';
-    }();
-    if (!packed) {
-      hipLaunchKernelGGL((deepfm_rows5_k<kRowsF, false>), dim3((unsigned)grid), dim3(320), 0, st, r);
-      RSX_LAUNCHED();
-      return 0;
-    }
-    if (mode == 'w' || mode == '2') {
-      const bool l1 = getenv("RSX_DEEPFM_ABL") != nullptr;
-      const dim3 g((unsigned)((R + 255) / 256));  // 256 rows per workgroup
-      if (mode == 'w' && l1) hipLaunchKernelGGL((deepfm_rows2m_k<kRowsF, 1, false>), g, dim3(512), 0, st, r);
-      else if (mode == 'w') hipLaunchKernelGGL((deepfm_rows2m_k<kRowsF, 1>), g, dim3(512), 0, st, r);
-      else if (l1) hipLaunchKernelGGL((deepfm_rows2m_k<kRowsF, 2, false>), g, dim3(256), 0, st, r);
-      else hipLaunchKernelGGL((deepfm_rows2m_k<kRowsF, 2>), g, dim3(256), 0, st, r);
-      RSX_LAUNCHED();
-      return 0;
-    }
-    if (mode == '5') {
-      hipLaunchKernelGGL((deepfm_rows5_k<kRowsF, true>), dim3((unsigned)grid), dim3(320), 0, st, r);
-      RSX_LAUNCHED();
-      return 0;
-    }
-    const char* abl_env = getenv("RSX_DEEPFM_ABL");  // timing ablations (diagnostic only)
-    const int abl = abl_env ? atoi(abl_env) : 0;
-    switch (abl) {
-      case 1: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 1>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      case 3: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 3>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      case 4: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 4>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      case 8: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 8>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      case 12: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 12>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      case 15: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 15>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-      default: hipLaunchKernelGGL((deepfm_rows_k<kRowsF, 0>), dim3((unsigned)grid), dim3(256), 0, st, r); break;
-    }
+    if (packed)  // 256 rows per workgroup
+      hipLaunchKernelGGL((deepfm_rows2m_k<kRowsF, 1>), dim3((unsigned)((R + 255) / 256)), dim3(512), 0, st, r);
+    else  // 4 compute waves x 32 rows
+      hipLaunchKernelGGL(deepfm_rows5_k<kRowsF>, dim3((unsigned)((R + 127) / 128)), dim3(320), 0, st, r);
     RSX_LAUNCHED();
     return 0;
   }

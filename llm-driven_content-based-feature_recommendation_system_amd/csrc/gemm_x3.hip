@@ -365,9 +365,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_k(GArgs a) {
 // The summation order over k is a fixed permutation (k-step s of a chunk takes k = 16s + 4h
 // + {0..3} and 16s + 8 + 4h + {0..3}); B's fragments use the same permutation, so each
 // product is the plain sum over k. Same epilogues and dropout hash as gemm_x3_nt_k.
-// WV = 4: one wave per SIMD with the whole 512-register file, three A chunks per wave (one being
-// computed, two in flight); WV = 8: two waves per SIMD (256 registers each), two chunks per wave
-// (the other wave's loads and stores in flight while one computes).
+// Four waves per workgroup: one wave per SIMD with the whole 512-register file, two A chunks per
+// wave (one being computed, one in flight).
 
 struct WsArgs {
   GArgs g;
@@ -375,12 +374,13 @@ struct WsArgs {
   int groups;   // workgroups per column block
 };
 
-// PF (WV = 4): the next 16-k step's B fragments are read from LDS while this step's MFMAs run (one wave
-// per SIMD has no other wave to cover an LDS round trip; without PF hipcc re-reads each fragment right
-// before its MFMA and waits for it), with two A chunks per wave instead of three for the registers.
-template <int KC, int NBW, int EPI, int WV, bool PF = false>
-__global__ __launch_bounds__(64 * WV, 1) void gemm_ws_k(WsArgs w) {
-  constexpr int kWsThreads = 64 * WV, kWsWaves = WV;
+constexpr int kWsWaves = 4, kWsThreads = 64 * kWsWaves;
+
+// The next 16-k step's B fragments are read from LDS while this step's MFMAs run (one wave per SIMD
+// has no other wave to cover an LDS round trip; left alone hipcc re-reads each fragment right before
+// its MFMA and waits for it).
+template <int KC, int NBW, int EPI>
+__global__ __launch_bounds__(kWsThreads, 1) void gemm_ws_k(WsArgs w) {
   constexpr int NT = NBW / 32;
   __shared__ __attribute__((aligned(16))) u32x4 sW[KC * 8 * NT * 2 * 64];
   const GArgs& a = w.g;
@@ -464,49 +464,31 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_ws_k(WsArgs w) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) z[j][g] = *reinterpret_cast<const float4*>(xrow + 32 * j + 8 * g);
     }
-    if constexpr (PF) {
-      u32x4 wf[2][NT][2];
-      auto wload = [&](int s, u32x4 (&wd)[NT][2]) {
-        const u32x4* wp = sW + ((q * 8 + s) * NT) * 128 + lane;
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          wd[j][0] = wp[j * 128];
-          wd[j][1] = wp[j * 128 + 64];
-        }
-      };
-      wload(0, wf[0]);
-#pragma unroll
-      for (int s = 0; s < 8; ++s) {
-        if (s + 1 < 8) wload(s + 1, wf[(s + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);  // keep the reads here: hipcc otherwise sinks each to its MFMA
-        u32x4 hi, lo;
-        split8(buf[2 * s], buf[2 * s + 1], hi, lo);
-        const bf16x8 xh = __builtin_bit_cast(bf16x8, hi), xl = __builtin_bit_cast(bf16x8, lo);
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-          const bf16x8 wh = __builtin_bit_cast(bf16x8, wf[s & 1][j][0]);
-          const bf16x8 wl = __builtin_bit_cast(bf16x8, wf[s & 1][j][1]);
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc[j], 0, 0, 0);
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc[j], 0, 0, 0);
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc[j], 0, 0, 0);
-        }
-      }
-    } else {
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-      u32x4 hi, lo;
-      split8(buf[2 * s], buf[2 * s + 1], hi, lo);
-      const bf16x8 xh = __builtin_bit_cast(bf16x8, hi), xl = __builtin_bit_cast(bf16x8, lo);
+    u32x4 wf[2][NT][2];
+    auto wload = [&](int s, u32x4 (&wd)[NT][2]) {
       const u32x4* wp = sW + ((q * 8 + s) * NT) * 128 + lane;
 #pragma unroll
       for (int j = 0; j < NT; ++j) {
-        const bf16x8 wh = __builtin_bit_cast(bf16x8, wp[j * 128]);
-        const bf16x8 wl = __builtin_bit_cast(bf16x8, wp[j * 128 + 64]);
+        wd[j][0] = wp[j * 128];
+        wd[j][1] = wp[j * 128 + 64];
+      }
+    };
+    wload(0, wf[0]);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      if (s + 1 < 8) wload(s + 1, wf[(s + 1) & 1]);
+      __builtin_amdgcn_sched_barrier(0);  // keep the reads here: hipcc otherwise sinks each to its MFMA
+      u32x4 hi, lo;
+      split8(buf[2 * s], buf[2 * s + 1], hi, lo);
+      const bf16x8 xh = __builtin_bit_cast(bf16x8, hi), xl = __builtin_bit_cast(bf16x8, lo);
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const bf16x8 wh = __builtin_bit_cast(bf16x8, wf[s & 1][j][0]);
+        const bf16x8 wl = __builtin_bit_cast(bf16x8, wf[s & 1][j][1]);
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xh, acc[j], 0, 0, 0);
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xl, acc[j], 0, 0, 0);
         acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xh, acc[j], 0, 0, 0);
       }
-    }
     }
     if (q != KC - 1) return;
     // epilogue. Rows past M loaded A row M-1 and computed exactly row M-1's values; they are
@@ -613,44 +595,20 @@ __global__ __launch_bounds__(64 * WV, 1) void gemm_ws_k(WsArgs w) {
   // loop then carry the same outstanding-load pattern, so the compiler's vmcnt waits stay
   // per buffer instead of draining the prefetches. The trailing re-loads are never used.
   const int last = nitems - 1;
-  if constexpr (WV == 8 || PF) {
-    float4 b0[16], b1[16];
-    load(0, b0);
-    load(last < 1 ? last : 1, b1);
-    for (int t = 0;; t += 2) {
-      WS_FENCE;
-      compute(t, b0);
-      WS_FENCE;
-      load(t + 2 < last ? t + 2 : last, b0);
-      if (t + 1 > last) break;
-      WS_FENCE;
-      compute(t + 1, b1);
-      WS_FENCE;
-      load(t + 3 < last ? t + 3 : last, b1);
-      if (t + 2 > last) break;
-    }
-    return;
-  }
-  float4 b0[16], b1[16], b2[16];
+  float4 b0[16], b1[16];
   load(0, b0);
   load(last < 1 ? last : 1, b1);
-  load(last < 2 ? last : 2, b2);
-  for (int t = 0;; t += 3) {
+  for (int t = 0;; t += 2) {
     WS_FENCE;
     compute(t, b0);
     WS_FENCE;
-    load(t + 3 < last ? t + 3 : last, b0);
+    load(t + 2 < last ? t + 2 : last, b0);
     if (t + 1 > last) break;
     WS_FENCE;
     compute(t + 1, b1);
     WS_FENCE;
-    load(t + 4 < last ? t + 4 : last, b1);
+    load(t + 3 < last ? t + 3 : last, b1);
     if (t + 2 > last) break;
-    WS_FENCE;
-    compute(t + 2, b2);
-    WS_FENCE;
-    load(t + 5 < last ? t + 5 : last, b2);
-    if (t + 3 > last) break;
   }
 #undef WS_FENCE
 }
@@ -677,9 +635,8 @@ bool ws_enabled() {
   return on == 1;
 }
 
-template <int KC, int NBW, int WV, bool PF = false>
-void launch_ws_w(const GArgs& g, hipStream_t st) {
-  constexpr int kWsThreads = 64 * WV, kWsWaves = WV;
+template <int KC, int NBW>
+void launch_ws(const GArgs& g, hipStream_t st) {
   WsArgs w;
   w.g = g;
   w.nblk = g.N / NBW;
@@ -690,75 +647,27 @@ void launch_ws_w(const GArgs& g, hipStream_t st) {
   if (groups > blocks_rows) groups = (int)blocks_rows;
   w.groups = groups;
   const int grid = (w.nblk * groups + 7) / 8 * 8;
-  if (g.epi == EPI_BIAS) hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_BIAS, WV, PF>), dim3(grid), dim3(kWsThreads), 0, st, w);
+  if (g.epi == EPI_BIAS) hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_BIAS>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else if (g.epi == EPI_ROWADD)
-    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_ROWADD, WV, PF>), dim3(grid), dim3(kWsThreads), 0, st, w);
+    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_ROWADD>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else if (g.epi == EPI_ADDLN)
-    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_ADDLN, WV, PF>), dim3(grid), dim3(kWsThreads), 0, st, w);
+    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_ADDLN>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else if (g.epi == EPI_GELU_DROP)
-    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_GELU_DROP, WV, PF>), dim3(grid), dim3(kWsThreads), 0, st, w);
-  else hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_DGELU_DROP, WV, PF>), dim3(grid), dim3(kWsThreads), 0, st, w);
+    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_GELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
+  else hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_DGELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
 }
 
-// RSX_GEMM_WS_WAVES = 4 | 8 (A/B): waves per weight-stationary workgroup
-int ws_waves() {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("RSX_GEMM_WS_WAVES");
-    v = (e && e[0] == '8') ? 8 : 4;
-  }
-  return v;
-}
-
-// RSX_GEMM_DEEP = 0 | 1 (A/B): the LDS-staged GEMM with four stages in flight when its tiles fit the chip
-bool deep_prefetch() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RSX_GEMM_DEEP");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
 bool a_nk_long(int K) { return K / kBK >= 16; }
 // the few-tile forms stage 32 of K per barrier (one workgroup per CU: half the barriers and stage
-// overheads; 80 KB of LDS) when K allows it; RSX_GEMM_FEW_BK=16 keeps 16 (A/B)
-int few_bk(int K) {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("RSX_GEMM_FEW_BK");
-    v = (e && atoi(e) == 16) ? 16 : 32;
-  }
-  return (v == 32 && K % 32 == 0) ? 32 : 16;
-}
-
-// RSX_GEMM_WS_PF = 0 | 1 (A/B): four waves with the B-fragment prefetch (PF) or without
-bool ws_pf() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("RSX_GEMM_WS_PF");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-template <int KC, int NBW>
-void launch_ws(const GArgs& g, hipStream_t st) {
-  if (ws_waves() == 8) launch_ws_w<KC, NBW, 8>(g, st);
-  else if (ws_pf()) launch_ws_w<KC, NBW, 4, true>(g, st);
-  else launch_ws_w<KC, NBW, 4>(g, st);
-}
+// overheads; 80 KB of LDS) when K allows it
+int few_bk(int K) { return K % 32 == 0 ? 32 : 16; }
 
 // split-K plan of the LDS-staged path: with fewer output tiles than CUs (one workgroup per CU at most,
 // e.g. the text BERT's 768-wide GEMMs at a few thousand tokens) and a long K, S K-ranges of >= 256 per
 // tile (S in {8, 4, 3, 2}, tiles * S <= 4 * CUs); M = 3,000 (tools/gemm_bert_micro.py): 768 x 3072 0.135 ->
-// 0.101 ms, 768 x 2304 0.105 -> 0.083 ms. 1 = no split. RSX_GEMM_SPLITK=0 disables it.
+// 0.101 ms, 768 x 2304 0.105 -> 0.083 ms. 1 = no split.
 int split_plan(int64_t M, int N, int K) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("RSX_GEMM_SPLITK");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || N % kBN || K % kBK || (K == 128 || K == 256 || K == 384)) return 1;
+  if (N % kBN || K % kBK || (K == 128 || K == 256 || K == 384)) return 1;
   const int64_t tiles = ((M + kBM - 1) / kBM) * (N / kBN);
   const int cus = num_cus();
   if (tiles >= cus) return 1;
@@ -828,7 +737,7 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
   const int64_t blocks = (tiles + g.per - 1) / g.per;
   const int grid = (int)((blocks + 7) / 8 * 8);
   // few tiles for the chip (one workgroup per CU at most) and a long K: four stages in flight per workgroup
-  if (deep_prefetch() && g.per == 1 && blocks <= num_cus() && a_nk_long(K)) {
+  if (g.per == 1 && blocks <= num_cus() && a_nk_long(K)) {
     const bool b32 = few_bk(K) == 32;
     if (epi == EPI_BIAS && b32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4, 32>), dim3(grid), dim3(256), 0, st, g);
     else if (epi == EPI_BIAS) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4>), dim3(grid), dim3(256), 0, st, g);

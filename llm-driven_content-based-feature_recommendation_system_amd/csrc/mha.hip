@@ -635,24 +635,6 @@ struct Col4 {  // 4 consecutive token rows of one column, split
   s16x4 hi, lo;
 };
 
-__device__ __forceinline__ Row8 load_row8(const float* base, int64_t ld, int row, bool ok, int g) {
-  float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-  if (ok) {
-    const float4* p = reinterpret_cast<const float4*>(base + (int64_t)row * ld + 8 * g);
-    v0 = p[0];
-    v1 = p[1];
-  }
-  const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-  Row8 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 h = (__bf16)f[k];
-    r.hi[k] = h;
-    r.lo[k] = (__bf16)(f[k] - (float)h);
-  }
-  return r;
-}
-
 __device__ __forceinline__ Col4 split4(const float (&f)[4]) {
   bf16x4 h, l;
 #pragma unroll
@@ -665,14 +647,6 @@ __device__ __forceinline__ Col4 split4(const float (&f)[4]) {
   c.hi = __builtin_bit_cast(s16x4, h);
   c.lo = __builtin_bit_cast(s16x4, l);
   return c;
-}
-
-// column col of rows row0 .. row0+3 (zero past L)
-__device__ __forceinline__ Col4 load_col4(const float* base, int64_t ld, int row0, int L, int col) {
-  float f[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) f[t] = (row0 + t < L) ? base[(int64_t)(row0 + t) * ld + col] : 0.0f;
-  return split4(f);
 }
 
 __device__ __forceinline__ f32x4 dot16_x3(const Row8& a, const Row8& b) {
@@ -690,95 +664,11 @@ __device__ __forceinline__ f32x4 sum16_x3(const Col4& a, const Col4& b, f32x4 ac
   return acc;
 }
 
-__global__ __launch_bounds__(256) void mha_fwd_x3_k(FwdArgs a) {
-  constexpr int DH = 32;
-  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int D = a.H * DH;
-  const int64_t ld = 3 * (int64_t)D;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = (L + 15) >> 4;
-  const float* Qb = a.qkv + tok0 * ld + hd * DH;
-  const float* Kb = Qb + D;
-  const float* Vb = Qb + 2 * D;
-  float* Ob = a.out + tok0 * D + hd * DH;
-  const int my_pad = (lane < L) ? (a.kpad ? (int)a.kpad[tok0 + lane] : 0) : 1;
-
-  for (int qb = 0; qb < nb; ++qb) {
-    const int i = 16 * qb + c;  // query of this lane's score column
-    const bool iok = i < L;
-    const Row8 qx = load_row8(Qb, ld, i, iok, g);
-    const int kb_end = a.causal ? qb : nb - 1;
-    f32x4 s[4];
-    float m = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      if (kb <= kb_end) {
-        const Row8 kx = load_row8(Kb, ld, 16 * kb + c, 16 * kb + c < L, g);
-        s[kb] = dot16_x3(kx, qx);  // S^T: [key 16kb+4g+r][query i]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = 16 * kb + 4 * g + r;
-          const int jpad = __shfl(my_pad, j & 63, 64);
-          const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i);
-          s[kb][r] = allowed ? s[kb][r] * a.scale : -INFINITY;
-          m = fmaxf(m, s[kb][r]);
-        }
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      if (kb <= kb_end) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float p = (s[kb][r] == -INFINITY) ? 0.0f : __expf(s[kb][r] - m);
-          s[kb][r] = p;
-          l += p;
-        }
-      }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = (l > 0.0f) ? 1.0f / l : 0.0f;
-    f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const uint64_t rowidx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax;
-#pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      if (kb <= kb_end) {
-        float p[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) p[r] = a.drop.apply(s[kb][r] * inv, rowidx + 16 * kb + 4 * g + r);
-        const Col4 pa = split4(p);
-#pragma unroll
-        for (int et = 0; et < 2; ++et) o[et] = sum16_x3(pa, load_col4(Vb, ld, 16 * kb + 4 * g, L, 16 * et + c), o[et]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * qb + 4 * g + r;
-      if (row < L) {
-        Ob[(int64_t)row * D + c] = o[0][r];
-        Ob[(int64_t)row * D + 16 + c] = o[1][r];
-      }
-    }
-    if (a.lse && g == 0 && iok) a.lse[(tok0 + i) * a.H + hd] = (l > 0.0f) ? m + logf(l) : -INFINITY;
-  }
-}
-
 // Forward with every operand load issued before the first use: the sequence's Q and K rows and
 // V columns of this head for all NB 16-token blocks come in through one buffer resource over the
 // sequence's rows (rows >= L read as zero by the range check: no branches, no per-load waits),
-// so a wave pays one memory latency instead of one or two per query block (mha_fwd_x3_k
-// re-loads K / V per query block behind data-dependent branches). Same arithmetic, masks,
-// dropout hash and lse as mha_fwd_x3_k.
+// so a wave pays one memory latency instead of one or two per query block (loading K / V per
+// query block behind data-dependent branches).
 typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ Row8 split_row8(const u32x4b& x0, const u32x4b& x1) {
   const float f[8] = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w),
@@ -1029,152 +919,13 @@ __global__ __launch_bounds__(256, 3) void mha_fwd_x3b_k(FwdArgs a) {
   else mha_fwd_x3b_seq<4>(a, hd, tok0, L, lane);
 }
 
-__global__ __launch_bounds__(256) void mha_bwd_x3_k(BwdArgs a) {
-  constexpr int DH = 32;
-  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int D = a.H * DH;
-  const int64_t ld = 3 * (int64_t)D;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = (L + 15) >> 4;
-  const float* Qb = a.qkv + tok0 * ld + hd * DH;
-  const float* Kb = Qb + D;
-  const float* Vb = Qb + 2 * D;
-  const float* dOb = a.dout + tok0 * D + hd * DH;
-  const float* Ob = a.out + tok0 * D + hd * DH;
-  float* dQb = a.dqkv + tok0 * ld + hd * DH;
-  float* dKb = dQb + D;
-  float* dVb = dQb + 2 * D;
-  const float sc = a.scale;
-
-  // per-token softmax statistics (token t < L on lane t): lse_t, delta_t = dO_t . O_t, key pad
-  float my_lse = -INFINITY, my_delta = 0.0f;
-  int my_pad = 1;
-  if (lane < L) {
-    my_lse = a.lse[(tok0 + lane) * a.H + hd];
-    const float4* op = reinterpret_cast<const float4*>(Ob + (int64_t)lane * D);
-    const float4* gp = reinterpret_cast<const float4*>(dOb + (int64_t)lane * D);
-    float d = 0.0f;
-#pragma unroll
-    for (int t = 0; t < DH / 4; ++t) {
-      const float4 x = op[t], y = gp[t];
-      d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    my_delta = d;
-    my_pad = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
-  }
-  // dS_ij and the dropped-out probability Pd_ij of one score element (mha_bwd_k's formulas)
-  auto grad_elem = [&](int i, int j, float s, float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
-    pd_out = 0.0f;
-    if (!allowed) return 0.0f;
-    const float p = __expf(s * sc - lse_i);
-    float pd = p, dpd = dp;
-    if (a.drop.active()) {
-      const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-      const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-      pd = keep ? p * a.drop.scale : 0.0f;
-      dpd = keep ? dp * a.drop.scale : 0.0f;
-    }
-    pd_out = pd;
-    return p * (dpd - delta_i) * sc;
-  };
-
-  // ---- pass 1: key block on the score columns (j = 16kb + c): dK, dV ----
-  for (int kb = 0; kb < nb; ++kb) {
-    const int j = 16 * kb + c;
-    const bool jok = j < L;
-    const int jpad = __shfl(my_pad, j & 63, 64);
-    const Row8 kx = load_row8(Kb, ld, j, jok, g);
-    const Row8 vx = load_row8(Vb, ld, j, jok, g);
-    f32x4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    for (int qb = a.causal ? kb : 0; qb < nb; ++qb) {
-      const int iq = 16 * qb + c;
-      const Row8 qx = load_row8(Qb, ld, iq, iq < L, g);
-      const Row8 gx = load_row8(dOb, D, iq, iq < L, g);
-      f32x4 S = dot16_x3(qx, kx);   // [query 16qb+4g+r][key j]
-      f32x4 dP = dot16_x3(gx, vx);  // [query][key]
-      float ds[4], pd[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * qb + 4 * g + r;
-        const float lse_i = __shfl(my_lse, i & 63, 64);
-        const float del_i = __shfl(my_delta, i & 63, 64);
-        const bool allowed = jok && i < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
-        ds[r] = grad_elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd[r]);
-      }
-      const Col4 pa = split4(pd), sa = split4(ds);
-#pragma unroll
-      for (int et = 0; et < 2; ++et) {
-        dv[et] = sum16_x3(pa, load_col4(dOb, D, 16 * qb + 4 * g, L, 16 * et + c), dv[et]);  // dV[j][e]
-        dk[et] = sum16_x3(sa, load_col4(Qb, ld, 16 * qb + 4 * g, L, 16 * et + c), dk[et]);  // dK[j][e]
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * kb + 4 * g + r;
-      if (row < L) {
-#pragma unroll
-        for (int et = 0; et < 2; ++et) {
-          dKb[(int64_t)row * ld + 16 * et + c] = dk[et][r];
-          dVb[(int64_t)row * ld + 16 * et + c] = dv[et][r];
-        }
-      }
-    }
-  }
-
-  // ---- pass 2: query block on the score columns (i = 16qb + c): dQ ----
-  for (int qb = 0; qb < nb; ++qb) {
-    const int i = 16 * qb + c;
-    const bool iok = i < L;
-    const float lse_i = __shfl(my_lse, i & 63, 64);
-    const float del_i = __shfl(my_delta, i & 63, 64);
-    const Row8 qx = load_row8(Qb, ld, i, iok, g);
-    const Row8 gx = load_row8(dOb, D, i, iok, g);
-    f32x4 dq[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const int kb_end = a.causal ? qb : nb - 1;
-    for (int kb = 0; kb <= kb_end; ++kb) {
-      const int jr = 16 * kb + c;
-      const Row8 kx = load_row8(Kb, ld, jr, jr < L, g);
-      const Row8 vx = load_row8(Vb, ld, jr, jr < L, g);
-      f32x4 St = dot16_x3(kx, qx);   // [key 16kb+4g+r][query i]
-      f32x4 dPt = dot16_x3(vx, gx);  // [key][query]
-      float ds[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int j = 16 * kb + 4 * g + r;
-        const int jpad = __shfl(my_pad, j & 63, 64);
-        const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
-        float pd;
-        ds[r] = grad_elem(i, j, St[r], dPt[r], lse_i, del_i, allowed, pd);
-      }
-      const Col4 sa = split4(ds);
-#pragma unroll
-      for (int et = 0; et < 2; ++et)
-        dq[et] = sum16_x3(sa, load_col4(Kb, ld, 16 * kb + 4 * g, L, 16 * et + c), dq[et]);  // dQ[i][e]
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * qb + 4 * g + r;
-      if (row < L) {
-        dQb[(int64_t)row * ld + c] = dq[0][r];
-        dQb[(int64_t)row * ld + 16 + c] = dq[1][r];
-      }
-    }
-  }
-}
-
 // ---- bf16x3 backward, software-pipelined ----------------------------------------------------
-// mha_bwd_x3_k's wave per (sequence, head) and its two passes, with each pass's (key block,
+// One wave per (sequence, head) and two passes (pass 1: key block on the score columns, dK and dV;
+// pass 2: query block on the score columns, dQ), with each pass's (key block,
 // query block) pairs walked as one flat sequence: the operands of pair n+1 are loaded (buffer
 // loads over the sequence's rows: rows past L, and the pair after the last, read as zero by the
 // range check, so no load is predicated) while pair n computes, in two ping-pong register sets
-// so that no in-flight load is copied. mha_bwd_x3_k waits one memory latency per pair.
+// so that no in-flight load is copied (loading per pair waits one memory latency each).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t seq_rsrc(const void* base, unsigned bytes) {
   const uintptr_t bp = (uintptr_t)base;
   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)bp);
@@ -1876,11 +1627,8 @@ RSX_API int rsx_mha_fwd_x3(const float* qkv, const uint8_t* key_pad, const int* 
   a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
   a.scale = 1.0f / sqrtf((float)Dh);
   a.drop = rsx::make_dropout(p_drop, seed);
-  static const bool legacy = getenv("RSX_MHA_FWD_LEGACY") != nullptr;  // A/B: the per-block-load kernel
   if (Dh == 64)
     hipLaunchKernelGGL(mha_fwd_x3b64_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else if (legacy)
-    hipLaunchKernelGGL(mha_fwd_x3_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(mha_fwd_x3b_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
   RSX_LAUNCHED();
@@ -1921,11 +1669,7 @@ RSX_API int rsx_mha_bwd_x3(const float* qkv, const uint8_t* key_pad, const int* 
   a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
   a.scale = 1.0f / sqrtf((float)Dh);
   a.drop = rsx::make_dropout(p_drop, seed);
-  static const bool legacy = getenv("RSX_MHA_BWD_LEGACY") != nullptr;  // A/B: one latency per pair
-  static const bool stash = getenv("RSX_MHA_BWD_STASH") == nullptr || getenv("RSX_MHA_BWD_STASH")[0] != '0';
-  if (legacy)
-    hipLaunchKernelGGL(mha_bwd_x3_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else if (causal && stash)
+  if (causal)
     hipLaunchKernelGGL(mha_bwd_x3s_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(mha_bwd_x3p_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);

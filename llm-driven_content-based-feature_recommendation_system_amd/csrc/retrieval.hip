@@ -427,14 +427,14 @@ __global__ __launch_bounds__(256) void topk_final_k(const float* bs, const int* 
 //     (the last term covers both fp32 accumulations, each < 2^-16 relative). Round 4 used the
 //     elementwise worst case (2^-7 + 2^-12) ||u|| W; the residual norms are ~0.58 of it on spread
 //     data, so the band of scores above t_q (the appends of P3) and the margin set of P4 narrow.
-// P1 (topk_bf16_scan_k<MODE 0>): a strided sample of the corpus (every S-th 32-item tile of each
+// P1 (topk_bf16_scan_k): a strided sample of the corpus (every S-th 32-item tile of each
 //     split, S ~ 8 nsplit / k so that ~4 collected entries per stream are expected in P3) over
 //     ns0 <= nsplit splits (sample_nsplit); each lane keeps its best T0 sample scores in registers
 //     (T0 = 1 where 2 ns0 >= 2k: a compare and two selects per score, no sorted insert).
 // P2 (topk_bf16_thresh_k): per query, c_k = k-th best of the sampled candidates. The k sampled
 //     items with a >= c_k have e >= c_k - delta, so the true k-th best exact score e_k >= c_k -
 //     delta, and every true top-k item has a >= e_k - delta >= c_k - 2 delta =: t_q.
-// P3 (topk_bf16_scan_k<MODE 1>): the one full scan; every (a, j) with a >= t_q is appended to
+// P3 (topk_bf16_collect_k): the one full scan; every (a, j) with a >= t_q is appended to
 //     its lane's stream buffer (cap kStreamCap; ~0.25 % of the items on spread data).
 // P4 (topk_bf16_select_k): per query, gather the appended entries, sort by a; a_k = k-th; every
 //     entry with a >= a_k - 2 delta (the only ones that can reach the exact k-th) is rescored in
@@ -505,16 +505,16 @@ struct BfArgs {
   int64_t Q, NI, ldu;
   int nsplit, nqb, sample;
   int64_t span;
-  float* cand_s;       // MODE 0: [Q][nsplit][2][T], each stream's list sorted desc
+  float* cand_s;       // P1: [Q][nsplit][2][T], each stream's list sorted desc
   int* cand_i;
-  const float* thr;    // MODE 1: [Q] collection threshold t_q
-  // MODE 1: [Q][nsplit][2][kStreamCap] entries (score, item id as float bits): one 8-B store per
+  const float* thr;    // P3: [Q] collection threshold t_q
+  // P3: [Q][nsplit][2][kStreamCap] entries (score, item id as float bits): one 8-B store per
   // append (two separate 4-B arrays made two write requests of a partial line each)
   float2* buf_e;
-  int* buf_n;          // MODE 1: [Q][nsplit][2] appended count (may exceed the cap: overflow)
+  int* buf_n;          // P3: [Q][nsplit][2] appended count (may exceed the cap: overflow)
 };
 
-template <int G, int T, int MODE>
+template <int G, int T>
 __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sI[2][kTile * kImgStride];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -526,12 +526,10 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
   const int64_t q0 = (int64_t)qb * (128 * G) + wave * (32 * G) + c;
   bf16x8 ub[G][8];
   bool q_ok[G];
-  float thr[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     const int64_t q = q0 + 32 * g;
     q_ok[g] = q < a.Q;
-    thr[g] = (MODE == 1 && q_ok[g]) ? a.thr[q] : INFINITY;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
       float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
@@ -547,24 +545,17 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
   const int64_t j_begin = (int64_t)split * a.span;
   int64_t j_end = j_begin + a.span;
   if (j_end > a.NI) j_end = a.NI;
-  const int64_t step = MODE == 0 ? (int64_t)kTile * a.sample : kTile;
+  const int64_t step = (int64_t)kTile * a.sample;
 
   float ts[G][T];
   int ti[G][T];
-  int cnt[G];
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    cnt[g] = 0;
+  for (int g = 0; g < G; ++g)
 #pragma unroll
     for (int t = 0; t < T; ++t) { ts[g][t] = -INFINITY; ti[g][t] = 0x7fffffff; }
-  }
   int64_t sbase[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) sbase[g] = ((q0 + 32 * g) * a.nsplit + split) * 2 + h;
-  float2* bep[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g)  // MODE 1 stream buffers of this lane's queries
-    bep[g] = MODE == 1 ? a.buf_e + sbase[g] * kStreamCap : nullptr;
 
   // staging: 8 threads per item row, each moving 16-B piece (tid & 7) of both 128-B halves (the
   // 8 threads of a row write 128 contiguous bytes per store: no bank conflicts, as in
@@ -608,41 +599,32 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
         for (int g = 0; g < G; ++g) acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, ub[g][ks], acc[g], 0, 0, 0);
       }
       // item ids in 32 bits (NI < 2^31, host-checked) and the split-end check only on the split's
-      // last tile. MODE 0 first compares a lane's tile max (v_max3) with its list minimum: the
-      // sorted insert is then skipped by most lanes once the lists have filled. (In MODE 1 about
-      // 0.25 % of the scores pass t_q, but some lane of a wave passes on ~90 % of the tiles, so a
-      // per-lane gate would not skip work there.)
+      // last tile. A lane's tile max (v_max3) is first compared with its list minimum: the
+      // sorted insert is then skipped by most lanes once the lists have filled.
       const int jt0 = (int)j0;
       const bool full_tile = j0 + kTile <= j_end;
       const int jend = (int)j_end;
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         if (!q_ok[g]) continue;
-        if (MODE == 0) {
-          float mx = fmaxf(acc[g][0], acc[g][1]);
+        float mx = fmaxf(acc[g][0], acc[g][1]);
 #pragma unroll
-          for (int r = 2; r < 16; r += 2) mx = fmaxf(mx, fmaxf(acc[g][r], acc[g][r + 1]));
-          if (!(mx > ts[g][T - 1])) continue;  // no score of this lane enters its list
-        }
+        for (int r = 2; r < 16; r += 2) mx = fmaxf(mx, fmaxf(acc[g][r], acc[g][r + 1]));
+        if (!(mx > ts[g][T - 1])) continue;  // no score of this lane enters its list
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int j = jt0 + tile_row(r, h);
           const float sc = acc[g][r];
-          if (MODE == 0) {
-            if (sc > ts[g][T - 1] && (full_tile || j < jend)) {
-              ts[g][T - 1] = sc;
-              ti[g][T - 1] = j;
+          if (sc > ts[g][T - 1] && (full_tile || j < jend)) {
+            ts[g][T - 1] = sc;
+            ti[g][T - 1] = j;
 #pragma unroll
-              for (int t = T - 1; t > 0; --t) {
-                if (ts[g][t] > ts[g][t - 1]) {
-                  const float fs = ts[g][t]; ts[g][t] = ts[g][t - 1]; ts[g][t - 1] = fs;
-                  const int fi = ti[g][t]; ti[g][t] = ti[g][t - 1]; ti[g][t - 1] = fi;
-                }
+            for (int t = T - 1; t > 0; --t) {
+              if (ts[g][t] > ts[g][t - 1]) {
+                const float fs = ts[g][t]; ts[g][t] = ts[g][t - 1]; ts[g][t - 1] = fs;
+                const int fi = ti[g][t]; ti[g][t] = ti[g][t - 1]; ti[g][t - 1] = fi;
               }
             }
-          } else if (sc >= thr[g] && (full_tile || j < jend)) {
-            if (cnt[g] < kStreamCap) bep[g][cnt[g]] = make_float2(sc, __int_as_float(j));
-            ++cnt[g];
           }
         }
       }
@@ -654,20 +636,16 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
 #pragma unroll
   for (int g = 0; g < G; ++g) {
     if (!q_ok[g]) continue;
-    if (MODE == 0) {
 #pragma unroll
-      for (int t = 0; t < T; ++t) {
-        a.cand_s[sbase[g] * T + t] = ts[g][t];
-        a.cand_i[sbase[g] * T + t] = ti[g][t];
-      }
-    } else {
-      a.buf_n[sbase[g]] = cnt[g];
+    for (int t = 0; t < T; ++t) {
+      a.cand_s[sbase[g] * T + t] = ts[g][t];
+      a.cand_i[sbase[g] * T + t] = ti[g][t];
     }
   }
 }
 
 // P3 as its own kernel (round 4): the one full scan, with every (a, j), a >= t_q, appended to its
-// lane's stream buffer. Against round 3's topk_bf16_scan_k<G, 8, 1> (a compare-and-append branch
+// lane's stream buffer. Against round 3's full scan inside topk_bf16_scan_k (a compare-and-append branch
 // per score: ~3 VALU + 5 SALU for each of a lane's 32 scores per tile):
 //   * a max gate: each lane takes the max of its 16 scores of a query group (v_max3) and only
 //     lanes whose max reaches t_q go on (one divergent branch per query group and tile);
@@ -675,8 +653,7 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
 //     check only on its last tile) and the append as one 8-B (score, id) store -- t_q lets ~0.25 %
 //     of the scores through, so some lane of a wave passes on ~90 % of the (tile, group) pairs and
 //     the appends, not the MFMAs, set the kernel's time (the same kernel with the gate but no
-//     appends runs 0.83 ms, the MFMA floor is ~0.5 ms). EXTRACT (RSX_TOPK_COLLECT=1) appends
-//     max-first instead (the lane's max, knocked out, repeated while the new max passes);
+//     appends runs 0.83 ms, the MFMA floor is ~0.5 ms);
 //   * a clamped slot instead of a capacity branch: a stream that overflows keeps counting and its
 //     query goes to the exact kernels (P4), so what lands in its last slot is never read;
 //   * staging stores without bank conflicts: the 8 threads of an item row write its two 128-B
@@ -688,10 +665,9 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_scan_k(BfArgs a) {
 // a loader wave filling a 4-slot LDS ring by LDS-DMA (3.24 ms: 2 compute waves per SIMD instead of
 // 3), a per-wave LDS event queue drained one event per lane (1.60 / 1.91 ms), the appends placed
 // after the next tile's staging store (1.67 ms), a second accumulator set pipelining the compares
-// under the next tile's MFMAs (2.49 ms). The entries of a stream are the same set in every form;
-// their order within the stream differs with EXTRACT, which P4 never sees (its margin set and
-// final sort use the total order (score desc, index asc)).
-template <int G, bool EXTRACT, bool BALLOT = false>
+// under the next tile's MFMAs (2.49 ms), max-first appends (the lane's max, knocked out, repeated
+// while the new max passes), each append behind a wave-uniform ballot branch (1.69 vs 1.50 ms).
+template <int G>
 __global__ __launch_bounds__(256, 2) void topk_bf16_collect_k(BfArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char sI[2][kTile * kImgStride];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -763,49 +739,16 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_collect_k(BfArgs a) {
       float m3 = fmaxf(fmaxf(acc[g][9], acc[g][10]), acc[g][11]);
       float m4 = fmaxf(fmaxf(acc[g][12], acc[g][13]), acc[g][14]);
       const float mx = fmaxf(fmaxf(fmaxf(m0, m1), fmaxf(m2, m3)), fmaxf(m4, acc[g][15]));
-      // wave-uniform gate: skip the group unless some lane's max reaches its threshold
-      if (BALLOT && !__builtin_amdgcn_ballot_w64(mx >= thr[g])) continue;
       if (!(mx >= thr[g])) continue;  // most lanes: no collected item of this query in the tile
-      if (EXTRACT) {
-        float v[16];
+      if (full) {  // whole tile inside the split: one compare per score
 #pragma unroll
-        for (int r = 0; r < 16; ++r) v[r] = acc[g][r];
-        float m = mx;
-        // at most 16 rounds (t_q = -inf lets every score through)
-        for (int it = 0; it < 16 && m >= thr[g]; ++it) {
-          int rs = 15;
-#pragma unroll
-          for (int r = 14; r >= 0; --r) rs = v[r] == m ? r : rs;  // lowest position holding the max
-          const int j = jt0 + tile_row(rs, h);
-          if (full || j < jend) append(g, m, j);
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = r == rs ? -INFINITY : v[r];
-          const float n0 = fmaxf(fmaxf(v[0], v[1]), v[2]);
-          const float n1 = fmaxf(fmaxf(v[3], v[4]), v[5]);
-          const float n2 = fmaxf(fmaxf(v[6], v[7]), v[8]);
-          const float n3 = fmaxf(fmaxf(v[9], v[10]), v[11]);
-          const float n4 = fmaxf(fmaxf(v[12], v[13]), v[14]);
-          m = fmaxf(fmaxf(fmaxf(n0, n1), fmaxf(n2, n3)), fmaxf(n4, v[15]));
-        }
-      } else if (full) {  // whole tile inside the split: one compare per score
-        // BALLOT (A/B, RSX_TOPK_COLLECT=3): each append behind a wave-uniform branch on the ballot of
-        // its compare. The compiler already skips empty append bodies (s_cbranch_execnz to
-        // out-of-line blocks); the ballots only add SALU (4096 x 1M: 1.69 vs 1.50 ms)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const bool pass = acc[g][r] >= thr[g];
-          if (!BALLOT || __builtin_amdgcn_ballot_w64(pass)) {
-            if (pass) append(g, acc[g][r], jt0 + tile_row(r, h));
-          }
-        }
+        for (int r = 0; r < 16; ++r)
+          if (acc[g][r] >= thr[g]) append(g, acc[g][r], jt0 + tile_row(r, h));
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int j = jt0 + tile_row(r, h);
-          const bool pass = acc[g][r] >= thr[g] && (full || j < jend);
-          if (!BALLOT || __builtin_amdgcn_ballot_w64(pass)) {
-            if (pass) append(g, acc[g][r], j);
-          }
+          if (acc[g][r] >= thr[g] && j < jend) append(g, acc[g][r], j);
         }
       }
     }
@@ -1241,21 +1184,13 @@ BfPlan bf_plan(int64_t Q, int64_t NI, int64_t k) {
   p.sample = S;
   // the sample's candidates must hold k items: 2 nsplit T >= 2 k
   p.use = NI > 16384 && k <= 512 && 2 * ns * p.T >= 2 * k;
-  static const bool off = getenv("RSX_TOPK_BF16") != nullptr && getenv("RSX_TOPK_BF16")[0] == '0';
-  if (off) p.use = false;
   return p;
 }
 
-// splits of the P1 sample scan: nsplit / 4 (>= 8, a multiple of 8 like nsplit) unless
-// RSX_TOPK_SAMPLE_DIV names another divisor (1 = the full split count, the round-3 form); at
-// least k / T splits, so the 2 ns0 T candidates hold 2k (bf_plan's condition for nsplit)
+// splits of the P1 sample scan: nsplit / 4 (>= 8, a multiple of 8 like nsplit); at least k / T
+// splits, so the 2 ns0 T candidates hold 2k (bf_plan's condition for nsplit)
 int sample_nsplit(int nsplit, int64_t k, int T) {
-  static const int div = [] {
-    const char* e = getenv("RSX_TOPK_SAMPLE_DIV");
-    const int v = e ? atoi(e) : 4;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 4;
-  }();
-  int ns0 = nsplit / div;
+  int ns0 = nsplit / 4;
   if (ns0 < 8) ns0 = 8;
   while (ns0 < nsplit && 2 * (int64_t)ns0 * T < 2 * k) ns0 *= 2;
   if (ns0 > nsplit) ns0 = nsplit;
@@ -1269,26 +1204,12 @@ int sample_nsplit(int nsplit, int64_t k, int T) {
 // checks it per query; a query that fails runs on the exact kernels, whose latency is that of a
 // whole batch). r = clamp(ceil(3 k / S), 32, k) keeps S r >= 3k with r >= 32 candidates behind the
 // estimate (tools/retrieval_micro.py, 4096 spread queries: no fallback down to r = 25 at k = 100,
-// 2 at r = 17; k = 10 at r = 3: 88); RSX_TOPK_RANK_DIV=d forces r = ceil(k / d) (A/B).
+// 2 at r = 17; k = 10 at r = 3: 88).
 int thr_rank(int k, int S) {
-  static const int div = [] {
-    const char* e = getenv("RSX_TOPK_RANK_DIV");
-    const int v = e ? atoi(e) : 0;
-    return v >= 1 && v <= 16 ? v : 0;
-  }();
-  int r = div ? (k + div - 1) / div : (3 * k + S - 1) / S;
-  if (!div && r < 32) r = 32;
+  int r = (3 * k + S - 1) / S;
+  if (r < 32) r = 32;
   if (r > k) r = k;
   return r < 1 ? 1 : r;
-}
-
-// RSX_TOPK_SAMPLE_T1=0: the sample scan keeps T best per lane stream (A/B)
-bool sample_t1() {
-  static const bool on = [] {
-    const char* e = getenv("RSX_TOPK_SAMPLE_T1");
-    return !(e && e[0] == '0');
-  }();
-  return on;
 }
 
 int choose_nsplit(int64_t Q, int64_t NI, int kmax) {
@@ -1443,20 +1364,20 @@ int run_bf16_chunk(const BfPlan& bp, const BfLayout& L, const float* U, int64_t 
   // compare-swap) where 4 nsplit can (k = 500 at 1M items: 3.19 -> 2.52 ms per 4096-query call
   // against T0 = T = 8), else T0 = T
   BfArgs b0 = b;
-  const int T0 = !sample_t1() ? bp.T : bp.nsplit >= k ? 1 : 2 * bp.nsplit >= k ? 2 : bp.T;
+  const int T0 = bp.nsplit >= k ? 1 : 2 * bp.nsplit >= k ? 2 : bp.T;
   const int ns0 = sample_nsplit(bp.nsplit, k, T0);
   b0.nsplit = ns0;
   b0.span = ((NI + ns0 - 1) / ns0 + kTile - 1) / kTile * kTile;
   const dim3 grid0((unsigned)(bp.nqb * ns0));
   if (T0 == 1) {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 1, 0>), grid0, dim3(256), 0, st, b0);
-    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 1, 0>), grid0, dim3(256), 0, st, b0);
+    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 1>), grid0, dim3(256), 0, st, b0);
+    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 1>), grid0, dim3(256), 0, st, b0);
   } else if (T0 == 2) {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 2, 0>), grid0, dim3(256), 0, st, b0);
-    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 2, 0>), grid0, dim3(256), 0, st, b0);
+    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 2>), grid0, dim3(256), 0, st, b0);
+    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 2>), grid0, dim3(256), 0, st, b0);
   } else {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 8, 0>), grid0, dim3(256), 0, st, b0);
-    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 8, 0>), grid0, dim3(256), 0, st, b0);
+    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 8>), grid0, dim3(256), 0, st, b0);
+    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 8>), grid0, dim3(256), 0, st, b0);
   }
   RSX_LAUNCHED();
   const int ncand = ns0 * 2 * T0;
@@ -1472,25 +1393,8 @@ int run_bf16_chunk(const BfPlan& bp, const BfLayout& L, const float* U, int64_t 
     hipLaunchKernelGGL(topk_bf16_thresh_k<4096>, dim3((unsigned)Q), dim3(256), 0, st, b.cand_s, b.cand_i, ncand, U,
                        ldu, r, wmax, thr);
   RSX_LAUNCHED();
-  // RSX_TOPK_COLLECT (A/B): 2 (default) topk_bf16_collect_k, per-score appends behind the max gate;
-  // 1 its max-first extraction; 0 topk_bf16_scan_k<G, 8, 1> (round 3's full scan)
-  static const int collect_k = [] {
-    const char* e = getenv("RSX_TOPK_COLLECT");
-    return e ? atoi(e) : 2;
-  }();
-  if (collect_k == 1) {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_collect_k<2, true>), grid, dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((topk_bf16_collect_k<1, true>), grid, dim3(256), 0, st, b);
-  } else if (collect_k == 0) {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_scan_k<2, 8, 1>), grid, dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((topk_bf16_scan_k<1, 8, 1>), grid, dim3(256), 0, st, b);
-  } else if (collect_k == 3) {  // A/B: each append behind a wave-uniform ballot branch (slower: 1.69 vs 1.50 ms)
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_collect_k<2, false, true>), grid, dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((topk_bf16_collect_k<1, false, true>), grid, dim3(256), 0, st, b);
-  } else {
-    if (bp.G == 2) hipLaunchKernelGGL((topk_bf16_collect_k<2, false>), grid, dim3(256), 0, st, b);
-    else hipLaunchKernelGGL((topk_bf16_collect_k<1, false>), grid, dim3(256), 0, st, b);
-  }
+  if (bp.G == 2) hipLaunchKernelGGL(topk_bf16_collect_k<2>, grid, dim3(256), 0, st, b);
+  else hipLaunchKernelGGL(topk_bf16_collect_k<1>, grid, dim3(256), 0, st, b);
   RSX_LAUNCHED();
   hipLaunchKernelGGL(topk_bf16_select_k, dim3((unsigned)Q), dim3(256), 0, st, b.buf_e, b.buf_n,
                      bp.nsplit * 2, U, ldu, I, ldi, (int)k, wmax, thr, r < k ? 1 : 0, out_scores, out_idx, qcount,

@@ -306,7 +306,7 @@ struct BwdCtx {
 // position and table rows (the LN recompute and the gate dot reuse the same table rows) — so a
 // lane has U x (1 + NL) id -> row chains in flight instead of one at a time. NL = kMaxTab is the
 // generic more-than-two-live-tables form (slots guarded by lv.n).
-template <int D, int U, int NL, int ABL, bool SC>
+template <int D, int U, int NL, bool SC>
 __device__ __forceinline__ void bwd_groups(const BwdArgs& a, const BwdLive& lv, const BwdCtx& cx, int64_t r00,
                                            float4& acc_w, float4& acc_b, float* acc_l) {
   constexpr int LPR = D / 4;
@@ -348,7 +348,7 @@ __device__ __forceinline__ void bwd_groups(const BwdArgs& a, const BwdLive& lv, 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       ev[u][k] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (NL > 0 && (NL != kMaxTab || k < lv.n) && need_e && !(ABL & 2))
+      if (NL > 0 && (NL != kMaxTab || k < lv.n) && need_e)
         ev[u][k] = ldg4(lv.tab[k] + id[u][k] * D + 4 * c);
     }
   if (cx.do_ln) {  // recompute x in the forward's op order: base, + E_j[id] * g_j (j ascending), + pos
@@ -393,8 +393,7 @@ __device__ __forceinline__ void bwd_groups(const BwdArgs& a, const BwdLive& lv, 
       dx.z = (dh.z - c1 - xh.z * c2) * rs;
       dx.w = (dh.w - c1 - xh.w * c2) * rs;
     }
-    if (a.dbase && !(ABL & 4)) reinterpret_cast<float4*>(a.dbase + r * D)[c] = dx;
-    if (ABL & 1) continue;
+    if (a.dbase) reinterpret_cast<float4*>(a.dbase + r * D)[c] = dx;
     if (!SC) {  // position / small-table sums come from seq_embed_keysum_k over dbase
       if (a.dgate) {
 #pragma unroll
@@ -460,16 +459,15 @@ constexpr int kSmallMax = 8192;  // floats (32 KiB)
 // gradients fold in registers; big-table rows are scatter-added with global float atomics.
 // The LDS and global scatter paths are kept apart so no flat (address-space-generic)
 // atomics are emitted.
-// ABL: timing ablations only (results wrong): 1 no LDS / global scatter, 2 no table-row loads,
-// 4 no dbase store (RSX_SEQ_EMBED_BWD_ABL, tools/seq_embed_step_micro.py)
 // SC = false: no scatter at all (every table gradient and the positions come from the sorted
 // segment sums / seq_embed_keysum_k over dbase); only LN weight / bias and gate sums, and only
 // those columns of the partial row are written.
-template <int D, int ABL, bool SC = true, int UB = 2>
+template <int D, bool SC = true>
 __global__ __launch_bounds__(256) void seq_embed_bwd_k(BwdArgs a) {
   constexpr int LPR = D / 4;
   constexpr int RPW = 64 / LPR;
   constexpr int NW = 4;
+  constexpr int UB = 2;  // row groups per wave iteration (up to two live tables)
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];  // [L*D] positions + small tables
   __shared__ __attribute__((aligned(16))) float s_red[NW][2][D];
   __shared__ __attribute__((aligned(16))) float s_xr[NW][RPW][D];  // per-wave dx rows (layout change)
@@ -529,13 +527,13 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_k(BwdArgs a) {
   BwdCtx cx{&s_xr[wave][sub][0], s_pos, s_small, r_begin, r_end, wave, sub, c, w, do_ln};
   if (lv.n <= 2) {
     for (int64_t r00 = r_begin; r00 < r_end; r00 += UB * NW * RPW) {
-      if (lv.n == 2) bwd_groups<D, UB, 2, ABL, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
-      else if (lv.n == 1) bwd_groups<D, UB, 1, ABL, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
-      else bwd_groups<D, UB, 0, ABL, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
+      if (lv.n == 2) bwd_groups<D, UB, 2, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
+      else if (lv.n == 1) bwd_groups<D, UB, 1, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
+      else bwd_groups<D, UB, 0, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
     }
   } else {
     for (int64_t r00 = r_begin; r00 < r_end; r00 += NW * RPW)
-      bwd_groups<D, 1, kMaxTab, ABL, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
+      bwd_groups<D, 1, kMaxTab, SC>(a, lv, cx, r00, acc_w, acc_b, acc_l);
   }
 #pragma unroll
   for (int j = 0; j < kMaxTab; ++j) {
@@ -838,35 +836,14 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_reduce_k(ReduceArgs a) {
   if (dst) *dst += v;
 }
 
-// row groups per wave iteration (seq_embed_fwd_k U); RSX_SEQ_EMBED_FWD_U in {1,2,4,8} overrides
-// (tuning experiments)
-int fwd_groups_setting() {
-  static int u = [] {
-    const char* s = getenv("RSX_SEQ_EMBED_FWD_U");
-    const int v = s ? atoi(s) : 2;
-    return (v == 1 || v == 2 || v == 4 || v == 8) ? v : 2;
-  }();
-  return u;
-}
-
-template <int D, int U>
-void launch_fwd_u(const FwdArgs& a, hipStream_t st) {
+template <int D>
+int launch_fwd(const FwdArgs& a, hipStream_t st) {
+  constexpr int U = 2;  // row groups per wave iteration
   const int64_t rows_per_block = 4 * (64 / (D / 4)) * U;
   int64_t blocks = (a.T + rows_per_block - 1) / rows_per_block;
   if (blocks > 16384) blocks = 16384;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL((seq_embed_fwd_k<D, U>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-}
-
-template <int D>
-int launch_fwd(const FwdArgs& a, hipStream_t st) {
-  switch (fwd_groups_setting()) {
-    case 1: launch_fwd_u<D, 1>(a, st); break;
-    case 2: launch_fwd_u<D, 2>(a, st); break;
-    case 8: launch_fwd_u<D, 8>(a, st); break;
-    case 4: launch_fwd_u<D, 4>(a, st); break;
-    default: launch_fwd_u<D, 2>(a, st); break;
-  }
   return 0;
 }
 
@@ -874,26 +851,11 @@ template <int D>
 int launch_bwd(const BwdArgs& a, hipStream_t st, bool keysum) {
   const int64_t blocks = (a.f.T + a.rows_per_block - 1) / a.rows_per_block;
   if (keysum) {  // no scatter: positions / small tables from seq_embed_keysum_k
-    static const int ub = [] {
-      const char* e = getenv("RSX_SEQ_EMBED_BWD_U");
-      return e ? atoi(e) : 2;
-    }();
-    if (ub == 4) hipLaunchKernelGGL((seq_embed_bwd_k<D, 0, false, 4>), dim3((unsigned)blocks), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((seq_embed_bwd_k<D, 0, false, 2>), dim3((unsigned)blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((seq_embed_bwd_k<D, false>), dim3((unsigned)blocks), dim3(256), 0, st, a);
     return 0;
   }
   const size_t lds = (size_t)(a.f.L * D + a.small_total) * sizeof(float);
-  static const int abl = [] {
-    const char* e = getenv("RSX_SEQ_EMBED_BWD_ABL");
-    return e ? atoi(e) : 0;
-  }();
-  switch (abl) {
-    case 1: hipLaunchKernelGGL((seq_embed_bwd_k<D, 1>), dim3((unsigned)blocks), dim3(256), lds, st, a); break;
-    case 2: hipLaunchKernelGGL((seq_embed_bwd_k<D, 2>), dim3((unsigned)blocks), dim3(256), lds, st, a); break;
-    case 3: hipLaunchKernelGGL((seq_embed_bwd_k<D, 3>), dim3((unsigned)blocks), dim3(256), lds, st, a); break;
-    case 7: hipLaunchKernelGGL((seq_embed_bwd_k<D, 7>), dim3((unsigned)blocks), dim3(256), lds, st, a); break;
-    default: hipLaunchKernelGGL((seq_embed_bwd_k<D, 0>), dim3((unsigned)blocks), dim3(256), lds, st, a); break;
-  }
+  hipLaunchKernelGGL((seq_embed_bwd_k<D>), dim3((unsigned)blocks), dim3(256), lds, st, a);
   return 0;
 }
 

@@ -417,11 +417,8 @@ int wgrad_launch(bool x3, const float* dY, int64_t ldy, const float* X, int64_t 
   const int blocks = a.tiles_n * a.tiles_k * a.nsplit;
   // 16-token stages measured faster for three or more output row tiles (tools/gemm_micro.py wgrad_384x128:
   // 0.119 vs 0.146 ms) and slower for fewer (wgrad_128x256: 0.075 vs 0.068 ms).
-  static const int stage16_min_tiles = [] {  // RSX_WGRAD_STAGE16_TILES: A/B of the stage choice
-    const char* e = getenv("RSX_WGRAD_STAGE16_TILES");
-    return e ? atoi(e) : 3;
-  }();
-  if (x3 && a.tiles_n >= stage16_min_tiles) hipLaunchKernelGGL(wgrad_x3_k<16>, dim3(blocks), dim3(256), 0, st, a);
+  constexpr int kStage16MinTiles = 3;
+  if (x3 && a.tiles_n >= kStage16MinTiles) hipLaunchKernelGGL(wgrad_x3_k<16>, dim3(blocks), dim3(256), 0, st, a);
   else if (x3) hipLaunchKernelGGL(wgrad_x3_k<32>, dim3(blocks), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(wgrad_k, dim3(blocks), dim3(256), 0, st, a);
   RSX_LAUNCHED();

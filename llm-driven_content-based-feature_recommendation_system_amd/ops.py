@@ -279,7 +279,7 @@ def seq_embed(base, ids, tables, gate, pos, ln_w, ln_b, eps=1e-5, p_drop=0.0, pa
 
 # ----------------------------------------------------------------------------------------
 # A3 / A9: masked MHA core
-# "bf16x3" (default): head dim 32 runs mha_fwd_x3_k / mha_bwd_x3_k (split-bf16 MFMA, ~2^-17
+# "bf16x3" (default): head dim 32 runs rsx_mha_fwd_x3 / rsx_mha_bwd_x3 (split-bf16 MFMA, ~2^-17
 # relative error per product); other head dims and "fp32" run the fp32 kernels.
 MHA_PRECISIONS = ("fp32", "bf16x3")
 _mha_precision = os.environ.get("RSX_MHA_PRECISION", "bf16x3")

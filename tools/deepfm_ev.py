@@ -24,7 +24,6 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--uniform", action="store_true")
     ap.add_argument("--zero", action="store_true")
-    ap.add_argument("--abl", default="0", help="comma list of RSX_DEEPFM_ABL values to time in turn")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     F = 39
@@ -43,21 +42,17 @@ def main():
     args = (N.ptr(x), a.rows, F, st["V"], st["W"], st["P"], float(model.out.bias.item()), st["b1"], st["b2"],
             st["wo"], st["ws"], N.ptr(logit), N.ptr(prob), N.stream())
     ids = "zero" if a.zero else ("uniform" if a.uniform else "zipf1.1")
-    for abl in a.abl.split(","):
-        os.environ["RSX_DEEPFM_ABL"] = abl
-        for _ in range(5):
-            N.check(N.lib().rsx_deepfm_fused_run(*args), "run")
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.iters):
-            N.lib().rsx_deepfm_fused_run(*args)
-        e1.record()
-        torch.cuda.synchronize()
-        ms = e0.elapsed_time(e1) / a.iters
-        print(json.dumps({"ids": ids, "abl": abl, "ms": round(ms, 4), "rows_per_s": round(a.rows / ms * 1e3)}),
-              flush=True)
-    os.environ.pop("RSX_DEEPFM_ABL", None)
+    for _ in range(5):
+        N.check(N.lib().rsx_deepfm_fused_run(*args), "run")
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(a.iters):
+        N.lib().rsx_deepfm_fused_run(*args)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / a.iters
+    print(json.dumps({"ids": ids, "ms": round(ms, 4), "rows_per_s": round(a.rows / ms * 1e3)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """rsx_gemm_x3 at the text BERT's token-GEMM shapes (M = 3,000 packed tokens, bert-base widths: QKV
 2304 x 768, out-projection 768 x 768, FFN 3072 x 768 with the GELU epilogue and 768 x 3072), where the
 output tiles number fewer than the CUs. Prints ms per call, TF/s (bf16x3 products counted once) and a
-checksum per shape; RSX_GEMM_DEEP=0 / 1 selects the one-stage / four-stage prefetch (checksums equal).
+checksum per shape.
 
   python tools/gemm_bert_micro.py --tokens 3000 --iters 20
 """
@@ -27,7 +27,7 @@ def main():
     dev = torch.device("cuda", 0)
     T = args.tokens
     g = torch.Generator(device="cpu").manual_seed(0)
-    res = {"tokens": T, "deep": os.environ.get("RSX_GEMM_DEEP", "1")}
+    res = {"tokens": T}
     shapes = [("qkv_2304x768", 2304, 768, 0), ("out_768x768", 768, 768, 0), ("ffn1_3072x768_gelu", 3072, 768, 1),
               ("ffn2_768x3072", 768, 3072, 0), ("dx_768x2304", 768, 2304, 0)]
     for name, n, k, epi in shapes:

@@ -71,7 +71,7 @@ def main():
     kms = [float(kev[i]) for i in range(max(nk, 0))]
     flops = 4.0 * n * int(grp.uniq.numel()) * 128
     out = {"rows": n, "distinct_targets": int(grp.uniq.numel()), "precision": args.precision,
-           "env_fwdg": os.environ.get("RSX_NCE_FWDG", ""), "loss_sum": float(s.item()),
+           "loss_sum": float(s.item()),
            "grad_u_abs_sum": float(U.grad.abs().sum().item()) / args.iters,
            "grad_b_abs_sum": float(B.grad.abs().sum().item()) / args.iters,
            "fwd_kernel_ms": round(sum(kms) / len(kms), 4) if kms else None,

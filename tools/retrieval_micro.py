@@ -1,6 +1,6 @@
 """Micro-benchmark of rsx_retrieve_topk at configs[4]'s shape (Q = 4096 normalised queries,
 1M-item normalised corpus, k = 100). Prints avg ms per call, the fallback flag and a checksum
-of the indices. RSX_TOPK_BF16=0 selects the previous two-pass fp32 path (A/B).
+of the indices.
 
   python tools/retrieval_micro.py --iters 10
 """
@@ -43,8 +43,7 @@ def main():
     flops = 2.0 * args.q * args.items * 128
     if args.save:
         torch.save({"s": s.cpu(), "i": i.cpu()}, args.save)
-    print(json.dumps({"path": "legacy-two-pass" if os.environ.get("RSX_TOPK_BF16") == "0" else "bf16-single-scan",
-                      "avg_ms": round(ms, 4), "algorithmic_TFLOPs": round(flops / ms / 1e9, 2),
+    print(json.dumps({"avg_ms": round(ms, 4), "algorithmic_TFLOPs": round(flops / ms / 1e9, 2),
                       "fallback_queries": diag.get("fallback_queries"), "idx_checksum": int(i.sum().item()),
                       "score_sum": float(s.double().sum().item())}))
 

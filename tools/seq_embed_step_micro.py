@@ -3,7 +3,7 @@ call (T ~ 316k tokens of 8192 users, positions consecutive per user segment), it
 47,064 rows (its gradient through the sorted segment sums, as the step does), time table 12
 rows, the other four tables gated off (the reference's s_mask), LayerNorm, dropout 0.2.
 Prints avg ms of the forward and of the backward (the rsx_seq_embed_bwd op window plus the
-segment sums). RSX_SEQ_EMBED_BWD_ABL selects a timing ablation of the backward kernel.
+segment sums).
 
   python tools/seq_embed_step_micro.py --iters 20
 """
@@ -66,8 +66,7 @@ def main():
         torch.autograd.grad(out, ins, gy, retain_graph=True, allow_unused=True)
     e[2].record()
     torch.cuda.synchronize()
-    print(json.dumps({"T": T, "abl": os.environ.get("RSX_SEQ_EMBED_BWD_ABL", "0"),
-                      "fwd_ms": round(e[0].elapsed_time(e[1]) / args.iters, 4),
+    print(json.dumps({"T": T, "fwd_ms": round(e[0].elapsed_time(e[1]) / args.iters, 4),
                       "bwd_ms": round(e[1].elapsed_time(e[2]) / args.iters, 4)}))
 
 
