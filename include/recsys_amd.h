@@ -151,7 +151,9 @@ int rsx_nce_bwd_x3(const float* A, const float* B, const float* bias, const int*
  * K mined logits alone and out2 is recomputed. Then rsx_nce_bwd(_x3) gives the dense gradient and
  * rsx_nce_emphasis_bwd adds the mined entries' extra (e^margin - 1) softmax weight into dA [N,128] / dB [M,128]
  * (nullable; dB by vector atomics: the summation order of a column shared by several rows is not fixed).
- * Mined ids outside [0, M) are skipped. O(N K) work and memory. */
+ * Mined ids outside [0, M) are skipped. O(N K) work and memory.
+ * Precondition: the K mined ids of one row are distinct (a repeated id is counted twice where the
+ * reference's scatter_ sets it once; rsx_hnm_mine's top-k never repeats one). */
 int rsx_nce_emphasis_fwd(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b,
                          const int64_t* top, int64_t N, int64_t M, int64_t K, int64_t lda, int64_t ldb,
                          int64_t diag_offset, float tau, float margin, int precision, int nsplit_fwd, float* ws,
@@ -190,7 +192,9 @@ int rsx_nce_emphasis_bwd_csr(const float* A, const float* B, const float* bias, 
  *            products, v1_usertower_train.py:787, with fp32 accumulation; RSX_NCE_F16_GP=2 adds the
  *            lo image); in the column pass the logits take two of the three products (the streamed rows'
  *            lo image dropped: ~2e-5 on unit vectors); elsewhere
- *            (rsx_nce_grouped_fwd, the row pass) as RSX_NCE_BF16X3. */
+ *            (rsx_nce_grouped_fwd, the row pass) as RSX_NCE_BF16X3.
+ *            Precondition of RSX_NCE_F16: every component of A and B has |x| < 256, so that x * 2^8
+ *            stays inside fp16's range; the callers pass unit-norm rows. */
 #define RSX_NCE_FP32 0
 #define RSX_NCE_BF16X3 1
 #define RSX_NCE_F16 2

@@ -187,18 +187,24 @@ def lib():
     return _lib if _lib is not None else load()
 
 
-def source_hash() -> str:
-    """sha256 (first 16 hex digits) of the library's sources in this tree, in csrc/Makefile's order
-    (the .hip files sorted by name, rsx_common.h, include/recsys_amd.h): equal to
-    rsx_build_hash() of a library built from them."""
+def source_files() -> list:
+    """The library's sources in this tree, in the order csrc/Makefile hashes them: the .hip files
+    sorted by name, the internal headers csrc/*.h sorted by name, include/recsys_amd.h."""
     import glob
+    here = os.path.dirname(os.path.abspath(__file__))
+    csrc = os.path.join(here, "csrc")
+    files = []
+    for ext in ("*.hip", "*.h"):
+        files += sorted(glob.glob(os.path.join(csrc, ext)), key=lambda f: os.path.basename(f).encode())
+    return files + [os.path.join(os.path.dirname(here), "include", "recsys_amd.h")]
+
+
+def source_hash() -> str:
+    """sha256 (first 16 hex digits) of source_files(): equal to rsx_build_hash() of a library built
+    from them."""
     import hashlib
-    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-    files = sorted(glob.glob(os.path.join(csrc, "*.hip")), key=lambda f: os.path.basename(f).encode())
-    files += [os.path.join(csrc, "rsx_common.h"),
-              os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "recsys_amd.h")]
     h = hashlib.sha256()
-    for f in files:
+    for f in source_files():
         with open(f, "rb") as fh:
             h.update(fh.read())
     return h.hexdigest()[:16]

@@ -9,7 +9,7 @@
 // at batch 4096) is huge and N, K <= 512 are small, so the GEMMs are bandwidth-bound once the
 // products leave the fp32 MFMA: each fp32 operand x is split x = hi + lo (hi = bf16(x),
 // lo = bf16(x - hi)) while it is staged into LDS, and a product is hi*hi' + hi*lo' + lo*hi'
-// on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the arithmetic of infonce.hip's
+// on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (the arithmetic of nce_mfma.h's
 // bf16x3 loss: ~2^-17 relative error per product, 5.3x fewer MFMA cycles than the fp32 MFMA).
 //
 // Epilogues (fusing the FFN's elementwise work into its two GEMMs):

@@ -1,0 +1,299 @@
+// Internal header of the contrastive-loss (InfoNCE) units nce_*.hip (file map: DESIGN.md, section 4).
+// Kernels stay in an anonymous namespace of their own file; only host launchers cross files.
+#pragma once
+#include "rsx_common.h"
+#include <math.h>
+#include <algorithm>
+#include <type_traits>
+
+namespace rsx {
+namespace nce {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kD = 128;        // embedding width (fixed by the reference: d_model=128)
+constexpr int kTile = 32;      // streamed rows per tile
+constexpr int kWaves = 4;      // waves per workgroup
+constexpr int kOwnRows = 32 * kWaves;  // owner rows per workgroup
+constexpr int kLdsStride = kD + 4;     // padded row (conflict-free ds_read_b128 columns)
+
+enum : int { F_EXCL_DIAG = 1, F_MASK_K1 = 2, F_MASK_K2 = 4, F_POS = 8 };
+enum : int { RSX_NCE_FP32 = 0, RSX_NCE_BF16X3 = 1, RSX_NCE_F16 = 2 };  // logit/gradient precision of the grouped kernels
+constexpr int kNsplitBwdGrouped = 8;  // split partials the grouped backward's region is sized for (GroupedLayout)
+
+struct FwdArgs {
+  const float* A;     // [N, lda] owner rows (queries)
+  const float* B;     // [M, ldb] streamed rows (columns)
+  const float* bias;  // [M] or nullptr
+  const int* k1a;     // [N] or nullptr
+  const int* k1b;     // [M]
+  const int* k2a;
+  const int* k2b;
+  int64_t N, M, lda, ldb;
+  int64_t diag_off;  // row i's label / diagonal column is i + diag_off (data-parallel shards)
+  float inv_tau;
+  int nsplit;
+  int64_t cols_per_split;
+  float* part;  // [4][nsplit][N] : running max, sum-exp, positive-logit sum, positive count
+};
+
+__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// Block-id remap: all workgroups of one column split share an XCD group (b % 8), so the
+// split's streamed operand is re-read from that XCD's L2. Speed only, never correctness.
+// I: the block index type (int, or int64_t where the caller's row-block arithmetic is 64-bit).
+template <typename I>
+__device__ __forceinline__ void remap_block(I b, int nsplit, int& split, I& rb) {
+  const int xcd = (int)(b & 7);
+  const I q = b >> 3;
+  if (nsplit >= 8) {  // multiple of 8: each split on one XCD group
+    const int nsub = nsplit >> 3;
+    split = xcd + 8 * (int)(q % nsub);
+    rb = q / nsub;
+  } else {  // nsplit in {1, 2, 4}: 8 / nsplit XCD groups per split
+    split = xcd % nsplit;
+    rb = (8 / nsplit) * q + xcd / nsplit;
+  }
+}
+__device__ __forceinline__ void remap_block(int nsplit, int& split, int& rb) {
+  remap_block<int>((int)blockIdx.x, nsplit, split, rb);
+}
+
+// ---------------------------------------------------------------------------------
+// Merge the column splits: LSE, label term, per-row loss/valid/1-over-count.
+struct MergeArgs {
+  const float* A;
+  const float* B;
+  const float* bias;
+  int64_t N, lda, ldb;
+  int64_t diag_off;
+  float inv_tau;
+  int nsplit;
+  const float* part;
+  int pos_mode;      // 0: label = diagonal, 1: label = positive set
+  float* lse;        // [N]
+  float* row_loss;   // [N]
+  float* row_valid;  // [N] 0/1
+  float* inv_cnt;    // [N] (pos mode) or nullptr
+};
+
+// ---------------------------------------------------------------------------------
+// Backward. G_ij = w_i * (P_ij - Y_ij) / tau, P_ij = exp(S_ij - LSE_i) (0 if excluded),
+// Y = diagonal (pos_mode 0) or M_ij / cnt_i (pos_mode 1), w_i = g * valid_i where g is the
+// upstream gradient of the row-loss SUM (device scalar).
+// ROW_OWNED: dA_i = sum_j G_ij B_j ; else dB_j = sum_i G_ij A_i.
+struct BwdArgs {
+  const float* A;
+  const float* B;
+  const float* bias;
+  const int* k1a;
+  const int* k1b;
+  const int* k2a;
+  const int* k2b;
+  int64_t N, M, lda, ldb;
+  int64_t diag_off;
+  float inv_tau;
+  const float* lse;
+  const float* row_valid;
+  const float* inv_cnt;
+  const float* gout;   // upstream gradient of the row-loss sum (device scalar)
+  int nsplit;
+  int64_t span_per_split;  // streamed rows per split
+  float* dout;             // [nsplit][owner_rows][128] (split partials) or final when nsplit==1
+};
+
+inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
+
+inline bool valid_flags(int f) {
+  // supported combinations (see header)
+  return f == 0 || f == F_MASK_K1 || f == (F_MASK_K1 | F_MASK_K2) || f == (F_EXCL_DIAG | F_POS);
+}
+
+// fn(std::integral_constant<int, FL>) for the kernel instantiation FL of a valid flag combination
+template <typename Fn>
+void with_flags(int flags, Fn&& fn) {
+  switch (flags) {
+    case 0: fn(std::integral_constant<int, 0>{}); break;
+    case F_MASK_K1: fn(std::integral_constant<int, F_MASK_K1>{}); break;
+    case F_MASK_K1 | F_MASK_K2: fn(std::integral_constant<int, F_MASK_K1 | F_MASK_K2>{}); break;
+    default: fn(std::integral_constant<int, F_EXCL_DIAG | F_POS>{}); break;
+  }
+}
+
+// =====================================================================================
+// Grouped form of the live LogQ loss (v1_refine_usertower.py:826-861).
+// The logit S_ij depends on column j only through its target t_j, so the N x N problem is
+// evaluated over the D distinct targets of the batch with exact integer multiplicities:
+//   w_{i,d} = 1                         if d == d(i) (the row's own target: only j == i survives
+//                                       the same-item mask)
+//           = c_d - n_{u_i,d}           otherwise (c_d: columns with target d, n_{u,d}: those
+//                                       belonging to row i's user, removed by the same-user mask)
+//   LSE_i = log sum_d w_{i,d} exp(x_{i,d}),  x_{i,d} = <A_i,B_d>/tau - bias_d
+// This is the same sum as the reference's (only the summation order differs); FLOPs drop by
+// N / D (4.7x on Zipf(1.0) H&M-shaped batches). The user's own targets are the sparse
+// exceptions, walked with a monotone pointer per lane.
+struct GArgs {
+  const float* A;        // [N, lda] rows (normalised user steps)
+  const float* B;        // [D, ldb] distinct target rows (normalised item vectors)
+  const float* bias;     // [D] logQ * lambda (nullable)
+  const float* colcnt;   // [D] c_d
+  const int* row_col;    // [N] d(i)
+  const int* row_beg;    // [N] row exception list range [row_beg, row_end) in exc_cols
+  const int* row_end;
+  const int* exc_cols;   // sorted d values of the row's user's targets (with repeats)
+  const int* col_beg;    // [D] column exception list range into exc_s/exc_e/exc_n
+  const int* col_end;
+  const int* exc_s;      // user row range [s, e) and multiplicity n_{u,d}, sorted by s
+  const int* exc_e;
+  const int* exc_n;
+  int64_t N, M, lda, ldb;
+  float inv_tau;
+  int nsplit;
+  int64_t span;          // streamed rows per split
+  float* part;           // fwd: [4][nsplit][N]
+  const float* lse;      // bwd
+  const float* gout;     // bwd: gradient of the row-loss sum
+  float* dout;           // bwd: [nsplit][owner][128]
+  const __bf16* ahi;     // bf16x3: hi/lo images of A [N][128] and B [M][128]
+  const __bf16* alo;
+  const __bf16* bhi;
+  const __bf16* blo;
+  // fused forward, tail-split geometry (fwdg_geometry): row blocks [0, rb1) run nsplit splits of
+  // span columns, the rest nsplit2 splits of span2; partial slots per row: nslots
+  int64_t rb1, span2;
+  int nsplit2, nslots;
+  int split_major;       // grouped backward: split-major block order (nce_grouped_bwd_x3_k)
+};
+
+__device__ __forceinline__ int lower_bound_i(const int* a, int lo, int hi, int64_t key) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)a[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// Block geometry of the fused forward (nce_grouped_fwdg_x3p_k). Row blocks [0, rb1)
+// run a.nsplit column splits, the rest a.nsplit2 (finer: their workgroups are shorter and are
+// dispatched last, so the final round of the grid is filled by short workgroups instead of a
+// third of the chip running long ones). Each region keeps the XCD-aware remap of remap_block.
+__device__ __forceinline__ void fwdg_geometry(const GArgs& a, int& split, int64_t& rb, int64_t& j_begin,
+                                              int64_t& j_end) {
+  const int64_t b = blockIdx.x, n1 = a.rb1 * a.nsplit;
+  int64_t span;
+  if (b < n1) {
+    remap_block<int64_t>(b, a.nsplit, split, rb);
+    span = a.span;
+  } else {  // n1 is a multiple of 8 (host), so b & 7 still names the XCD group
+    const int64_t b2 = b - n1;
+    const int xcd = (int)(b2 & 7);
+    const int64_t q = b2 >> 3;
+    const int nsub = a.nsplit2 >> 3;  // nsplit2 in {8, 16, ...}
+    split = xcd + 8 * (int)(q % nsub);
+    rb = a.rb1 + q / nsub;
+    span = a.span2;
+  }
+  j_begin = (int64_t)split * span;
+  j_end = j_begin + span;
+  if (j_end > a.M) j_end = a.M;
+}
+
+// streamed rows (or columns) per split: whole tiles, at least one
+inline int64_t split_span(int64_t n_str, int nsplit) {
+  const int64_t s = round_up((n_str + nsplit - 1) / nsplit, kTile);
+  return s < kTile ? kTile : s;
+}
+
+// split count of one pass of the plain bf16x3 kernels: the smallest power of two (<= 64) that gives
+// the owner side >= 1024 workgroups while every split keeps >= 2 streamed tiles
+inline int plain_split(int64_t n_own, int64_t n_str) {
+  const int64_t ob = (n_own + kOwnRows - 1) / kOwnRows;
+  // workgroup target: one round of two workgroups per CU (512 on MI355X) measured 8 % faster than
+  // 1024 over the DuoRec + SupCon passes at B = 8192 (tools/nce_plain_micro.py: 0.763 vs 0.830 ms;
+  // 256: 1.05, 2048: 0.93).
+  const int64_t target = 2 * rsx::cu_count();
+  int ps = 1;
+  while (ps < 64 && ob * ps < target && n_str >= (int64_t)ps * 4 * kTile) ps *= 2;
+  return ps;
+}
+
+// ---- workspace layouts: float offsets into ws, and the total *_workspace_floats returns ----
+// Every family starts with part [4][nf][N] | lse [N] | row_loss [N] | row_valid [N] | inv_cnt [N];
+// then come the backward's split partials (dpart, room for dpart_cap floats) and the hi/lo
+// 16-bit images of A and B (img: ahi [N][128] | alo | bhi [M][128] | blo, two per float).
+struct StatsLayout {
+  int nf;  // forward splits
+  int64_t part = 0, lse, row_loss, row_valid, inv_cnt, stats_end;
+  StatsLayout(int64_t N, int nf_)
+      : nf(nf_), lse(4 * (int64_t)nf_ * N), row_loss(lse + N), row_valid(row_loss + N), inv_cnt(row_valid + N),
+        stats_end(inv_cnt + N) {}
+};
+// plain fp32: stats | dpart [nsplit_bwd][max(N, M)][128] | 16
+struct PlainLayout : StatsLayout {
+  int64_t dpart, dpart_cap, total;
+  PlainLayout(int64_t N, int64_t M, int nsplit_fwd, int nsplit_bwd)
+      : StatsLayout(N, nsplit_fwd), dpart(stats_end), dpart_cap((int64_t)nsplit_bwd * std::max(N, M) * kD),
+        total(dpart + dpart_cap + 16) {}
+};
+// plain bf16x3: stats | (64-float aligned) img | dpart [max(pr N, pc M)][128] | 16; the splits of
+// the forward (nf), the row pass (pr) and the column pass (pc) come from plain_split
+struct PlainX3Layout : StatsLayout {
+  int pr, pc;
+  int64_t img, dpart, dpart_cap, total;
+  PlainX3Layout(int64_t N, int64_t M)
+      : StatsLayout(N, plain_split(N, M)), pr(plain_split(N, M)), pc(plain_split(M, N)), img(round_up(stats_end, 64)),
+        dpart(img + (N + M) * kD), dpart_cap(std::max((int64_t)pr * N, (int64_t)pc * M) * kD),
+        total(dpart + dpart_cap + 16) {}
+};
+// grouped: the plain fp32 layout over (N, D), then (bf16x3, f16: 64-float aligned) img | 64. The
+// fused forward's per-slot row gradients (nslots x N x 128) and the column pass's up to 32 splits
+// also live in dpart: both are checked against dpart_cap where they are chosen.
+struct GroupedLayout : PlainLayout {
+  int64_t img, total;
+  GroupedLayout(int64_t N, int64_t D, int nsplit_fwd, int precision, int nsplit_bwd = kNsplitBwdGrouped)
+      : PlainLayout(N, D, nsplit_fwd, nsplit_bwd), img(round_up(PlainLayout::total, 64)),
+        total(img + (precision != RSX_NCE_FP32 ? (N + D) * kD + 64 : 0)) {}
+};
+
+struct Images {
+  __bf16 *ahi, *alo, *bhi, *blo;
+};
+inline Images images_at(float* ws, int64_t img, int64_t N, int64_t M) {
+  __bf16* p = reinterpret_cast<__bf16*>(ws + img);
+  return {p, p + N * kD, p + 2 * N * kD, p + 2 * N * kD + M * kD};
+}
+
+// ---- argument checks shared by the entry points: nullptr, or the message for RSX_ARG ----
+inline const char* operand_error(const float* A, const float* B, int64_t lda, int64_t ldb) {
+  if (!(lda % 4 == 0 && ldb % 4 == 0 && lda >= kD && ldb >= kD)) return "row strides must be >=128 and multiples of 4";
+  if (((uintptr_t)A % 16) != 0 || ((uintptr_t)B % 16) != 0) return "A/B must be 16-byte aligned";
+  return nullptr;
+}
+inline const char* diag_error(int64_t N, int64_t M, int64_t diag_offset) {
+  if (!(diag_offset >= 0 && diag_offset + N <= M)) return "need 0 <= diag_offset and diag_offset + N <= M";
+  return nullptr;
+}
+#define NCE_REQUIRE(err)           \
+  do {                             \
+    const char* m_ = (err);        \
+    RSX_ARG(m_ == nullptr, m_);    \
+  } while (0)
+
+// the forwards' N == 0 case: out2 = {0, 0}
+inline int zero_sums(float* out2, hipStream_t st) {
+  (void)hipMemsetAsync(out2, 0, 2 * sizeof(float), st);
+  RSX_LAUNCHED();
+  return 0;
+}
+
+// ---- host launchers that cross files; the kernels are defined once: in nce_plain.hip ...
+void launch_reduce(const float* row_loss, const float* row_valid, int64_t N, float* out2, hipStream_t st);
+void launch_sum_splits(const float* part, int nsplit, int64_t n_own, float* out, int accumulate, hipStream_t st);
+// rows x 128 fp32 -> hi/lo images: bf16 (half = false) or the fp16 images of RSX_NCE_F16
+void launch_split(const float* src, int64_t ld, int64_t rows, __bf16* hi, __bf16* lo, bool half, hipStream_t st);
+// ... and in nce_grouped_f16.hip
+void launch_grouped_fwdg_h(const GArgs& g, int blocks, hipStream_t st);
+void launch_grouped_bwd_cols_h(const GArgs& g, int blocks, hipStream_t st);
+
+}  // namespace nce
+}  // namespace rsx

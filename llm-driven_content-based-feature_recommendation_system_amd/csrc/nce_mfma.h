@@ -1,0 +1,262 @@
+// Internal header of the contrastive-loss units: the bf16x3 / fp16 tile images and the MFMA
+// helpers that more than one of nce_plain.hip, nce_grouped.hip and nce_grouped_f16.hip use.
+#pragma once
+#include "nce_common.h"
+
+namespace rsx {
+namespace nce {
+
+// =====================================================================================
+// bf16x3 form of the grouped kernels (precision RSX_NCE_BF16X3).
+// Every fp32 operand x is split x = hi + lo, hi = bf16(x), lo = bf16(x - hi) (x - hi is exact
+// in fp32), and a product is hi*hi' + hi*lo' + lo*hi' on v_mfma_f32_32x32x16_bf16 with fp32
+// accumulation (bf16 products are exact; the dropped lo*lo' and the rounding of lo leave
+// ~2^-17 relative error per term: max |dot error| 2.7e-6 on unit vectors against 5e-7 for
+// the fp32 MFMA and 1.2e-3 for plain bf16). Both products of the backward use it:
+//   S tile  : streamed rows (A, ds_read_b128 row reads) x owner rows (B, registers)
+//   gradient: G^T (A, straight from the S accumulator: its rows are the k index) x streamed
+//             rows (B, ds_read_b64_tr_b16 transposed reads of the same LDS image)
+// 3 x 32 cycles per 16 k per 32x32 tile instead of 8 x 64 for the fp32 MFMA (5.3x fewer
+// MFMA cycles). The log-sum-exp runs in base 2 (v_exp_f32 without the log2e multiply).
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+constexpr float kLog2e = 1.4426950408889634f;
+constexpr float kLn2 = 0.6931471805599453f;
+// s_waitcnt vmcnt(0) (expcnt, lgkmcnt left at their maxima): gfx9 encoding
+constexpr int kVmcnt0 = 0x0F70;
+
+// [32][128] bf16 image: 320-B rows plus a 16-B skew per 8-row group, i.e. byte offset
+// 320*row + 16*(row>>3) + 2*col. Conflict-free for the row reads (ds_read_b128, lane (c,h)
+// -> row c, chunk 8h+s), the transposed reads (ds_read_b64_tr_b16) and the staging stores
+// (ds_write_b128), and every read address is a per-lane base + an immediate (no per-step
+// address registers); checked with tools/lds_banks.py.
+constexpr int kImgRow = 160;  // bf16 elements per image row
+constexpr int kImgElems = 5120;
+__device__ __forceinline__ int img_off(int row, int col) { return row * kImgRow + 8 * (row >> 3) + col; }
+
+struct X3Tile {
+  __bf16 hi[kImgElems];
+  __bf16 lo[kImgElems];
+};
+
+__device__ __forceinline__ void split8(const float4& a, const float4& b, bf16x8& h, bf16x8& l) {
+  const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const __bf16 hk = (__bf16)f[k];
+    h[k] = hk;
+    l[k] = (__bf16)(f[k] - (float)hk);
+  }
+}
+
+// owner row (dims 64h .. 64h+63 on lane half h) -> hi/lo fragments of k-steps s = 0..7
+// (fragment s, element j = dim 64h + 8s + j: the chunk 8h + s of the streamed row reads)
+__device__ __forceinline__ void load_owner_x3(bf16x8 (&uh)[8], bf16x8 (&ul)[8], const float* base, int64_t row,
+                                              int64_t ld, bool ok, int h) {
+  // all 16 loads issued back to back from a clamped row, then zeroed past the rows (a branch
+  // around each pair made hipcc wait for every pair before issuing the next)
+  const float4* src = reinterpret_cast<const float4*>(base + (ok ? row : 0) * ld + h * 64);
+  float4 v[16];
+#pragma unroll
+  for (int t = 0; t < 16; ++t) v[t] = src[t];
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) split8(ok ? v[2 * s] : z, ok ? v[2 * s + 1] : z, uh[s], ul[s]);
+}
+
+// Streamed operands are split once per call into global hi/lo bf16 images ([rows][128] each,
+// nce_split_k), so staging a tile is a plain copy: thread tid moves row tid>>3, 16-B chunks
+// tid&7 and 8+(tid&7) of both images (4 x 16-B loads, 4 ds_write_b128).
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+struct X3Stage {
+  u32x4 v[4];  // hi chunk0, hi chunk1, lo chunk0, lo chunk1
+  __device__ __forceinline__ void load(const __bf16* hi, const __bf16* lo, int64_t row, bool ok, int tid) {
+    if (ok) {
+      const int64_t o = row * kD + (tid & 7) * 8;
+      v[0] = *reinterpret_cast<const u32x4*>(hi + o);
+      v[1] = *reinterpret_cast<const u32x4*>(hi + o + 64);
+      v[2] = *reinterpret_cast<const u32x4*>(lo + o);
+      v[3] = *reinterpret_cast<const u32x4*>(lo + o + 64);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t) v[t] = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+  __device__ __forceinline__ void store(X3Tile& t, int tid) const {
+    const int row = tid >> 3, ch = tid & 7;
+    const int o0 = img_off(row, 8 * ch), o1 = img_off(row, 64 + 8 * ch);
+    *reinterpret_cast<u32x4*>(&t.hi[o0]) = v[0];
+    *reinterpret_cast<u32x4*>(&t.hi[o1]) = v[1];
+    *reinterpret_cast<u32x4*>(&t.lo[o0]) = v[2];
+    *reinterpret_cast<u32x4*>(&t.lo[o1]) = v[3];
+  }
+  // the hi image alone (a pass whose products never read the streamed rows' lo image)
+  __device__ __forceinline__ void load_hi(const __bf16* hi, int64_t row, bool ok, int tid) {
+    if (ok) {
+      const int64_t o = row * kD + (tid & 7) * 8;
+      v[0] = *reinterpret_cast<const u32x4*>(hi + o);
+      v[1] = *reinterpret_cast<const u32x4*>(hi + o + 64);
+    } else {
+      v[0] = v[1] = u32x4{0u, 0u, 0u, 0u};
+    }
+  }
+  __device__ __forceinline__ void store_hi(X3Tile& t, int tid) const {
+    const int row = tid >> 3, ch = tid & 7;
+    *reinterpret_cast<u32x4*>(&t.hi[img_off(row, 8 * ch)]) = v[0];
+    *reinterpret_cast<u32x4*>(&t.hi[img_off(row, 64 + 8 * ch)]) = v[1];
+  }
+};
+
+
+// S tile: acc[r] = <streamed row tile_row(r,h), owner row c> (owner on the lane).
+// The next k-step's fragments are read before this step's MFMAs (LDS latency under MFMA);
+// the scheduling barrier keeps the compiler from hoisting more reads (VGPR budget).
+__device__ __forceinline__ f32x16 dots_x3(const X3Tile& t, int c, int h, const bf16x8 (&uh)[8],
+                                          const bf16x8 (&ul)[8]) {
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+  const int base = img_off(c, 64 * h);
+  bf16x8 ah = *reinterpret_cast<const bf16x8*>(&t.hi[base]);
+  bf16x8 al = *reinterpret_cast<const bf16x8*>(&t.lo[base]);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    bf16x8 nh = ah, nl = al;
+    if (s < 7) {
+      nh = *reinterpret_cast<const bf16x8*>(&t.hi[base + 8 * (s + 1)]);
+      nl = *reinterpret_cast<const bf16x8*>(&t.lo[base + 8 * (s + 1)]);
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, uh[s], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, ul[s], acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, uh[s], acc, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    ah = nh;
+    al = nl;
+  }
+  return acc;
+}
+
+// gacc[nb] += G^T X over the tile, G given as its hi/lo bf16 fragments (acc layout: streamed
+// row tile_row(r,h) in register r, owner on the lane; k-step ks takes registers 8ks..8ks+7,
+// i.e. streamed rows 16ks + 8(j>>2) + 4h + (j&3)). The B fragment is those rows of dims
+// 32nb + c, two transposed 4-row reads per image. Steps (ks, nb) are software-pipelined by one.
+__device__ __forceinline__ void grad_x3s(f32x16 (&gacc)[4], const bf16x8 (&gh)[2], const bf16x8 (&gl)[2],
+                                         const X3Tile& t, int lane) {
+  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
+  const int base = img_off(4 * h + q, 16 * cb + 4 * p);  // + img_off(16ks + 8half, 32nb) - img_off(0,0)
+  auto rd = [&](const __bf16* img, int step, bf16x8& out) {
+    const int ks = step >> 2, nb = step & 3;
+    const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
+    const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
+    const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
+    out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+  bf16x8 bh, bl;
+  rd(t.hi, 0, bh);
+  rd(t.lo, 0, bl);
+#pragma unroll
+  for (int step = 0; step < 8; ++step) {
+    bf16x8 nh = bh, nl = bl;
+    if (step < 7) {
+      rd(t.hi, step + 1, nh);
+      rd(t.lo, step + 1, nl);
+    }
+    const int ks = step >> 2, nb = step & 3;
+    gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl[ks], bh, gacc[nb], 0, 0, 0);
+    gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh[ks], bl, gacc[nb], 0, 0, 0);
+    gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh[ks], bh, gacc[nb], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    bh = nh;
+    bl = nl;
+  }
+}
+
+// (a, b) -> packed bf16 hi pair and lo pair (x = hi + lo, hi = RNE bf16(x), lo = bf16(x - hi)):
+// one pair conversion for hi, its two halves unpacked as fp32 by a shift and a mask, two
+// subtractions and one pair conversion for lo (the per-element form converted every element
+// twice and re-packed).
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
+  const bf16x2 h = {(__bf16)a, (__bf16)b};
+  hi = __builtin_bit_cast(uint32_t, h);
+  const float ha = __uint_as_float(hi << 16), hb = __uint_as_float(hi & 0xffff0000u);
+  const bf16x2 l = {(__bf16)(a - ha), (__bf16)(b - hb)};
+  lo = __builtin_bit_cast(uint32_t, l);
+}
+
+__device__ __forceinline__ void split_tile(const f32x16& g, bf16x8 (&gh)[2], bf16x8 (&gl)[2]) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    u32x4 h, l;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t hq, lq;
+      split_pair(g[8 * ks + 2 * q], g[8 * ks + 2 * q + 1], hq, lq);
+      h[q] = hq;
+      l[q] = lq;
+    }
+    gh[ks] = __builtin_bit_cast(bf16x8, h);
+    gl[ks] = __builtin_bit_cast(bf16x8, l);
+  }
+}
+
+__device__ __forceinline__ int grad_lane_base(int lane) {
+  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
+  return img_off(4 * h + q, 16 * cb + 4 * p);
+}
+
+__device__ __forceinline__ void grad_rd(const __bf16* img, int base, int ks, int nb, bf16x8& out) {
+  const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
+  const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
+  const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
+  out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// fused forwards: the running max is raised only when a tile max exceeds it by more than 2^8
+constexpr float kLazyLog2 = 8.0f;
+
+// Bias / column-count staging of the fused forwards (nce_grouped_fwdg_x3p_k, nce_grouped_fwdg_h_k):
+// thread tid < kTile carries column j0 + tid. Raw loads only (math on a load in flight would wait
+// for it); columns past the split get bias +inf and count 0.
+__device__ __forceinline__ void stage_bias_count_load(const GArgs& a, int64_t j0, int64_t j_end, int tid, float& stg_b,
+                                                      float& stg_c) {
+  if (tid < kTile) {
+    const int64_t jj = j0 + tid;
+    const bool ok = jj < j_end;
+    stg_b = ok ? (a.bias ? a.bias[jj] : 0.0f) : INFINITY;
+    stg_c = ok ? a.colcnt[jj] : 0.0f;
+  }
+}
+// -bias log2e + log2 c_d: the multiplicity rides in the exponent (one fma per logit, no
+// multiply); -inf past the split (c = 0, bias = inf)
+__device__ __forceinline__ void stage_bias_count_store(float* sB2, float* sCnt, int tid, float stg_b, float stg_c) {
+  if (tid < kTile) {
+    sB2[tid] = -(stg_b * kLog2e) + __log2f(stg_c);
+    sCnt[tid] = stg_c;
+  }
+}
+
+// fp16 images of RSX_NCE_F16 (nce_grouped_f16.hip): hi + lo of x * 2^8 in the bf16 containers
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+constexpr float kHScale = 256.0f;         // operand scale 2^8
+
+__device__ __forceinline__ void split8_h(const float4& a, const float4& b, bf16x8& h, bf16x8& l) {
+  const float f[8] = {a.x * kHScale, a.y * kHScale, a.z * kHScale, a.w * kHScale,
+                      b.x * kHScale, b.y * kHScale, b.z * kHScale, b.w * kHScale};
+  f16x8 hv, lv;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const _Float16 hk = (_Float16)f[k];
+    hv[k] = hk;
+    lv[k] = (_Float16)(f[k] - (float)hk);
+  }
+  h = __builtin_bit_cast(bf16x8, hv);
+  l = __builtin_bit_cast(bf16x8, lv);
+}
+
+}  // namespace nce
+}  // namespace rsx

@@ -4,7 +4,7 @@
 // unique_consecutive / repeat_interleave / the count all-gather).
 // Reference: the per-batch host work of train_user_tower_all_time (tower_code/
 // v1_usertower_train.py:794-835: valid-step flattening, target / user ids, the DuoRec "last"
-// index count-1) and the structures the grouped loss kernels read (csrc/infonce.hip GArgs).
+// index count-1) and the structures the grouped loss kernels read (csrc/nce_common.h GArgs).
 // Same arrays, same orders, as the torch builders it replaces (PackedTokens, pack_inputs,
 // ops.sort_segments, ops.TargetGroups): tests/test_gpu_step_index.py compares them element
 // for element.

@@ -138,11 +138,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_k(WArgs a) {
 
 // bf16x3 form (rsx_linear_wgrad_x3): the staged dY / X stages are split into hi/lo bf16
 // images (x = hi + lo) as they are written to LDS, and every product is hi*hi' + hi*lo' +
-// lo*hi' on v_mfma_f32_32x32x16_bf16 (fp32 accumulate; the arithmetic of infonce.hip's
+// lo*hi' on v_mfma_f32_32x32x16_bf16 (fp32 accumulate; the arithmetic of nce_mfma.h's
 // bf16x3 loss). Both MFMA operands have the token axis as their k index, so both come from
 // ds_read_b64_tr_b16 transposed reads of the token-major images: lane (c, h) element j of
 // k-step ks is token 16ks + 8(j>>2) + 4h + (j&3), column c of the 32-wide block. Image
-// layout (as infonce.hip): 320-B rows + a 16-B skew per 8 rows, conflict-free for the
+// layout (as nce_mfma.h): 320-B rows + a 16-B skew per 8 rows, conflict-free for the
 // transposed reads. db is summed in fp32 from the staged registers.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));

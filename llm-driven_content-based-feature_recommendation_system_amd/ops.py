@@ -701,7 +701,8 @@ def nce_emphasis_loss(A, B, keys, top, margin, bias=None, tau=0.1, tag="hard_emp
     """Mean over the N rows of CE(A B^T / tau - bias + margin on each row's mined columns top [N, K],
     same-key columns off the diagonal at -inf; label = diagonal) -- full_batch_hard_emphasis_loss's
     objective (v1_refine_usertower.py:546-554) without its N x N tensors. margin is in logit units
-    (the reference's hard_margin / temperature). A [N, 128], B [N, 128], keys [N] int."""
+    (the reference's hard_margin / temperature). A [N, 128], B [N, 128], keys [N] int. The mined ids of
+    one row must be distinct (a repeated id is counted twice where the reference's scatter_ sets it once)."""
     if A.shape[0] != B.shape[0]:
         raise ValueError("nce_emphasis_loss: A and B must have the same number of rows (label = diagonal)")
     if bias is not None:
@@ -832,7 +833,9 @@ class _NCEGrouped(torch.autograd.Function):
 def nce_grouped_sum(A, B_distinct, bias, groups: TargetGroups, tau=0.1, tag="nce", precision=None):
     """(sum of row losses, N) of the live LogQ loss with same-item / same-user masking, with
     the columns given as the distinct targets (B_distinct[d] = normalised item groups.uniq[d]).
-    precision: "fp32" | "bf16x3" | "f16" | None (= set_nce_precision / RSX_NCE_PRECISION)."""
+    precision: "fp32" | "bf16x3" | "f16" | None (= set_nce_precision / RSX_NCE_PRECISION).
+    "f16" scales the operands by 2^8 into fp16: every component of A and B_distinct must have
+    |x| < 256 (the callers pass unit-norm rows)."""
     if bias is not None:
         bias = _c(bias.to(torch.float32))
     prec = NCE_PRECISIONS[precision or _nce_precision]

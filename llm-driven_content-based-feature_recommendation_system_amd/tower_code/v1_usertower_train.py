@@ -166,7 +166,7 @@ def contrastive_losses(model, item_tower, log_q_tensor, batch, cfg, pretrained_v
         flat_user_ids = pk.tok_user[pk.valid_tok]
         # Grouped evaluation of inbatch_corrected_logq_loss (v1_refine_usertower.py:826-861):
         # the columns normalize(item_matrix)[flat_targets] collapse onto the distinct targets
-        # with exact multiplicities (see csrc/infonce.hip); same result, N/D fewer FLOPs.
+        # with exact multiplicities (see csrc/nce_grouped.hip); same result, N/D fewer FLOPs.
         groups = ops.TargetGroups(flat_targets, flat_user_ids)
         items_d = ops.gather_rows(item_tower.get_all_embeddings(), groups.uniq, normalize=True, unique=True)
         bias = log_q_tensor[groups.uniq] * cfg.lambda_logq if cfg.lambda_logq > 0.0 else None

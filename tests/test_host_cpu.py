@@ -74,7 +74,7 @@ def test_module_params_same_set_as_parameters():
 
 
 def test_emphasis_correction_identity_matches_dense_form():
-    """The arithmetic rsx_nce_emphasis_fwd / _bwd implement (csrc/infonce.hip, nce_emph_*_k), checked in
+    """The arithmetic rsx_nce_emphasis_fwd / _bwd implement (csrc/nce_emphasis.hip, nce_emph_*_k), checked in
     float64 against full_batch_hard_emphasis_loss's dense form (v1_refine_usertower.py:546-554): with lse
     the masked row log-sum-exp and E_i = sum over allowed mined j of exp(S_ij - lse_i),
       lse'_i = lse_i + log1p((e^m - 1) E_i),  loss'_i = lse'_i - S_ii - m [i mined],

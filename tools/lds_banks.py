@@ -1,5 +1,5 @@
 """LDS bank-conflict model (MI355X_MICROARCH.md §LDS lane groups / bank rules) for the bf16
-tile images of csrc/infonce.hip: ds_read_b128 row reads of the S-tile operand, ds_read_b64_tr_b16
+tile images of csrc/nce_mfma.h: ds_read_b128 row reads of the S-tile operand, ds_read_b64_tr_b16
 transposed reads of the gradient operand, ds_write_b128 staging stores. Prints the cycles per
 wave-instruction of candidate layouts (ideal: b128 4, tr 2, write 8); the layout in use is
 row*320 + 16*(row>>3) + 2*col bytes (S=320, a=1 below)."""
