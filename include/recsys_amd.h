@@ -513,6 +513,41 @@ int64_t rsx_binary_eval_workspace_bytes(int64_t R);
 int rsx_binary_eval(const float* logit, const float* y, int64_t R, void* ws, int64_t ws_bytes, int64_t* counts,
                     double* loss_sum, int* flag, void* stream);
 
+/* ---- A16 grouped validation: per-query NDCG@top and QueryAUC, csrc/group_eval.hip ------------------
+ * The reference's ranker rows come in per-customer groups (utils/monitor/log_importer.py,
+ * HMLogImporter.load_and_preprocess -> X_user, X_item, y, groups: the "CatBoost Group ID"); a reranker
+ * is judged on the order inside each group. logit [R], y [R] fp32 in {0, 1}, group_id [R] int32 in
+ * [0, 2^31), rows of a group anywhere in the input. For each distinct group g with rows I_g:
+ *   P_g = #{y == 1}, N_g = |I_g| - P_g;
+ *   U2_g = sum over the positives i of I_g of #{negative j in I_g : z_j < z_i} + #{... : z_j <= z_i}
+ *     (twice the tie-aware Mann-Whitney U within the group, an exact integer); AUC_g = U2_g / (2 P_g N_g);
+ *   DCG_g = the tie-averaged DCG@top (McSherry & Najork; sklearn's ndcg_score(ignore_ties=False)): with
+ *     disc[p] = 1 / log2(p + 2) for the 0-based position p < top, else 0, and D[i] = sum_{p<i} disc[p],
+ *     a tie group at the positions [s, e] of the group sorted by descending score with pos positives
+ *     adds pos (D[min(e + 1, top)] - D[min(s, top)]) / (e - s + 1); IDCG_g = D[min(P_g, top)],
+ *     NDCG_g = DCG_g / IDCG_g. Scores compare as reals: -0.0 and +0.0 tie.
+ * D [top + 1] (double, device) is the caller's table D[0..top], 1 <= top <= 65536: the device takes no
+ * logarithm. max_group_id: an upper bound of the ids known on the host (the sort then skips the bits
+ * above it), -1 = unknown.
+ * Per-group outputs, each sized R by the caller, their first G entries written, groups ascending:
+ *   gid (int32), P, N, U2 (int64), dcg (double).
+ * summary (int64 [5], 8-byte aligned): [0] = G, [1] = ndcg_groups = #{g : P_g > 0}, [2] = auc_groups =
+ *   #{g : P_g > 0 and N_g > 0}, [3] = (double) ndcg_sum = sum of NDCG_g over the former, [4] = (double)
+ *   auc_sum = sum of AUC_g over the latter; NDCG = ndcg_sum / ndcg_groups, QueryAUC = auc_sum / auc_groups.
+ * flag [1] (int32): bit 0 = a logit is NaN or +-inf, bit 1 = a label is neither 0 nor 1, bit 2 = a
+ *   group id is negative or above max_group_id; with a flag set the other outputs are unspecified
+ *   (every access stays in bounds).
+ * Key pass, radix sort of (group << 32 | ~score key, label), two passes over 2048-row tiles with a
+ * one-workgroup carry pass after each, the per-group quotients; no step walks a group or a tie group,
+ * so the cost does not depend on the groups' sizes. Integer sums and fixed-order double sums:
+ * deterministic, no float atomics. 1 <= R < 2^31 (rsx_group_eval_workspace_bytes returns -1 outside
+ * it, and is non-decreasing in R); ws 16-byte aligned, D / summary / P / N / U2 / dcg 8-byte aligned;
+ * the outputs need no zeroing by the caller; everything is enqueued on stream. */
+int64_t rsx_group_eval_workspace_bytes(int64_t R);
+int rsx_group_eval(const float* logit, const float* y, const int32_t* group_id, int64_t R, int top, const double* D,
+                   int64_t max_group_id, void* ws, int64_t ws_bytes, int64_t* summary, int32_t* gid, int64_t* P,
+                   int64_t* N, int64_t* U2, double* dcg, int* flag, void* stream);
+
 /* ---- §8f #3: GDCN reranker batch (utils/data_preprocessing/feature_processor.py:144-195) ----
  * rsx_reranker_batch replaces RerankerDataset.__getitem__ (:156-181) + reranker_collate_fn
  * (:184-191) for a batch of (user row uidx[b], item row iidx[b]) on device tables:

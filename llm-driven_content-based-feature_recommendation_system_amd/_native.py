@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 8  # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 9  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -156,6 +156,8 @@ _SIGS = {
                                            c_p, c_p, c_d, c_d, c_d, c_d, c_i64, c_p, c_i64, c_p, c_p, c_p]),
     "rsx_binary_eval_workspace_bytes": (c_i64, [c_i64]),
     "rsx_binary_eval": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "rsx_group_eval_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_group_eval": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -6,6 +6,7 @@ There is no CPU path: a non-ROCm tensor raises.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import weakref
 
@@ -2458,6 +2459,150 @@ def binary_eval(logit, y):
     with timed("binary_eval"):
         N.check(lib.rsx_binary_eval(N.ptr(z), N.ptr(y), R, N.ptr(ws), nws, N.ptr(out.counts), N.ptr(out.loss_sum),
                                     N.ptr(out.flag), N.stream()), "binary_eval")
+    return out
+
+
+# ----------------------------------------------------------------------------------------
+# A16 grouped validation: per-query NDCG@top and QueryAUC (csrc/group_eval.hip)
+NDCG_MAX_TOP = 65536
+_GROUP_EVAL_WS = {}     # R -> workspace bytes
+_NDCG_DISCOUNTS = {}    # (top, device) -> the table D[0..top]; device None = the host tensor
+
+
+def _check_top(top, what):
+    if isinstance(top, bool) or not isinstance(top, int) or not 1 <= top <= NDCG_MAX_TOP:
+        raise ValueError(f"{what}: top must be an integer in [1, {NDCG_MAX_TOP}] (got {top!r})")
+
+
+def ndcg_discounts(top, device=None):
+    """D [top + 1] float64 with D[i] = sum_{p<i} 1 / log2(p + 2): the cumulated DCG discounts of the
+    0-based positions below i, a sequential float64 sum on the host (D[0] = 0, D[1] = 1). Cached per
+    (top, device); device None -> the CPU tensor. The device never takes a logarithm: rsx_group_eval
+    and the tests' reference index the same table."""
+    _check_top(top, "ndcg_discounts")
+    host = _NDCG_DISCOUNTS.get((top, None))
+    if host is None:
+        acc, vals = 0.0, [0.0]
+        for p in range(top):
+            acc += 1.0 / math.log2(p + 2)
+            vals.append(acc)
+        host = _NDCG_DISCOUNTS[(top, None)] = torch.tensor(vals, dtype=torch.float64)
+    if device is None:
+        return host
+    device = torch.device(device)
+    dev = _NDCG_DISCOUNTS.get((top, device))
+    if dev is None:
+        dev = _NDCG_DISCOUNTS[(top, device)] = host.to(device)
+    return dev
+
+
+class GroupEval:
+    """What group_eval returns. The outputs stay on the device until result(): the summary (int64
+    [3]: groups G, ndcg_groups, auc_groups; float64 [2]: ndcg_sum, auc_sum) and the flag (int32) are
+    views of one 48-byte allocation, fetched by one copy; the per-group arrays (sized R, their first
+    G entries written) are sliced by per_group() once result() has made G known."""
+
+    def __init__(self, buf, rows, top, per_group):
+        self._buf, self.rows, self.top, self._per_group = buf, rows, top, per_group
+        self.summary, self.flag = buf[:5], buf[5:6].view(torch.int32)[:1]
+        self.groups = None
+
+    def result(self, also=None):
+        """The one host read: {"ndcg", "query_auc", "groups", "ndcg_groups", "auc_groups"}. ndcg =
+        the mean of NDCG_g over the ndcg_groups groups with a positive, query_auc = the mean of
+        AUC_g over the auc_groups groups with both classes (NaN when there is none), formed in
+        double. ValueError for a non-finite logit, a label that is neither 0 nor 1 or a group id
+        out of range. also: as BinaryEval.result."""
+        if also is None:
+            host = self._buf.cpu()
+        else:
+            host = torch.cat([self._buf, also.detach().reshape(-1).view(torch.int64)]).cpu()
+        out = self._result(host)
+        return out if also is None else (out, host[6:].view(torch.float64).tolist())
+
+    def _result(self, host):
+        flag = int(host[5:6].view(torch.int32)[0])
+        if flag:
+            why = [w for b, w in ((1, "a logit is NaN or infinite"), (2, "a label is neither 0 nor 1"),
+                                  (4, "a group id is outside [0, 2^31) or above max_group_id")) if flag & b]
+            raise ValueError("group_eval: " + " and ".join(why))
+        g, ng, na = (int(v) for v in host[:3])
+        s_ndcg, s_auc = host[3:5].view(torch.float64).tolist()
+        self.groups = g
+        return {"ndcg": s_ndcg / ng if ng else float("nan"), "query_auc": s_auc / na if na else float("nan"),
+                "groups": g, "ndcg_groups": ng, "auc_groups": na}
+
+    def per_group(self):
+        """(gid int32, P, N, U2 int64, dcg float64), device tensors [G], the groups ascending by id."""
+        if self.groups is None:
+            raise RuntimeError("GroupEval.per_group: call result() first (it reads the number of groups)")
+        return tuple(t[:self.groups] for t in self._per_group)
+
+
+def _fetch_evals(binary, group, also=None):
+    """A BinaryEval's and a GroupEval's result() by one copy: (binary dict, group dict[, the values of
+    the float64 device tensor `also` as a list])."""
+    parts = [binary._buf, group._buf]
+    if also is not None:
+        parts.append(also.detach().reshape(-1).view(torch.int64))
+    host = torch.cat(parts).cpu()
+    out = (binary._result(host[:5]), group._result(host[5:11]))
+    return out if also is None else out + (host[11:].view(torch.float64).tolist(),)
+
+
+def group_ids_int32(group_id, device):
+    """group_id (an integer tensor or array-like) as the contiguous int32 device tensor rsx_group_eval
+    reads, without a host read: an id outside [0, 2^31) becomes -1, which the kernel flags."""
+    g = torch.as_tensor(group_id)
+    if g.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64):
+        raise ValueError(f"group_eval: group_id must have an integer dtype (got {g.dtype})")
+    g = g.detach().to(device).reshape(-1)
+    if g.dtype == torch.int64:
+        g = torch.where((g >= 0) & (g < 2 ** 31), g, torch.full_like(g, -1))
+    return _c(g.to(torch.int32))
+
+
+def group_eval(logit, y, group_id, top=10, max_group_id=None):
+    """Per-query evaluation of the scores logit [R] (fp32, device) against the labels y [R] (any
+    dtype, values 0 / 1) within the groups group_id [R] (integer dtype, ids in [0, 2^31), the rows of
+    a group anywhere): every group's P, N, U2 and tie-averaged DCG@top, and the sums behind NDCG and
+    QueryAUC (definitions: include/recsys_amd.h), without a host synchronisation: rsx_group_eval on
+    the current stream. max_group_id: an upper bound of the ids, if the host knows one (fewer sort
+    passes). Returns a GroupEval; its result() does the one host read."""
+    N.ensure_device(logit)
+    if logit.dtype != torch.float32:
+        raise ValueError(f"group_eval: logits must be float32 (got {logit.dtype})")
+    z = _c(logit.detach().reshape(-1))
+    R = z.numel()
+    if R < 1:
+        raise ValueError("group_eval needs at least one row")
+    y = _c(torch.as_tensor(y).detach().to(device=z.device, dtype=torch.float32).reshape(-1))
+    if y.numel() != R:
+        raise ValueError(f"group_eval: {y.numel()} labels for {R} scores")
+    g = group_ids_int32(group_id, z.device)
+    if g.numel() != R:
+        raise ValueError(f"group_eval: {g.numel()} group ids for {R} scores")
+    _check_top(top, "group_eval")
+    if max_group_id is None:
+        max_group_id = -1
+    elif not 0 <= int(max_group_id) < 2 ** 31:
+        raise ValueError(f"group_eval: max_group_id must be in [0, 2^31) (got {max_group_id!r})")
+    lib = N.lib()
+    nws = _GROUP_EVAL_WS.get(R)
+    if nws is None:
+        nws = _GROUP_EVAL_WS[R] = int(lib.rsx_group_eval_workspace_bytes(R))
+        if nws < 0:
+            N.check(1, "group_eval_workspace_bytes")
+    D = ndcg_discounts(top, z.device)
+    ws = torch.empty(nws, device=z.device, dtype=torch.uint8)
+    gid = torch.empty(R, device=z.device, dtype=torch.int32)
+    cnt = torch.empty(3, R, device=z.device, dtype=torch.int64)
+    dcg = torch.empty(R, device=z.device, dtype=torch.float64)
+    out = GroupEval(torch.empty(6, device=z.device, dtype=torch.int64), R, top, (gid, cnt[0], cnt[1], cnt[2], dcg))
+    with timed("group_eval"):
+        N.check(lib.rsx_group_eval(N.ptr(z), N.ptr(y), N.ptr(g), R, top, N.ptr(D), int(max_group_id), N.ptr(ws), nws,
+                                   N.ptr(out.summary), N.ptr(gid), N.ptr(cnt[0]), N.ptr(cnt[1]), N.ptr(cnt[2]),
+                                   N.ptr(dcg), N.ptr(out.flag), N.stream()), "group_eval")
     return out
 
 

@@ -11,7 +11,10 @@ Compute: DeepFM forward = rsx_deepfm_embed + rsx_linear_fwd + rsx_linear_dot_fwd
 (the reference trains its ranker before use, RecommendationRanker.train :114-137, Logloss) =
 ops.deepfm_train_step (DeepFM.make_trainer / DeepFM.fit); its validation (eval_set, eval_metric='AUC',
 early_stopping_rounds, use_best_model, :98-108 and :123-135) = DeepFM.evaluate / DeepFM.fit(eval_set=...)
-over ops.binary_eval (rsx_binary_eval: exact tie-aware AUC and Logloss on the device); retrieval
+over ops.binary_eval (rsx_binary_eval: exact tie-aware AUC and Logloss on the device) and, for rows
+that carry the per-customer group id of the reference's ranker data (utils/monitor/log_importer.py),
+ops.group_eval (rsx_group_eval: per-query NDCG@top and QueryAUC; evaluate(group_id=...),
+fit(eval_group_id=..., eval_metric="NDCG" | "NDCG:top=K" | "QueryAUC")); retrieval
 (user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk).
 """
 from __future__ import annotations
@@ -25,12 +28,33 @@ import torch.nn as nn
 from .. import ops
 
 
-def _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every):
+def _parse_eval_metric(eval_metric):
+    """eval_metric -> (the key of evals_result_["validation"] it selects, the NDCG cut-off): "AUC",
+    "Logloss", "QueryAUC", "NDCG" (top 10) or "NDCG:top=K"."""
+    if eval_metric in ("AUC", "Logloss", "QueryAUC", "NDCG"):
+        return eval_metric, 10
+    if isinstance(eval_metric, str) and eval_metric.startswith("NDCG:"):
+        suffix = eval_metric[len("NDCG:"):]
+        digits = suffix[len("top="):]
+        if not suffix.startswith("top=") or not (digits.isascii() and digits.isdigit()):
+            raise ValueError(f'eval_metric "NDCG" takes the suffix ":top=K" with an integer K (got {eval_metric!r})')
+        top = int(digits)
+        if not 1 <= top <= ops.NDCG_MAX_TOP:
+            raise ValueError(f"eval_metric {eval_metric!r}: top must be in [1, {ops.NDCG_MAX_TOP}]")
+        return "NDCG", top
+    raise ValueError('eval_metric must be "AUC", "Logloss", "NDCG", "NDCG:top=K" or "QueryAUC" '
+                     f"(got {eval_metric!r})")
+
+
+def _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every, eval_group_id=None):
     """The argument checks of fit (DeepFM.fit documents them) that need no data; returns the
     effective use_best_model (default True with an eval_set)."""
-    if eval_metric not in ("AUC", "Logloss"):
-        raise ValueError(f'eval_metric must be "AUC" or "Logloss" (got {eval_metric!r})')
+    metric, _ = _parse_eval_metric(eval_metric)
+    if metric in ("NDCG", "QueryAUC") and eval_group_id is None:
+        raise ValueError(f"eval_metric {eval_metric!r} is a per-group metric: it needs eval_group_id")
     if eval_set is None:
+        if eval_group_id is not None:
+            raise ValueError("eval_group_id needs an eval_set")
         if early_stopping_rounds is not None or eval_every is not None or use_best_model:
             raise ValueError("early_stopping_rounds, eval_every and use_best_model need an eval_set")
         return False
@@ -50,13 +74,47 @@ def _fit_eval_labels(yv, eval_metric):
         raise ValueError('eval_set holds a single class: eval_metric="AUC" is undefined')
 
 
+def _fit_eval_groups(yv, eval_group_id, eval_metric):
+    """eval_group_id as the int32 device tensor of the validation rows yv. ValueError for a wrong
+    length, an id outside [0, 2^31), eval_metric "NDCG" with no group that holds a positive or
+    "QueryAUC" with no group that holds both classes (one host read: ops.group_eval on zero logits)."""
+    n = len(eval_group_id)
+    if n != yv.numel():
+        raise ValueError(f"eval_group_id has {n} ids for {yv.numel()} validation rows")
+    gv = ops.group_ids_int32(eval_group_id, yv.device)
+    metric, top = _parse_eval_metric(eval_metric)
+    try:
+        res = ops.group_eval(torch.zeros_like(yv), yv, gv, top=top).result()
+    except ValueError as e:
+        raise ValueError(f"eval_group_id: {e}") from None
+    if metric == "NDCG" and res["ndcg_groups"] == 0:
+        raise ValueError(f"no group of the eval_set holds a positive: eval_metric={eval_metric!r} is undefined")
+    if metric == "QueryAUC" and res["auc_groups"] == 0:
+        raise ValueError('no group of the eval_set holds both classes: eval_metric="QueryAUC" is undefined')
+    return gv
+
+
+def _evaluate_result(run, rows, y, batch_size, group_id, top):
+    """The dict of evaluate: run = the model's _evaluate_on_device, rows = its row arguments. One host
+    read with or without group_id."""
+    if group_id is None:
+        res = run(*rows, batch_size).result()
+        return {"Logloss": res["logloss"], "AUC": res["auc"]}
+    g = ops.group_ids_int32(group_id, y.device)
+    if g.numel() != y.numel():
+        raise ValueError(f"group_id has {g.numel()} ids for {y.numel()} rows")
+    res, grp = ops._fetch_evals(*run(*rows, batch_size, g, top))
+    return {"Logloss": res["logloss"], "AUC": res["auc"], "NDCG": grp["ndcg"], "QueryAUC": grp["query_auc"]}
+
+
 def _fit_loop(model, tr, step, R, dev, batch_size, epochs, shuffle, seed, validate, eval_metric,
               early_stopping_rounds, use_best_model, eval_every, after_steps=None):
     """The training loop of DeepFM.fit and RankingModel.fit (semantics: DeepFM.fit's docstring).
     step(sel) -> the loss of the batch of rows sel (a slice, or an index tensor when shuffled);
     tr.reduction says how it was reduced. validate: None, or a callable returning the validation
-    rows' ops.BinaryEval. after_steps: called once the last step was taken, before the best
-    parameters are restored. Returns the completed epochs' mean row losses."""
+    rows' ops.BinaryEval, or (with eval_group_id) their (ops.BinaryEval, ops.GroupEval). after_steps:
+    called once the last step was taken, before the best parameters are restored. Returns the
+    completed epochs' mean row losses."""
     gen = torch.Generator().manual_seed(seed)
     means = []
     if validate is None:
@@ -74,6 +132,7 @@ def _fit_loop(model, tr, step, R, dev, batch_size, epochs, shuffle, seed, valida
 
     model.evals_result_ = {"learn": {"Logloss": []}, "validation": {"Logloss": [], "AUC": []}}
     model.best_iteration_, model.best_score_ = None, None
+    metric, _ = _parse_eval_metric(eval_metric)
     params = list(model.parameters())
     snapshot, stale = None, False      # stale: steps were taken since the snapshot was written
     state = {"best": None, "since": 0}
@@ -81,16 +140,22 @@ def _fit_loop(model, tr, step, R, dev, batch_size, epochs, shuffle, seed, valida
     def evaluate_now(learn_mean):
         """One evaluation; learn_mean: 0-d float64 device tensor. True when training should stop."""
         nonlocal snapshot, stale
-        res, (learn,) = validate().result(also=learn_mean)
+        evs = validate()
+        if isinstance(evs, tuple):      # with eval_group_id: both blocks and the learn mean in one copy
+            res, grp, (learn,) = ops._fetch_evals(*evs, also=learn_mean)
+            now = {"Logloss": res["logloss"], "AUC": res["auc"], "NDCG": grp["ndcg"], "QueryAUC": grp["query_auc"]}
+        else:
+            res, (learn,) = evs.result(also=learn_mean)
+            now = {"Logloss": res["logloss"], "AUC": res["auc"]}
         ev = model.evals_result_
         ev["learn"]["Logloss"].append(learn)
-        ev["validation"]["Logloss"].append(res["logloss"])
-        ev["validation"]["AUC"].append(res["auc"])
-        score = res["auc"] if eval_metric == "AUC" else -res["logloss"]
+        for name, value in now.items():
+            ev["validation"].setdefault(name, []).append(value)
+        score = -now["Logloss"] if metric == "Logloss" else now[metric]
         if state["best"] is None or score > state["best"]:
             state["best"], state["since"] = score, 0
             model.best_iteration_ = len(ev["validation"]["AUC"]) - 1
-            model.best_score_ = {"validation": {"Logloss": res["logloss"], "AUC": res["auc"]}}
+            model.best_score_ = {"validation": now}
             if use_best_model:
                 with torch.no_grad():
                     if snapshot is None:
@@ -236,26 +301,31 @@ class DeepFM(nn.Module):
         return X, y
 
     @torch.no_grad()
-    def _evaluate_on_device(self, X, y, batch_size):
-        """forward_logits over X in batches into one [R] buffer, then one ops.binary_eval: nothing is
-        read back here (forward_logits itself re-reads out.bias, 4 bytes, once after the weights changed)."""
+    def _evaluate_on_device(self, X, y, batch_size, group=None, top=10):
+        """forward_logits over X in batches into one [R] buffer, then one ops.binary_eval (and, with
+        group [R] int32, one ops.group_eval: the pair is returned): nothing is read back here
+        (forward_logits itself re-reads out.bias, 4 bytes, once after the weights changed)."""
         R = X.shape[0]
         logits = torch.empty(R, device=X.device, dtype=torch.float32)
         for s in range(0, R, batch_size):
             logits[s:s + batch_size].copy_(self.forward_logits(X[s:s + batch_size])[0])
-        return ops.binary_eval(logits, y)
+        be = ops.binary_eval(logits, y)
+        return be if group is None else (be, ops.group_eval(logits, y, group, top=top))
 
-    def evaluate(self, X, y, batch_size=65536):
+    def evaluate(self, X, y, batch_size=65536, group_id=None, top=10):
         """{"Logloss", "AUC"} of the model on X [R, F] / y [R] in {0, 1} (tensors or array-likes): the
         fused inference kernel over batches of batch_size (the last short batch included) and one
         device-side evaluation (ops.binary_eval: exact tie-aware ROC-AUC, mean Logloss), one host
-        read. AUC is NaN when y holds a single class."""
+        read. AUC is NaN when y holds a single class. With group_id [R] (integers in [0, 2^31), the
+        reference's per-customer group id; the rows of a group anywhere) the dict gains "NDCG" (the
+        mean tie-averaged NDCG@top over the groups with a positive) and "QueryAUC" (the mean AUC
+        over the groups with both classes) from ops.group_eval, still one host read; NaN when no
+        group qualifies."""
         X, y = self._rows_on_device(X, y)
-        res = self._evaluate_on_device(X, y, int(batch_size)).result()
-        return {"Logloss": res["logloss"], "AUC": res["auc"]}
+        return _evaluate_result(self._evaluate_on_device, (X, y), y, int(batch_size), group_id, top)
 
     def fit(self, X, y, batch_size, epochs=1, shuffle=True, seed=0, eval_set=None, eval_metric="AUC",
-            early_stopping_rounds=None, use_best_model=None, eval_every=None, **trainer_kw):
+            early_stopping_rounds=None, use_best_model=None, eval_every=None, eval_group_id=None, **trainer_kw):
         """Train on X [R, F] int64 / y [R] in {0, 1} (the slot of RecommendationRanker.train :114-137)
         for `epochs` passes in batches of batch_size (the last short batch included; row order
         shuffled per epoch from `seed`). Returns the completed epochs' mean row losses (one host read
@@ -278,13 +348,26 @@ class DeepFM(nn.Module):
         {"Logloss": [...], "AUC": [...]}} (learn: the mean training loss since the previous
         evaluation), best_iteration_ (0-based index of the best evaluation) and best_score_ =
         {"validation": {"Logloss", "AUC"}} at it. ValueError before the first step for an unknown
-        eval_metric, validation labels outside {0, 1}, or a single class with eval_metric "AUC"."""
-        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every)
+        eval_metric, validation labels outside {0, 1}, or a single class with eval_metric "AUC".
+
+        eval_group_id [validation rows] (integers in [0, 2^31): the reference's per-customer group id
+        of its ranker rows) adds the per-query metrics of evaluate(group_id=...): every evaluation also
+        records "NDCG" and "QueryAUC" under evals_result_["validation"] and best_score_["validation"]
+        (the binary block, the group block and the learn mean in one copy: still one host read per
+        evaluation), and eval_metric may be "NDCG" (NDCG@10), "NDCG:top=K" or "QueryAUC" (larger is
+        better). Without it nothing changes. ValueError before the first step for a per-group
+        eval_metric without eval_group_id, a malformed or out-of-range ":top=K", a length other than
+        the validation rows', an id outside [0, 2^31), "NDCG" with no group that holds a positive or
+        "QueryAUC" with no group that holds both classes (one more host read up front)."""
+        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every,
+                                   eval_group_id)
         validate = None
         if eval_set is not None:
             Xv, yv = self._rows_on_device(*eval_set)
             _fit_eval_labels(yv, eval_metric)
-            validate = lambda: self._evaluate_on_device(Xv, yv, 65536)   # noqa: E731
+            gv = None if eval_group_id is None else _fit_eval_groups(yv, eval_group_id, eval_metric)
+            top = _parse_eval_metric(eval_metric)[1]
+            validate = lambda: self._evaluate_on_device(Xv, yv, 65536, gv, top)   # noqa: E731
         tr = self.make_trainer(**trainer_kw)
         X, y = self._rows_on_device(X, y)
         return _fit_loop(self, tr, lambda sel: tr.step(X[sel], y[sel]), X.shape[0], X.device, batch_size, epochs,
@@ -580,39 +663,46 @@ class RankingModel(nn.Module):
         return parts, y
 
     @torch.no_grad()
-    def _evaluate_on_device(self, parts, y, batch_size):
-        """forward_logits over the rows in batches into one [R] buffer, then one ops.binary_eval."""
+    def _evaluate_on_device(self, parts, y, batch_size, group=None, top=10):
+        """forward_logits over the rows in batches into one [R] buffer, then one ops.binary_eval (and,
+        with group [R] int32, one ops.group_eval: the pair is returned)."""
         R = y.numel()
         logits = torch.empty(R, device=y.device, dtype=torch.float32)
         ctx = parts[2] if len(parts) > 2 else None
         for s in range(0, R, batch_size):
             e = s + batch_size
             logits[s:e].copy_(self.forward_logits(parts[0][s:e], parts[1][s:e], None if ctx is None else ctx[s:e]))
-        return ops.binary_eval(logits, y)
+        be = ops.binary_eval(logits, y)
+        return be if group is None else (be, ops.group_eval(logits, y, group, top=top))
 
-    def evaluate(self, user, item, context, y, batch_size=65536):
+    def evaluate(self, user, item, context, y, batch_size=65536, group_id=None, top=10):
         """{"Logloss", "AUC"} of the model on the rows (user [R, du], item [R, di], context [R, dc] or
         None) against y [R] in {0, 1}: the inference path over batches of batch_size and one
-        device-side evaluation (ops.binary_eval), one host read. AUC is NaN when y holds one class."""
+        device-side evaluation (ops.binary_eval), one host read. AUC is NaN when y holds one class.
+        group_id [R] adds "NDCG" (at top) and "QueryAUC" as DeepFM.evaluate documents."""
         parts, y = self._rows_on_device(user, item, context, y)
-        res = self._evaluate_on_device(parts, y, int(batch_size)).result()
-        return {"Logloss": res["logloss"], "AUC": res["auc"]}
+        return _evaluate_result(self._evaluate_on_device, (parts, y), y, int(batch_size), group_id, top)
 
     def fit(self, user, item, context, y, batch_size, epochs=1, shuffle=True, seed=0, eval_set=None,
-            eval_metric="AUC", early_stopping_rounds=None, use_best_model=None, eval_every=None, **trainer_kw):
+            eval_metric="AUC", early_stopping_rounds=None, use_best_model=None, eval_every=None, eval_group_id=None,
+            **trainer_kw):
         """Train on the rows (user, item, context or None) / y [R] in {0, 1} with exactly the semantics
         documented on DeepFM.fit (one shared loop): batches of batch_size, the row order shuffled per
         epoch from `seed`, the completed epochs' mean row losses returned; eval_set = (user, item,
         context, y) with eval_metric, early_stopping_rounds, use_best_model (the device snapshot
-        restored into the same Parameter objects) and eval_every; evals_result_, best_iteration_,
-        best_score_; the same ValueErrors. trainer_kw: make_trainer's other arguments (`seed` also seeds
-        the trainer's dropout masks, so one seed reproduces a fit)."""
-        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every)
+        restored into the same Parameter objects), eval_every and eval_group_id (the per-query "NDCG" /
+        "NDCG:top=K" / "QueryAUC"); evals_result_, best_iteration_, best_score_; the same ValueErrors.
+        trainer_kw: make_trainer's other arguments (`seed` also seeds the trainer's dropout masks, so
+        one seed reproduces a fit)."""
+        use_best_model = _fit_args(eval_set, eval_metric, early_stopping_rounds, use_best_model, eval_every,
+                                   eval_group_id)
         validate = None
         if eval_set is not None:
             pv, yv = self._rows_on_device(*eval_set)
             _fit_eval_labels(yv, eval_metric)
-            validate = lambda: self._evaluate_on_device(pv, yv, 65536)   # noqa: E731
+            gv = None if eval_group_id is None else _fit_eval_groups(yv, eval_group_id, eval_metric)
+            top = _parse_eval_metric(eval_metric)[1]
+            validate = lambda: self._evaluate_on_device(pv, yv, 65536, gv, top)   # noqa: E731
         tr = self.make_trainer(seed=seed, **trainer_kw)
         parts, y = self._rows_on_device(user, item, context, y)
         ctx = parts[2] if len(parts) > 2 else None
