@@ -1,5 +1,6 @@
 """Module- and step-level parity: recsys_amd SASRecUserTower + contrastive step on cuda:0 vs
-the CPU oracle (same weights, same inputs, dropout p=0 so both views are deterministic)."""
+the CPU oracle (same weights, same inputs, dropout p=0 so both views are deterministic). The same
+tower at p = 0.2 against float64 with host-rebuilt dropout masks: tests/test_gpu_dropout_exact.py."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -329,8 +330,10 @@ def test_native_tower_tail_rows_dropout(gpu):
     bit-identical to it; view 2's last query rows key their attention mask by their packed row as
     well (it used the user index, i.e. view 1's token masks), while the last layer's
     per-row ops past the attention key view 2's kept rows by their tail index (a different draw than
-    the all-rows program, not shared with any view-1 row), so those rows are only checked to be
-    finite and dropout-perturbed."""
+    the all-rows program, not shared with any view-1 row). Those rows, and every gradient of the tail
+    form, are compared with a float64 reference under host-rebuilt masks in
+    tests/test_gpu_dropout_exact.py::test_tower_dropout_against_float64[tail]; here they only have to
+    be finite and to differ from the all-rows program's draw."""
     cfg = small_cfg(num_items=500, dropout=0.2)
     items = small_universe(500)
     batch = to_dev(synth.make_batch(items, 96, seed=23), gpu)
