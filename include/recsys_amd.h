@@ -142,6 +142,41 @@ int rsx_nce_bwd_x3(const float* A, const float* B, const float* bias, const int*
                    int64_t diag_offset, float tau, int flags, const float* gout, float* ws, float* dA, float* dB,
                    int accumulate, void* stream);
 
+/* Plain-family view of the fused grouped kernels (rsx_nce_grouped_fwd_grad and the grouped column
+ * pass, below): the same objective as rsx_nce_fwd_x3 for
+ *   flags 0                          (label = column i + diag_offset), and
+ *   flags 9 (EXCL_DIAG|POS) with bias == NULL  (SupCon; keys k1a [N], k1b [M]),
+ * anything else is an argument error. The N x M problem is run as a grouped one whose groups are
+ * trivial (every column distinct with multiplicity 1; row i's one exception is its diagonal column,
+ * kept at weight 1 as the label for flags 0 and dropped for flags 9), so the forward also gives the
+ * row gradient and the backward is the column pass alone: two sweeps over the logits instead of
+ * the plain family's three.
+ *   view: rsx_nce_view_ints(N, M) ints filled by rsx_nce_view_fill (device memory, one launch) or
+ *         rsx_nce_view_fill_host (host memory); depends on (N, M, diag_offset) only, so a caller
+ *         with a fixed batch size fills it once.
+ *   ws:   rsx_nce_fused_workspace_floats(N, M) floats, shared by the two calls.
+ * Products: RSX_NCE_BF16X3 (see below) in both sweeps, whatever the grouped loss's mode. The one-fp16-MFMA
+ * gradient products of RSX_NCE_F16 are not offered here: near convergence these two terms' gradients are
+ * what is left after the softmax-weighted sum cancels against the label / the positives' mean, and 11-bit
+ * products then leave up to 2.5e-2 of the gradient's scale (bf16x3: below 1e-3).
+ * rsx_nce_fwd_grad: out2 as rsx_nce_fwd_x3; ga [N][128] = d(out2[0])/dA per unit upstream gradient
+ * (dA = gout * ga); lse stays in ws. rsx_nce_bwd_cols writes dB [M][128] and must follow the forward
+ * on the same ws. SupCon's positive term (mean positive logit) is sparse and runs in fp32 beside
+ * the sweeps: per row cnt_i, P_i = sum of the positives' rows of B (ascending j) before the merge,
+ * per column the sum of A_i / cnt_i over the rows that hold it as a positive (ascending i) after the
+ * split sum. No float atomics: both calls are deterministic. A row without positives has zero loss
+ * and gradient and is not counted in out2[1]. */
+int64_t rsx_nce_fused_workspace_floats(int64_t N, int64_t M);
+int64_t rsx_nce_view_ints(int64_t N, int64_t M);
+int rsx_nce_view_fill(int64_t N, int64_t M, int64_t diag_offset, int* view, void* stream);
+int rsx_nce_view_fill_host(int64_t N, int64_t M, int64_t diag_offset, int* view);
+int rsx_nce_fwd_grad(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b, int64_t N,
+                     int64_t M, int64_t lda, int64_t ldb, int64_t diag_offset, float tau, int flags,
+                     const int* view, float* ws, float* out2, float* ga, void* stream);
+int rsx_nce_bwd_cols(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b, int64_t N,
+                     int64_t M, int64_t lda, int64_t ldb, int64_t diag_offset, float tau, int flags,
+                     const int* view, const float* gout, float* ws, float* dB, void* stream);
+
 /* Hard-emphasis term of full_batch_hard_emphasis_loss (replaces the reference's dense emphasis tensor,
  * scatter_ and masked cross-entropy over N x N logits, tower_code/v1_refine_usertower.py:762-822): row i's
  * K mined columns top[i*K + r] (int64, from rsx_hnm_mine) get +margin (already divided by tau) on top of
@@ -192,7 +227,8 @@ int rsx_nce_emphasis_bwd_csr(const float* A, const float* B, const float* bias, 
  *            products, v1_usertower_train.py:787, with fp32 accumulation; RSX_NCE_F16_GP=2 adds the
  *            lo image); in the column pass the logits take two of the three products (the streamed rows'
  *            lo image dropped: ~2e-5 on unit vectors); elsewhere
- *            (rsx_nce_grouped_fwd, the row pass) as RSX_NCE_BF16X3.
+ *            (rsx_nce_grouped_fwd, the row pass) as RSX_NCE_BF16X3. RSX_NCE_F16 covers the grouped
+ *            loss only: the plain view above (rsx_nce_fwd_grad / rsx_nce_bwd_cols) runs bf16x3 products.
  *            Precondition of RSX_NCE_F16: every component of A and B has |x| < 256, so that x * 2^8
  *            stays inside fp16's range; the callers pass unit-norm rows. */
 #define RSX_NCE_FP32 0

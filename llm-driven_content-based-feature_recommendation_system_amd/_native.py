@@ -53,6 +53,14 @@ _SIGS = {
                              c_p]),
     "rsx_nce_bwd_x3": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_i, c_p, c_p,
                              c_p, c_p, c_i, c_p]),
+    "rsx_nce_fused_workspace_floats": (c_i64, [c_i64, c_i64]),
+    "rsx_nce_view_ints": (c_i64, [c_i64, c_i64]),
+    "rsx_nce_view_fill": (c_i, [c_i64, c_i64, c_i64, c_p, c_p]),
+    "rsx_nce_view_fill_host": (c_i, [c_i64, c_i64, c_i64, c_p]),
+    "rsx_nce_fwd_grad": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_i, c_p, c_p, c_p,
+                               c_p, c_p]),
+    "rsx_nce_bwd_cols": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_i, c_p, c_p, c_p,
+                               c_p, c_p]),
     "rsx_nce_emphasis_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_f,
                                    c_i, c_i, c_p, c_p, c_p]),
     "rsx_nce_emphasis_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_f,

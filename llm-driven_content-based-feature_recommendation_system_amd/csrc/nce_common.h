@@ -255,6 +255,45 @@ struct GroupedLayout : PlainLayout {
         total(img + (precision != RSX_NCE_FP32 ? (N + D) * kD + 64 : 0)) {}
 };
 
+// Plain-family view of the grouped kernels (rsx_nce_fwd_grad / rsx_nce_bwd_cols): the plain N x M
+// problem as a grouped one with trivial groups. D = M, every column distinct with multiplicity 1;
+// row i's one exception is its diagonal column i + off, column j's one exception the row j - off.
+// The weight rule c - n = 0 then excludes the diagonal and the label rule keeps it at weight 1.
+// The arrays depend on (N, M, off) only; 5 N + 3 M ints:
+//   lab [N] = i + off (row_col of flags 0, and every row's exception list exc_cols)
+//   none [N] = -1     (row_col of flags 9: no label column)
+//   beg [N] = i, end [N] = i + 1  (row_beg / row_end, and the columns' row ranges exc_s / exc_e)
+//   one [N] = 1       (exc_n)
+//   col_beg [M], col_end [M]: [j - off, j - off + 1) where 0 <= j - off < N, else empty
+//   colcnt [M] = 1.0f (float bits)
+struct ViewLayout {
+  int64_t lab = 0, none, beg, end, one, col_beg, col_end, colcnt, total;
+  ViewLayout(int64_t N, int64_t M)
+      : none(N), beg(2 * N), end(3 * N), one(4 * N), col_beg(5 * N), col_end(5 * N + M), colcnt(5 * N + 2 * M),
+        total(5 * N + 3 * M) {}
+};
+// entry k of the view (host and device: the device fill and the host fill of the CPU tests share it)
+__host__ __device__ inline int view_entry(int64_t k, int64_t N, int64_t M, int64_t off) {
+  if (k < 5 * N) {
+    const int64_t a = k / N, i = k % N;
+    return a == 0 ? (int)(i + off) : a == 1 ? -1 : a == 2 ? (int)i : a == 3 ? (int)(i + 1) : 1;
+  }
+  k -= 5 * N;
+  const int64_t a = k / M, r = k % M - off;
+  if (a == 2) return 0x3f800000;  // 1.0f
+  if (r < 0 || r >= N) return 0;
+  return a == 0 ? (int)r : (int)(r + 1);
+}
+// fused plain view (bf16x3 products only, see rsx_nce_fwd_grad): the grouped layout over (N, M) with
+// 8 forward slots and 8 column-pass splits, then SupCon's positive term: cnt [N] | ps [N] | P [N][128]
+constexpr int kNsplitFused = 8;
+struct FusedLayout : GroupedLayout {
+  int64_t pos_cnt, pos_ps, pos_P, total;
+  FusedLayout(int64_t N, int64_t M)
+      : GroupedLayout(N, M, kNsplitFused, RSX_NCE_BF16X3, kNsplitFused), pos_cnt(round_up(GroupedLayout::total, 4)),
+        pos_ps(pos_cnt + N), pos_P(round_up(pos_ps + N, 4)), total(pos_P + N * kD + 16) {}
+};
+
 struct Images {
   __bf16 *ahi, *alo, *bhi, *blo;
 };

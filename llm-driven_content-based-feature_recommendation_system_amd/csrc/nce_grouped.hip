@@ -1058,13 +1058,19 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwdg_x3p_k(GArgs a) {
 
 // merge of the fused forward: lse / row loss as nce_grouped_merge_k, plus the row gradient
 // per unit upstream gradient  ga_i = (sum_s O_s e^(m_s - M) / sum_s l_s e^(m_s - M) - B_d(i)) / tau
+// POS (the plain view's flags 9, SupCon): the row has no label column; its positive set enters through
+// pos_cnt / pos_ps / pos_P (nce_pos_rows_k) as loss_i = lse_i - ps_i / cnt_i and ga_i -= P_i / (tau cnt_i).
+// A row without positives is invalid: zero loss and gradient, and lse = +inf for the column pass
+// (every column weight of the row exactly 0). row_col is not read.
+template <bool POS>
 __global__ __launch_bounds__(256) void nce_grouped_merge_g_k(const float* A, const float* B, const float* bias,
                                                              const int* row_col, int64_t N, int64_t lda,
                                                              int64_t ldb, float inv_tau, int nsplit,
                                                              const float* part, const float* opart,
                                                              float* lse_out, float* row_loss, float* row_valid,
                                                              float* ga, int64_t rows1, int nsplit2, int nslots,
-                                                             int lab_out) {
+                                                             int lab_out, const float* pos_cnt, const float* pos_ps,
+                                                             const float* pos_P) {
   const int lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= N) return;
@@ -1081,12 +1087,19 @@ __global__ __launch_bounds__(256) void nce_grouped_merge_g_k(const float* A, con
   float t = l * f;
   for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
   const float lse = (mm == -INFINITY) ? -INFINITY : mm + logf(t);
-  const int d = row_col[i];
-  const float2 x = reinterpret_cast<const float2*>(A + i * lda)[lane];
-  const float2 y = reinterpret_cast<const float2*>(B + (int64_t)d * ldb)[lane];
-  float dd = x.x * y.x + x.y * y.y;
-  for (int o = 32; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
-  const float sii = dd * inv_tau - (bias ? bias[d] : 0.0f);
+  float2 y;
+  float sii = 0.0f, pcnt = 0.0f;
+  if (POS) {
+    pcnt = pos_cnt[i];
+    y = reinterpret_cast<const float2*>(pos_P + i * kD)[lane];
+  } else {
+    const int d = row_col[i];
+    const float2 x = reinterpret_cast<const float2*>(A + i * lda)[lane];
+    y = reinterpret_cast<const float2*>(B + (int64_t)d * ldb)[lane];
+    float dd = x.x * y.x + x.y * y.y;
+    for (int o = 32; o > 0; o >>= 1) dd += __shfl_xor(dd, o, 64);
+    sii = dd * inv_tau - (bias ? bias[d] : 0.0f);
+  }
   const float inv_t = (t > 0.0f) ? 1.0f / t : 0.0f;
   // every split's partial row is loaded unconditionally (all in flight at once) and a split
   // with no columns (f = 0: its slot was never written) is dropped by a select, not a branch
@@ -1106,6 +1119,18 @@ __global__ __launch_bounds__(256) void nce_grouped_merge_g_k(const float* A, con
   }
   // lab_out: the kernel left the label column out of its partial rows (nce_grouped_fwdg_h_k): its term
   // p_pos B_d(i) and the label's -B_d(i) enter together as (p_pos - 1) B_d(i), p_pos = e^(s_ii - lse)
+  if (POS) {
+    const bool valid = pcnt > 0.0f;
+    const float ic = valid ? 1.0f / pcnt : 0.0f;
+    const float2 g = make_float2(fmaf(-ic, y.x, acc.x) * inv_tau, fmaf(-ic, y.y, acc.y) * inv_tau);
+    reinterpret_cast<float2*>(ga + i * kD)[lane] = valid ? g : make_float2(0.0f, 0.0f);
+    if (lane == 0) {
+      lse_out[i] = valid ? lse : INFINITY;
+      row_loss[i] = valid ? lse - pos_ps[i] * ic : 0.0f;
+      row_valid[i] = valid ? 1.0f : 0.0f;
+    }
+    return;
+  }
   const float cy = lab_out ? ((lse == -INFINITY) ? -1.0f : __expf(sii - lse) - 1.0f) : -1.0f;
   reinterpret_cast<float2*>(ga + i * kD)[lane] = make_float2(fmaf(cy, y.x, acc.x) * inv_tau, fmaf(cy, y.y, acc.y) * inv_tau);
   if (lane == 0) {
@@ -1115,7 +1140,152 @@ __global__ __launch_bounds__(256) void nce_grouped_merge_g_k(const float* A, con
   }
 }
 
+// ---- plain-family view (rsx_nce_fwd_grad / rsx_nce_bwd_cols) ------------------------------
+__global__ __launch_bounds__(256) void nce_view_fill_k(int* view, int64_t N, int64_t M, int64_t off, int64_t total) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < total) view[k] = view_entry(k, N, M, off);
+}
+
+// SupCon's positive term, row side (flags 9): pos(i) = {j : k1b[j] == k1a[i] != 0, j != i + off}.
+// One wave per row scans the M keys and adds the matching rows of B in ascending j (fp32, a fixed
+// order): cnt_i = |pos(i)|, P_i = sum B_j, ps_i = <A_i, P_i> / tau.
+// Two chains of dependent loads are broken up. The key scan loads kPosScan x 64 keys per step. The
+// matches are first collected, in order, in a per-wave LDS list and then added kPosBatch rows at a
+// time with all of a batch's row loads in flight: on a Zipf batch a popular target has hundreds of
+// members spread over the whole batch, and one row load per match, each waited for, made these two
+// kernels take 78 and 93 us at batch 8192, as long as the MFMA sweeps beside them.
+constexpr int kPosScan = 16;
+constexpr int kPosList = 512;  // list entries per wave (flushed when 64 more may not fit)
+constexpr int kPosBatch = 8;
+
+// the matches of one 64-key block appended to the wave's list (ascending: lane order)
+__device__ __forceinline__ void pos_append(int* list, int& nl, unsigned long long mask, bool hit, int idx, int lane) {
+  if (hit) list[nl + __popcll(mask & ((1ull << lane) - 1))] = idx;
+  nl += __popcll(mask);
+}
+
+// acc += sum over the list of w_k X[list[k]] (W: w_k = 1 / cnt[list[k]], else 1), kPosBatch rows in flight
+template <bool W>
+__device__ __forceinline__ void pos_flush(const int* list, int& nl, const float* X, int64_t ld, const float* cnt,
+                                          int lane, float2& acc) {
+  __builtin_amdgcn_wave_barrier();  // the list's writes (this wave's lanes) before its reads
+  for (int t0 = 0; t0 < nl; t0 += kPosBatch) {
+    float2 v[kPosBatch];
+    float w[kPosBatch];
+#pragma unroll
+    for (int t = 0; t < kPosBatch; ++t) {
+      const int k = t0 + t < nl ? t0 + t : nl - 1;  // past the list: a valid row, not added
+      const int r = list[k];
+      v[t] = reinterpret_cast<const float2*>(X + (int64_t)r * ld)[lane];
+      w[t] = W ? cnt[r] : 1.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < kPosBatch; ++t) {
+      if (t0 + t < nl) {
+        const float f = W ? 1.0f / w[t] : 1.0f;
+        acc.x = fmaf(f, v[t].x, acc.x);
+        acc.y = fmaf(f, v[t].y, acc.y);
+      }
+    }
+  }
+  nl = 0;
+  __builtin_amdgcn_wave_barrier();  // the reads before the next block's writes
+}
+
+__global__ __launch_bounds__(256) void nce_pos_rows_k(const float* A, const float* B, const int* k1a, const int* k1b,
+                                                      int64_t N, int64_t M, int64_t lda, int64_t ldb, int64_t off,
+                                                      float inv_tau, float* cnt, float* ps, float* P) {
+  __shared__ int sList[4][kPosList];
+  const int lane = threadIdx.x & 63;
+  int* list = sList[threadIdx.x >> 6];
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= N) return;
+  const int key = k1a[i];
+  float2 acc = make_float2(0.0f, 0.0f);
+  int n = 0, nl = 0;
+  if (key != 0) {
+    for (int64_t j0 = 0; j0 < M; j0 += 64 * kPosScan) {
+      int kv[kPosScan];  // independent loads, all in flight at once; past the end: key 0, never a match
+#pragma unroll
+      for (int u = 0; u < kPosScan; ++u) {
+        const int64_t j = j0 + 64 * u + lane;
+        kv[u] = j < M ? k1b[j] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < kPosScan; ++u) {
+        const int64_t j = j0 + 64 * u + lane;
+        const bool hit = kv[u] == key && j != i + off;
+        const unsigned long long mask = __ballot(hit);
+        if (mask == 0) continue;
+        n += __popcll(mask);
+        pos_append(list, nl, mask, hit, (int)j, lane);
+        if (nl + 64 > kPosList) pos_flush<false>(list, nl, B, ldb, nullptr, lane, acc);
+      }
+    }
+    if (nl > 0) pos_flush<false>(list, nl, B, ldb, nullptr, lane, acc);
+  }
+  const float2 x = reinterpret_cast<const float2*>(A + i * lda)[lane];
+  float d = x.x * acc.x + x.y * acc.y;
+  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+  reinterpret_cast<float2*>(P + i * kD)[lane] = acc;
+  if (lane == 0) {
+    cnt[i] = (float)n;
+    ps[i] = d * inv_tau;
+  }
+}
+
+// Column side, after the column pass's split sum: dB_j -= gout / tau * sum_{i : j in pos(i)} A_i / cnt_i,
+// one wave per column, rows in ascending i (j in pos(i) makes row i valid: cnt_i >= 1).
+__global__ __launch_bounds__(256) void nce_pos_cols_k(const float* A, const int* k1a, const int* k1b, int64_t N,
+                                                      int64_t M, int64_t lda, int64_t off, float inv_tau,
+                                                      const float* cnt, const float* gout, float* dB) {
+  __shared__ int sList[4][kPosList];
+  const int lane = threadIdx.x & 63;
+  int* list = sList[threadIdx.x >> 6];
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= M) return;
+  const int key = k1b[j];
+  if (key == 0) return;
+  float2 acc = make_float2(0.0f, 0.0f);
+  bool any = false;
+  int nl = 0;
+  for (int64_t i0 = 0; i0 < N; i0 += 64 * kPosScan) {
+    int kv[kPosScan];
+#pragma unroll
+    for (int u = 0; u < kPosScan; ++u) {
+      const int64_t i = i0 + 64 * u + lane;
+      kv[u] = i < N ? k1a[i] : 0;
+    }
+#pragma unroll
+    for (int u = 0; u < kPosScan; ++u) {
+      const int64_t i = i0 + 64 * u + lane;
+      const bool hit = kv[u] == key && i + off != j;
+      const unsigned long long mask = __ballot(hit);
+      if (mask == 0) continue;
+      any = true;
+      pos_append(list, nl, mask, hit, (int)i, lane);
+      if (nl + 64 > kPosList) pos_flush<true>(list, nl, A, lda, cnt, lane, acc);
+    }
+  }
+  if (!any) return;
+  if (nl > 0) pos_flush<true>(list, nl, A, lda, cnt, lane, acc);
+  const float f = -gout[0] * inv_tau;
+  float2* dst = reinterpret_cast<float2*>(dB + j * kD) + lane;
+  float2 o = *dst;
+  o.x = fmaf(f, acc.x, o.x);
+  o.y = fmaf(f, acc.y, o.y);
+  *dst = o;
+}
+
 // ---- host side ------------------------------------------------------------------------
+// SupCon's positive term of the plain view, handed to the fused forward's merge
+struct PosTerm {
+  const int* k1a;
+  const int* k1b;
+  int64_t off;
+  float *cnt, *ps, *P;
+};
+
 // The fields every grouped entry point fills the same way; splits, spans and the workspace
 // pointers are set by the caller.
 GArgs grouped_args(const float* A, const float* B, const float* bias, const float* colcnt, const int* row_col,
@@ -1149,10 +1319,12 @@ KernelEvents& kernel_events() {
 
 // The two grouped forwards after their argument checks. ga == nullptr: the loss alone over nsplit
 // column splits; else fused with the row gradient ga, nsplit partial slots per row.
+// pos: the plain view's SupCon term (no label column; ga required); events: whether the fused kernel's
+// launch is bracketed for rsx_kernel_events (the main loss's launches only).
 int grouped_forward(const float* A, const float* B, const float* bias, const float* colcnt, const int* row_col,
                     const int* row_beg, const int* row_end, const int* exc_cols, int64_t N, int64_t D, int64_t lda,
                     int64_t ldb, float tau, int precision, int nsplit, float* ws, float* out2, float* ga,
-                    hipStream_t st) {
+                    hipStream_t st, const PosTerm* pos = nullptr, bool events = true) {
   if (N == 0) return zero_sums(out2, st);
   const GroupedLayout L(N, D, nsplit, precision);
   const bool h16 = precision == RSX_NCE_F16;
@@ -1197,7 +1369,7 @@ int grouped_forward(const float* A, const float* B, const float* bias, const flo
     g.dout = ws + L.dpart;
     const int blocks = (int)(rb1 * ns1 + (rbs - rb1) * (nsplit == 8 ? 8 : 0));
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    {
+    if (events) {
       KernelEvents& k = kernel_events();
       std::lock_guard<std::mutex> lk(k.mu);
       if (k.on && hipEventCreate(&ev0) == hipSuccess && hipEventCreate(&ev1) == hipSuccess) {
@@ -1209,9 +1381,19 @@ int grouped_forward(const float* A, const float* B, const float* bias, const flo
     else hipLaunchKernelGGL(nce_grouped_fwdg_x3p_k, dim3(blocks), dim3(256), 0, st, g);
     RSX_LAUNCHED();
     if (ev1) (void)hipEventRecord(ev1, st);
-    hipLaunchKernelGGL(nce_grouped_merge_g_k, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, A, B, bias, row_col,
-                       N, lda, ldb, g.inv_tau, ns1, g.part, g.dout, ws + L.lse, ws + L.row_loss, ws + L.row_valid, ga,
-                       rb1 * kOwnRows, 8, nsplit, h16 ? 1 : 0);
+    const dim3 mgrid((unsigned)((N + 3) / 4));
+    if (pos) {
+      hipLaunchKernelGGL(nce_pos_rows_k, mgrid, dim3(256), 0, st, A, B, pos->k1a, pos->k1b, N, D, lda, ldb, pos->off,
+                         g.inv_tau, pos->cnt, pos->ps, pos->P);
+      RSX_LAUNCHED();
+      hipLaunchKernelGGL(nce_grouped_merge_g_k<true>, mgrid, dim3(256), 0, st, A, B, bias, row_col, N, lda, ldb,
+                         g.inv_tau, ns1, g.part, g.dout, ws + L.lse, ws + L.row_loss, ws + L.row_valid, ga,
+                         rb1 * kOwnRows, 8, nsplit, 0, pos->cnt, pos->ps, pos->P);
+    } else {
+      hipLaunchKernelGGL(nce_grouped_merge_g_k<false>, mgrid, dim3(256), 0, st, A, B, bias, row_col, N, lda, ldb,
+                         g.inv_tau, ns1, g.part, g.dout, ws + L.lse, ws + L.row_loss, ws + L.row_valid, ga,
+                         rb1 * kOwnRows, 8, nsplit, h16 ? 1 : 0, nullptr, nullptr, nullptr);
+    }
   }
   RSX_LAUNCHED();
   launch_reduce(ws + L.row_loss, ws + L.row_valid, N, out2, st);
@@ -1351,6 +1533,115 @@ RSX_API int rsx_nce_grouped_bwd(const float* A, const float* B, const float* bia
     else hipLaunchKernelGGL(nce_grouped_bwd_k<false>, dim3(blocks), dim3(256), 0, st, g);
     RSX_LAUNCHED();
     launch_sum_splits(g.dout, ps, n_own, target, accumulate, st);
+    RSX_LAUNCHED();
+  }
+  return 0;
+}
+
+// ---- plain-family view of the fused kernels (include/recsys_amd.h) --------------------------
+namespace {
+
+// the view's arguments checked, and the grouped arguments over its arrays
+const char* fused_error(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b, int64_t N,
+                        int64_t M, int64_t lda, int64_t ldb, int64_t off, int flags) {
+  if (!(flags == 0 || (flags == (F_EXCL_DIAG | F_POS) && bias == nullptr)))
+    return "fused plain view: flags must be 0, or 9 without a bias";
+  if (flags != 0 && !(k1a && k1b)) return "flags 9 needs k1a and k1b";
+  if (!(N >= 0 && M >= 0 && N < (1ll << 30) && M < (1ll << 30))) return "N and M must be in [0, 2^30)";
+  if (const char* e = operand_error(A, B, lda, ldb)) return e;
+  return diag_error(N, M, off);
+}
+
+GArgs view_args(const float* A, const float* B, const float* bias, const int* view, int64_t N, int64_t M, int64_t lda,
+                int64_t ldb, float tau, int flags) {
+  const ViewLayout V(N, M);
+  GArgs g = grouped_args(A, B, bias, reinterpret_cast<const float*>(view + V.colcnt),
+                         view + (flags == 0 ? V.lab : V.none), view + V.beg, view + V.end, view + V.lab, N, M, lda,
+                         ldb, tau);
+  g.col_beg = view + V.col_beg;
+  g.col_end = view + V.col_end;
+  g.exc_s = view + V.beg;
+  g.exc_e = view + V.end;
+  g.exc_n = view + V.one;
+  return g;
+}
+
+}  // namespace
+
+RSX_API int64_t rsx_nce_fused_workspace_floats(int64_t N, int64_t M) {
+  return FusedLayout(N, M).total;
+}
+
+RSX_API int64_t rsx_nce_view_ints(int64_t N, int64_t M) { return ViewLayout(N, M).total; }
+
+RSX_API int rsx_nce_view_fill_host(int64_t N, int64_t M, int64_t diag_offset, int* view) {
+  RSX_ARG(view != nullptr || ViewLayout(N, M).total == 0, "null view");
+  NCE_REQUIRE(diag_error(N, M, diag_offset));
+  const int64_t total = ViewLayout(N, M).total;
+  for (int64_t k = 0; k < total; ++k) view[k] = view_entry(k, N, M, diag_offset);
+  return 0;
+}
+
+RSX_API int rsx_nce_view_fill(int64_t N, int64_t M, int64_t diag_offset, int* view, void* stream) {
+  RSX_ARG(view != nullptr, "null view");
+  RSX_ARG(N >= 0 && M >= 0 && N < (1ll << 30) && M < (1ll << 30), "N and M must be in [0, 2^30)");
+  NCE_REQUIRE(diag_error(N, M, diag_offset));
+  const int64_t total = ViewLayout(N, M).total;
+  if (total == 0) return 0;
+  hipLaunchKernelGGL(nce_view_fill_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, view,
+                     N, M, diag_offset, total);
+  RSX_LAUNCHED();
+  return 0;
+}
+
+RSX_API int rsx_nce_fwd_grad(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b,
+                             int64_t N, int64_t M, int64_t lda, int64_t ldb, int64_t diag_offset, float tau, int flags,
+                             const int* view, float* ws, float* out2, float* ga, void* stream) {
+  RSX_ARG(A && B && view && ws && out2 && ga, "null tensor");
+  NCE_REQUIRE(fused_error(A, B, bias, k1a, k1b, N, M, lda, ldb, diag_offset, flags));
+  const FusedLayout L(N, M);
+  const GArgs g = view_args(A, B, bias, view, N, M, lda, ldb, tau, flags);
+  const PosTerm pos = {k1a, k1b, diag_offset, ws + L.pos_cnt, ws + L.pos_ps, ws + L.pos_P};
+  return grouped_forward(A, B, bias, g.colcnt, g.row_col, g.row_beg, g.row_end, g.exc_cols, N, M, lda, ldb, tau,
+                         RSX_NCE_BF16X3, kNsplitFused, ws, out2, ga, (hipStream_t)stream, flags == 0 ? nullptr : &pos,
+                         false);
+}
+
+RSX_API int rsx_nce_bwd_cols(const float* A, const float* B, const float* bias, const int* k1a, const int* k1b,
+                             int64_t N, int64_t M, int64_t lda, int64_t ldb, int64_t diag_offset, float tau, int flags,
+                             const int* view, const float* gout, float* ws, float* dB, void* stream) {
+  RSX_ARG(A && B && view && ws && gout && dB, "null tensor");
+  NCE_REQUIRE(fused_error(A, B, bias, k1a, k1b, N, M, lda, ldb, diag_offset, flags));
+  hipStream_t st = (hipStream_t)stream;
+  if (M == 0) return 0;
+  if (N == 0) {
+    (void)hipMemsetAsync(dB, 0, (size_t)M * kD * sizeof(float), st);
+    RSX_LAUNCHED();
+    return 0;
+  }
+  const FusedLayout L(N, M);
+  const Images im = images_at(ws, L.img, N, M);
+  GArgs g = view_args(A, B, bias, view, N, M, lda, ldb, tau, flags);
+  g.lse = ws + L.lse;
+  g.gout = gout;
+  g.dout = ws + L.dpart;
+  g.ahi = im.ahi; g.alo = im.alo; g.bhi = im.bhi; g.blo = im.blo;
+  // 8 row splits: at batch 8192 the 64 owner blocks x 8 fill one round of two workgroups per CU
+  g.nsplit = kNsplitFused;
+  g.span = split_span(N, kNsplitFused);
+  g.split_major = 0;
+  const int64_t own_blocks = (M + kOwnRows - 1) / kOwnRows;
+  RSX_ARG(own_blocks * kNsplitFused < (1ll << 31), "too many workgroups");
+  const int blocks = (int)(own_blocks * kNsplitFused);
+  launch_split(A, lda, N, im.ahi, im.alo, false, st);
+  RSX_LAUNCHED();
+  hipLaunchKernelGGL((nce_grouped_bwd_x3_k<false, true>), dim3(blocks), dim3(256), 0, st, g);
+  RSX_LAUNCHED();
+  launch_sum_splits(g.dout, kNsplitFused, M, dB, 0, st);
+  RSX_LAUNCHED();
+  if (flags != 0) {
+    hipLaunchKernelGGL(nce_pos_cols_k, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, A, k1a, k1b, N, M, lda,
+                       diag_offset, g.inv_tau, ws + L.pos_cnt, gout, dB);
     RSX_LAUNCHED();
   }
   return 0;

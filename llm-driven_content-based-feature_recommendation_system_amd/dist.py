@@ -602,12 +602,14 @@ def contrastive_objective_dp(model, item_tower, log_q_tensor, batch, cfg, pretra
     z1_glob = all_gather_rows(z1, bcounts)
     z2_glob = all_gather_rows(z2, bcounts)
     t_glob_last = index.t_glob_last
+    # both terms in the grouped loss's precision mode (as contrastive_losses; fp32: the plain kernels)
+    prec = ops.nce_precision()
     un_sum, _ = ops.nce_sum(z1, z2_glob, tau=temperature, flags=ops.NCE_PLAIN, diag_offset=rank * B,
-                            tag="duorec")
+                            tag="duorec", precision=prec)
     sup_sum = cnt_glob = None
     if cfg.lambda_sup > 0:
         sup_sum, sup_cnt = ops.nce_sum(z1, z1_glob, None, last_t, t_glob_last, tau=temperature,
-                                       flags=ops.NCE_SUPCON, diag_offset=rank * B, tag="supcon")
+                                       flags=ops.NCE_SUPCON, diag_offset=rank * B, tag="supcon", precision=prec)
         cnt_glob = sup_cnt.detach()
         if ws > 1:
             cnt_glob = all_reduce_sum_(cnt_glob.clone())

@@ -607,19 +607,96 @@ def _i32(t):
     return None if t is None else t.to(torch.int32)
 
 
+# The plain view's index arrays (rsx_nce_view_fill) depend on (N, M, diag_offset) only: filled once per
+# size and device and kept (a training run has one batch size; the cache holds a few evaluation sizes too).
+_nce_views: dict = {}
+
+
+def _nce_view(n, m, off, device):
+    key = (n, m, off, device)
+    view = _nce_views.get(key)
+    if view is None:
+        if len(_nce_views) >= 16:
+            _nce_views.clear()
+        view = torch.empty(max(1, N.lib().rsx_nce_view_ints(n, m)), device=device, dtype=torch.int32)
+        N.check(N.lib().rsx_nce_view_fill(n, m, off, N.ptr(view), N.stream()), "nce_view_fill")
+        _nce_views[key] = view
+    return view
+
+
+class _NCEFused(torch.autograd.Function):
+    """_NCE for flags 0 and 9 (no bias) on the fused grouped kernels (rsx_nce_fwd_grad /
+    rsx_nce_bwd_cols, bf16x3 products): the forward also produces the row gradient, the backward is the
+    column pass."""
+
+    @staticmethod
+    def forward(ctx, A, B, bias, k1a, k1b, tau, flags, diag_offset, tag):
+        N.ensure_device(A)
+        A = _c(A)
+        B = _c(B)
+        n, m = A.shape[0], B.shape[0]
+        view = _nce_view(n, m, diag_offset, A.device)
+        ws = torch.empty(N.lib().rsx_nce_fused_workspace_floats(n, m), device=A.device, dtype=torch.float32)
+        out2 = torch.empty(2, device=A.device, dtype=torch.float32)
+        ga = torch.empty(n, 128, device=A.device, dtype=torch.float32)
+        k1a, k1b = _c(k1a), _c(k1b)
+        with timed(f"{tag}/nce_fwd"):
+            rc = N.lib().rsx_nce_fwd_grad(N.ptr(A), N.ptr(B), N.ptr(bias), N.ptr(k1a), N.ptr(k1b), n, m, A.stride(0),
+                                          B.stride(0), diag_offset, tau, flags, N.ptr(view), N.ptr(ws),
+                                          N.ptr(out2), N.ptr(ga), N.stream())
+        N.check(rc, "nce_fwd_grad")
+        ctx.save_for_backward(A, B, bias, k1a, k1b, view, ws, ga)
+        ctx.cfg = (n, m, tau, flags, diag_offset, tag)
+        cnt = out2[1]
+        ctx.mark_non_differentiable(cnt)
+        return out2[0], cnt
+
+    @staticmethod
+    def backward(ctx, g, _gcnt):
+        A, B, bias, k1a, k1b, view, ws, ga = ctx.saved_tensors
+        n, m, tau, flags, off, tag = ctx.cfg
+        g = _c(g.reshape(1).to(torch.float32))
+        dA = ga * g  # the forward's row gradient, per unit upstream gradient
+        dB = None
+        if ctx.needs_input_grad[1]:
+            dB = torch.empty(m, 128, device=B.device, dtype=torch.float32)
+            with timed(f"{tag}/nce_bwd_cols"):
+                rc = N.lib().rsx_nce_bwd_cols(N.ptr(A), N.ptr(B), N.ptr(bias), N.ptr(k1a), N.ptr(k1b), n, m,
+                                              A.stride(0), B.stride(0), off, tau, flags, N.ptr(view), N.ptr(g),
+                                              N.ptr(ws), N.ptr(dB), N.stream())
+            N.check(rc, "nce_bwd_cols")
+        return dA, dB, None, None, None, None, None, None, None
+
+
 def nce_sum(A, B, bias=None, k1a=None, k1b=None, k2a=None, k2b=None, tau=0.1, flags=NCE_PLAIN, diag_offset=0,
-            tag="nce"):
+            tag="nce", precision=None):
     """(sum of row losses, valid-row count) of S = A B^T / tau - bias; row i's label column
-    is i + diag_offset (see include/recsys_amd.h)."""
+    is i + diag_offset (see include/recsys_amd.h).
+    precision: None = the plain kernels (bf16x3, or fp32 under set_nce_precision("fp32")), bit for bit
+    what they always gave. "bf16x3" | "f16" (the grouped loss's modes, as ops.nce_precision() names them)
+    = the fused grouped kernels where they apply (flags 0, and flags 9 without a bias, when A needs a
+    gradient), with bf16x3 products in both modes: the f16 mode's one-MFMA gradient products do not hold
+    1e-3 of the gradient's scale for these terms near convergence. "fp32" and every other case fall back
+    to the plain kernels."""
+    if precision is not None and precision not in NCE_PRECISIONS:
+        raise ValueError(f"precision must be None or one of {sorted(NCE_PRECISIONS)}")
     if bias is not None:
         bias = _c(bias.to(torch.float32))
-    return _NCE.apply(A, B, bias, _i32(k1a), _i32(k1b), _i32(k2a), _i32(k2b), float(tau), int(flags),
+    flags = int(flags)
+    fused = (precision in ("bf16x3", "f16") and A.requires_grad
+             and torch.is_grad_enabled() and A.shape[1] == 128 and B.shape[1] == 128 and A.shape[0] > 0
+             and (flags == NCE_PLAIN or (flags == NCE_SUPCON and bias is None and k1a is not None
+                                         and k1b is not None)))
+    if fused:
+        return _NCEFused.apply(A, B, bias, _i32(k1a), _i32(k1b), float(tau), flags, int(diag_offset), str(tag))
+    return _NCE.apply(A, B, bias, _i32(k1a), _i32(k1b), _i32(k2a), _i32(k2b), float(tau), flags,
                       int(diag_offset), str(tag))
 
 
-def nce_loss(A, B, bias=None, k1a=None, k1b=None, k2a=None, k2b=None, tau=0.1, flags=NCE_PLAIN, tag="nce"):
+def nce_loss(A, B, bias=None, k1a=None, k1b=None, k2a=None, k2b=None, tau=0.1, flags=NCE_PLAIN, tag="nce",
+             precision=None):
     """Mean InfoNCE over valid rows (0 if none), the reference's F.cross_entropy mean."""
-    total, cnt = nce_sum(A, B, bias, k1a, k1b, k2a, k2b, tau, flags, tag=tag)
+    total, cnt = nce_sum(A, B, bias, k1a, k1b, k2a, k2b, tau, flags, tag=tag, precision=precision)
     return total / cnt.clamp(min=1.0)
 
 

@@ -445,14 +445,15 @@ def inbatch_corrected_logq_loss_no_user(user_emb, item_tower_emb, target_ids, lo
     return ops.nce_loss(user_emb, batch_item_emb, bias, k1, k1, tau=temperature, flags=ops.NCE_MASK_ITEM)
 
 
-def duorec_loss_refined(user_emb_1, user_emb_2, target_ids, temperature=0.1, lambda_sup=0.1):
-    """Reference :576-627 (InfoNCE between views + lambda_sup * SupCon on same targets)."""
+def duorec_loss_refined(user_emb_1, user_emb_2, target_ids, temperature=0.1, lambda_sup=0.1, precision=None):
+    """Reference :576-627 (InfoNCE between views + lambda_sup * SupCon on same targets).
+    precision: ops.nce_sum's (None: the plain kernels; the training step passes ops.nce_precision())."""
     z_i = ops.l2_normalize(user_emb_1)
     z_j = ops.l2_normalize(user_emb_2)
-    loss_unsup = ops.nce_loss(z_i, z_j, tau=temperature, flags=ops.NCE_PLAIN)
+    loss_unsup = ops.nce_loss(z_i, z_j, tau=temperature, flags=ops.NCE_PLAIN, precision=precision)
     if lambda_sup > 0:
         k = _as_keys(target_ids)
-        loss_sup = ops.nce_loss(z_i, z_i, None, k, k, tau=temperature, flags=ops.NCE_SUPCON)
+        loss_sup = ops.nce_loss(z_i, z_i, None, k, k, tau=temperature, flags=ops.NCE_SUPCON, precision=precision)
         return loss_unsup + lambda_sup * loss_sup
     return loss_unsup + lambda_sup * torch.zeros((), device=z_i.device)
 

@@ -179,7 +179,9 @@ def contrastive_losses(model, item_tower, log_q_tensor, batch, cfg, pretrained_v
     last_output_1 = ops.gather_rows(out1, pk.last_tok, unique=True)
     last_output_2 = out2  # the tail rows: view 2's "last" row of every user, in user order
     last_targets = target_ids.reshape(-1)[pk.flat[pk.last_tok]]
-    cl_loss = duorec_loss_refined(last_output_1, last_output_2, last_targets, lambda_sup=cfg.lambda_sup)
+    # the grouped loss's precision mode also picks the kernels of the two small terms (fp32: the plain ones)
+    cl_loss = duorec_loss_refined(last_output_1, last_output_2, last_targets, lambda_sup=cfg.lambda_sup,
+                                  precision=ops.nce_precision())
     total_loss = main_loss + cfg.lambda_cl * cl_loss
     return total_loss, main_loss, cl_loss
 
