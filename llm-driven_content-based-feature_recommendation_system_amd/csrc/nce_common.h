@@ -35,6 +35,8 @@ struct FwdArgs {
   int nsplit;
   int64_t cols_per_split;
   float* part;  // [4][nsplit][N] : running max, sum-exp, positive-logit sum, positive count
+  const __bf16* shi;  // bf16x3: hi/lo images [M][128] of the streamed rows
+  const __bf16* slo;
 };
 
 __device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
@@ -100,7 +102,52 @@ struct BwdArgs {
   int nsplit;
   int64_t span_per_split;  // streamed rows per split
   float* dout;             // [nsplit][owner_rows][128] (split partials) or final when nsplit==1
+  const __bf16* shi;       // bf16x3: hi/lo images [streamed rows][128]
+  const __bf16* slo;
 };
+
+// ---------------------------------------------------------------------------------
+// Device helpers shared by the plain and the grouped kernels.
+//
+// Fold the two lane halves (same row i, complementary column sets) and write the split's partials
+// part[4][nsplit][N]. POS: the positive-logit sum and count planes carry ps / pc, else zeros.
+template <bool POS>
+__device__ __forceinline__ void fold_store_partials(float* part, int nsplit, int split, int64_t N, int64_t i,
+                                                    bool row_ok, int h, float m, float l, float ps, float pc) {
+  const float m2 = __shfl_xor(m, 32, 64);
+  const float l2 = __shfl_xor(l, 32, 64);
+  const float ps2 = POS ? __shfl_xor(ps, 32, 64) : 0.0f;
+  const float pc2 = POS ? __shfl_xor(pc, 32, 64) : 0.0f;
+  const float mm = fmaxf(m, m2);
+  float ll = 0.0f;
+  if (mm != -INFINITY) {
+    if (m != -INFINITY) ll += l * __expf(m - mm);
+    if (m2 != -INFINITY) ll += l2 * __expf(m2 - mm);
+  }
+  if (h == 0 && row_ok) {
+    const int64_t stride = (int64_t)nsplit * N;
+    const int64_t o = (int64_t)split * N + i;
+    part[o] = mm;
+    part[stride + o] = ll;
+    part[2 * stride + o] = POS ? ps + ps2 : 0.0f;
+    part[3 * stride + o] = POS ? pc + pc2 : 0.0f;
+  }
+}
+
+// One wave's 32 x 128 gradient tile to its owner rows: D[own_base + tile_row(r,h)][32kb + c] =
+// gacc[kb][r], times scale where SCALED (the fp16 kernels' operand scales)
+template <bool SCALED = false>
+__device__ __forceinline__ void store_d_own(int64_t own_base, float* dst, int64_t n_own, int h, int c,
+                                            const f32x16 (&gacc)[4], float scale = 1.0f) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int64_t orow = own_base + tile_row(r, h);
+    if (orow < n_own) {
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = SCALED ? gacc[kb][r] * scale : gacc[kb][r];
+    }
+  }
+}
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 

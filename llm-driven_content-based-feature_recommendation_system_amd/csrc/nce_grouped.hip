@@ -9,36 +9,6 @@ using namespace rsx::nce;
 
 namespace {
 
-__device__ __forceinline__ void load_owner(float (&u)[64], const float* base, int64_t row, int64_t ld, bool ok,
-                                           int h) {
-  if (ok) {
-    const float4* src = reinterpret_cast<const float4*>(base + row * ld + h * 64);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const float4 v = src[t];
-      u[4 * t + 0] = v.x; u[4 * t + 1] = v.y; u[4 * t + 2] = v.z; u[4 * t + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < 64; ++t) u[t] = 0.0f;
-  }
-}
-
-__device__ __forceinline__ f32x16 tile_dots(const float* xrow, const float (&u)[64]) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-  for (int s = 0; s < 64; s += 4) {
-    const float4 bv = *reinterpret_cast<const float4*>(xrow + s);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, u[s + 0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, u[s + 1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.z, u[s + 2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.w, u[s + 3], acc, 0, 0, 0);
-  }
-  return acc;
-}
-
 // Row-side weights for the tile [d0, d0+32): w[r] = multiplicity of column d0 + tile_row(r,h)
 // for row i (0 => excluded). p/next walk the row's sorted exception list.
 __device__ __forceinline__ void row_weights(float (&w)[16], const float* s_cnt, int64_t d0, int64_t d_end, int h,
@@ -66,7 +36,7 @@ __device__ __forceinline__ void row_weights(float (&w)[16], const float* s_cnt, 
 }
 
 __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
-  __shared__ __attribute__((aligned(16))) float sB[2][kTile][kLdsStride];
+  __shared__ __attribute__((aligned(16))) F32Prod::Tile sB[2];
   __shared__ __attribute__((aligned(16))) float sBias[2][kTile];
   __shared__ __attribute__((aligned(16))) float sCnt[2][kTile];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -75,8 +45,8 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
   remap_block(a.nsplit, split, rb);
   const int64_t i = (int64_t)rb * kOwnRows + wave * 32 + c;
   const bool row_ok = i < a.N;
-  float u[64];
-  load_owner(u, a.A, i, a.lda, row_ok, h);
+  F32Prod::Owner own;
+  F32Prod::load_owner(own, {}, a.A, i, a.lda, row_ok, h);
   const int64_t j_begin = (int64_t)split * a.span;
   int64_t j_end = j_begin + a.span;
   if (j_end > a.M) j_end = a.M;
@@ -89,19 +59,11 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
     next = (p < e) ? a.exc_cols[p] : 0x7fffffff;
   }
   float m = -INFINITY, l = 0.0f;
-  const int srow = tid >> 3, scol = (tid & 7) * 16;
-  float4 stg[4];
+  F32Prod::Stage stg = F32Prod::stage(tid);
   float stg_b = 0.0f, stg_c = 0.0f;
   auto gload = [&](int64_t j0) {
-    const int64_t j = j0 + srow;
-    if (j < j_end) {
-      const float4* src = reinterpret_cast<const float4*>(a.B + j * a.ldb + scol);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = src[t];
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    const int64_t j = j0 + (tid >> 3);
+    stg.load({a.B, a.ldb}, j, j < j_end, tid);
     if (tid < kTile) {
       const int64_t jj = j0 + tid;
       const bool ok = jj < j_end;
@@ -110,8 +72,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
     }
   };
   auto lstore = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(&sB[buf][srow][scol + 4 * t]) = stg[t];
+    stg.store(sB[buf], tid);
     if (tid < kTile) {
       sBias[buf][tid] = stg_b;
       sCnt[buf][tid] = stg_c;
@@ -125,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
     for (int64_t j0 = j_begin; j0 < j_end; j0 += kTile) {
       const bool has_next = j0 + kTile < j_end;
       if (has_next) gload(j0 + kTile);
-      const f32x16 acc = tile_dots(&sB[cur][c][h * 64], u);
+      const f32x16 acc = F32Prod::dots(sB[cur], own, {}, c, h);
       float w[16];
       row_weights(w, sCnt[cur], j0, j_end, h, di, a.exc_cols, p, e, next);
       float v[16];
@@ -152,22 +113,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwd_k(GArgs a) {
       cur ^= 1;
     }
   }
-  const float m2 = __shfl_xor(m, 32, 64);
-  const float l2 = __shfl_xor(l, 32, 64);
-  const float mm = fmaxf(m, m2);
-  float ll = 0.0f;
-  if (mm != -INFINITY) {
-    if (m != -INFINITY) ll += l * __expf(m - mm);
-    if (m2 != -INFINITY) ll += l2 * __expf(m2 - mm);
-  }
-  if (h == 0 && row_ok) {
-    const int64_t stride = (int64_t)a.nsplit * a.N;
-    const int64_t o = (int64_t)split * a.N + i;
-    a.part[o] = mm;
-    a.part[stride + o] = ll;
-    a.part[2 * stride + o] = 0.0f;
-    a.part[3 * stride + o] = 0.0f;
-  }
+  fold_store_partials<false>(a.part, a.nsplit, split, a.N, i, row_ok, h, m, l, 0.0f, 0.0f);
 }
 
 // merge for the grouped form: S_ii = <A_i, B_{d(i)}>/tau - bias_{d(i)}
@@ -205,7 +151,7 @@ __global__ __launch_bounds__(256) void nce_grouped_merge_k(const float* A, const
 
 template <bool ROW_OWNED>
 __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
-  __shared__ __attribute__((aligned(16))) float sX[2][kTile][kLdsStride];
+  __shared__ __attribute__((aligned(16))) F32Prod::Tile sX[2];
   __shared__ __attribute__((aligned(16))) float sM0[2][kTile];  // rows: lse_i  | cols: bias_d
   __shared__ __attribute__((aligned(16))) float sM1[2][kTile];  // cols: c_d
   __shared__ __attribute__((aligned(16))) int sM2[2][kTile];    // rows: d(i)
@@ -222,8 +168,8 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
   const float gs = a.gout[0] * a.inv_tau;
   const int64_t o = (int64_t)ob * kOwnRows + wave * 32 + c;
   const bool own_ok = o < n_own;
-  float u[64];
-  load_owner(u, own, o, ld_own, own_ok, h);
+  F32Prod::Owner u;
+  F32Prod::load_owner(u, {}, own, o, ld_own, own_ok, h);
   const int64_t s_begin = (int64_t)split * a.span;
   int64_t s_end = s_begin + a.span;
   if (s_end > n_str) s_end = n_str;
@@ -254,20 +200,12 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) gacc[kb][r] = 0.0f;
 
-  const int srow = tid >> 3, scol = (tid & 7) * 16;
-  float4 stg[4];
+  F32Prod::Stage stg = F32Prod::stage(tid);
   float stg0 = 0.0f, stg1 = 0.0f;
   int stg2 = 0;
   auto gload = [&](int64_t s0) {
-    const int64_t sidx = s0 + srow;
-    if (sidx < s_end) {
-      const float4* src = reinterpret_cast<const float4*>(str + sidx * ld_str + scol);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = src[t];
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    const int64_t sidx = s0 + (tid >> 3);
+    stg.load({str, ld_str}, sidx, sidx < s_end, tid);
     if (tid < kTile) {
       const int64_t ss = s0 + tid;
       const bool ok = ss < s_end;
@@ -281,8 +219,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
     }
   };
   auto lstore = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(&sX[buf][srow][scol + 4 * t]) = stg[t];
+    stg.store(sX[buf], tid);
     if (tid < kTile) {
       sM0[buf][tid] = stg0;
       sM1[buf][tid] = stg1;
@@ -298,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
     for (int64_t s0 = s_begin; s0 < s_end; s0 += kTile) {
       const bool has_next = s0 + kTile < s_end;
       if (has_next) gload(s0 + kTile);
-      f32x16 acc = tile_dots(&sX[cur][c][h * 64], u);
+      f32x16 acc = F32Prod::dots(sX[cur], u, {}, c, h);
       if (ROW_OWNED) {
         // exceptions of this row inside the tile: exc_cols[p, q)
         int q = p;
@@ -342,29 +279,14 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_k(GArgs a) {
           acc[r] = own_ok ? gs * (pr - (di == (int)o ? 1.0f : 0.0f)) : 0.0f;
         }
       }
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const float* srow_p = &sX[cur][tile_row(t, h)][c];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-          gacc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[t], srow_p[kb * 32], gacc[kb], 0, 0, 0);
-      }
+      F32Prod::grad(gacc, acc, sX[cur], lane, c, h);
       __syncthreads();
       if (has_next) lstore(cur ^ 1);
       __syncthreads();
       cur ^= 1;
     }
   }
-  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * n_own * kD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < n_own) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r];
-    }
-  }
+  store_d_own((int64_t)ob * kOwnRows + wave * 32, a.dout + (int64_t)split * n_own * kD, n_own, h, c, gacc);
 }
 
 // g = 2^(x - m) per element of the tile, summed into ls and split to hi/lo fragments, two elements
@@ -852,16 +774,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_x3_k(GArgs a) {
       cur ^= 1;
     }
   }
-  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * n_own * kD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < n_own) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r];
-    }
-  }
+  store_d_own((int64_t)ob * kOwnRows + wave * 32, a.dout + (int64_t)split * n_own * kD, n_own, h, c, gacc);
 }
 
 // Forward of the grouped loss fused with the row-side gradient (bf16x3). The row gradient
@@ -1043,16 +956,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwdg_x3p_k(GArgs a) {
     a.part[2 * stride + o] = 0.0f;
     a.part[3 * stride + o] = 0.0f;
   }
-  const int64_t own_base = rb * kRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * a.N * kD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < a.N) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r];
-    }
-  }
+  store_d_own(rb * kRows + wave * 32, a.dout + (int64_t)split * a.N * kD, a.N, h, c, gacc);
 }
 
 

@@ -314,6 +314,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwdg_h_k(GArgs a) {
     a.part[2 * stride + o] = 0.0f;
     a.part[3 * stride + o] = 0.0f;
   }
+  // not on store_d_own: with it hipcc allocates this kernel's registers differently (GP = 1)
   const int64_t own_base = rb * kRows + wave * 32;
   float* dst = a.dout + (int64_t)split * a.N * kD;
 #pragma unroll
@@ -541,17 +542,9 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
       cur ^= 1;
     }
   }
-  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * n_own * kD;
-  const float f = gs * (kHUnscale / kHGSv);  // gout / tau, the 2^-8 row scale and the 2^-14 weight scale
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < n_own) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r] * f;
-    }
-  }
+  // scale: gout / tau, the 2^-8 row scale and the 2^-14 weight scale
+  store_d_own<true>((int64_t)ob * kOwnRows + wave * 32, a.dout + (int64_t)split * n_own * kD, n_own, h, c, gacc,
+                    gs * (kHUnscale / kHGSv));
 }
 
 // RSX_NCE_F16_GP = 1 | 2: MFMAs per gradient-product k-step in the fp16 kernels (default 1)

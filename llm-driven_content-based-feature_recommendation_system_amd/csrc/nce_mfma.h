@@ -69,8 +69,15 @@ __device__ __forceinline__ void load_owner_x3(bf16x8 (&uh)[8], bf16x8 (&ul)[8], 
 // nce_split_k), so staging a tile is a plain copy: thread tid moves row tid>>3, 16-B chunks
 // tid&7 and 8+(tid&7) of both images (4 x 16-B loads, 4 ds_write_b128).
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+struct X3Src {
+  const __bf16* hi;  // the streamed operand's hi/lo images [rows][128]
+  const __bf16* lo;
+};
 struct X3Stage {
   u32x4 v[4];  // hi chunk0, hi chunk1, lo chunk0, lo chunk1
+  __device__ __forceinline__ void load(const X3Src& s, int64_t row, bool ok, int tid) {
+    load(s.hi, s.lo, row, ok, tid);
+  }
   __device__ __forceinline__ void load(const __bf16* hi, const __bf16* lo, int64_t row, bool ok, int tid) {
     if (ok) {
       const int64_t o = row * kD + (tid & 7) * 8;
@@ -137,30 +144,36 @@ __device__ __forceinline__ f32x16 dots_x3(const X3Tile& t, int c, int h, const b
   return acc;
 }
 
+// transposed reads of the gradient product: the lane's base offset (+ img_off(16ks + 8half, 32nb)
+// - img_off(0,0) per read) and the B fragment of step (ks, nb), two 4-row reads of one image
+__device__ __forceinline__ int grad_lane_base(int lane) {
+  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
+  return img_off(4 * h + q, 16 * cb + 4 * p);
+}
+
+__device__ __forceinline__ void grad_rd(const __bf16* img, int base, int ks, int nb, bf16x8& out) {
+  const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
+  const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
+  const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
+  out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
 // gacc[nb] += G^T X over the tile, G given as its hi/lo bf16 fragments (acc layout: streamed
 // row tile_row(r,h) in register r, owner on the lane; k-step ks takes registers 8ks..8ks+7,
 // i.e. streamed rows 16ks + 8(j>>2) + 4h + (j&3)). The B fragment is those rows of dims
 // 32nb + c, two transposed 4-row reads per image. Steps (ks, nb) are software-pipelined by one.
 __device__ __forceinline__ void grad_x3s(f32x16 (&gacc)[4], const bf16x8 (&gh)[2], const bf16x8 (&gl)[2],
                                          const X3Tile& t, int lane) {
-  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
-  const int base = img_off(4 * h + q, 16 * cb + 4 * p);  // + img_off(16ks + 8half, 32nb) - img_off(0,0)
-  auto rd = [&](const __bf16* img, int step, bf16x8& out) {
-    const int ks = step >> 2, nb = step & 3;
-    const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
-    const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
-    const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
-    out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
+  const int base = grad_lane_base(lane);
   bf16x8 bh, bl;
-  rd(t.hi, 0, bh);
-  rd(t.lo, 0, bl);
+  grad_rd(t.hi, base, 0, 0, bh);
+  grad_rd(t.lo, base, 0, 0, bl);
 #pragma unroll
   for (int step = 0; step < 8; ++step) {
     bf16x8 nh = bh, nl = bl;
     if (step < 7) {
-      rd(t.hi, step + 1, nh);
-      rd(t.lo, step + 1, nl);
+      grad_rd(t.hi, base, (step + 1) >> 2, (step + 1) & 3, nh);
+      grad_rd(t.lo, base, (step + 1) >> 2, (step + 1) & 3, nl);
     }
     const int ks = step >> 2, nb = step & 3;
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl[ks], bh, gacc[nb], 0, 0, 0);
@@ -201,17 +214,130 @@ __device__ __forceinline__ void split_tile(const f32x16& g, bf16x8 (&gh)[2], bf1
   }
 }
 
-__device__ __forceinline__ int grad_lane_base(int lane) {
-  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
-  return img_off(4 * h + q, 16 * cb + 4 * p);
-}
+// =====================================================================================
+// Product types: everything the fp32 and the bf16x3 form of one kernel body differ in.
+//   Owner, OwnerLo  the wave's 32 owner rows in registers (lane (c,h): dims 64h .. 64h+63 of row c),
+//          filled by load_owner. Two blocks, each a variable of its own in the kernel: bf16x3 keeps
+//          its hi and lo fragments apart (as one object hipcc vectorises their conversion differently
+//          and every bf16x3 kernel changes); fp32 has one block and an empty tag for the other.
+//   Src    where streamed rows come from; Stage: one thread's share of a tile on its way from Src to
+//          LDS (thread tid: row tid>>3), made by stage(tid); Tile: the LDS image of 32 streamed rows
+//   dots   acc[r] = <streamed row tile_row(r,h), owner row c> (owner on the lane)
+//   grad   gacc[kb] += G^T X over the tile, G in the layout dots returns: owner row c's gradient
+//          columns 32kb + n += sum_s G[s] X[tile_row(s,h)][32kb + n]; (c, h) = (lane & 31, lane >> 5)
+//   kStoreAfterBarrier  the next tile's Stage::store sits between two barriers (true) or ahead of
+//          the tile's only barrier (false: the buffer was last read in the previous tile)
+// Two conditions keep hipcc's output what it is for the same text written out in the kernel (DESIGN.md,
+// section 4): F32Prod::stage fixes the thread's row and column once, at kernel scope (computed inside
+// load and store they are sunk into the branch and computed twice), and a Src is built where it is
+// used (held in a local that the staging lambdas capture, it changes how the owner loads vectorise).
+struct F32Prod {
+  typedef float Tile[kTile][kLdsStride];
+  struct Src {
+    const float* p;
+    int64_t ld;
+  };
+  static __device__ __forceinline__ Src src(const float* p, int64_t ld, const __bf16*, const __bf16*) {
+    return {p, ld};
+  }
+  struct Owner {
+    float u[64];  // k permuted as k = 64h + s: a contiguous half row per lane
+  };
+  struct OwnerLo {};  // taken by value: it never reaches the generated code
+  static __device__ __forceinline__ void load_owner(Owner& o, OwnerLo, const float* base, int64_t row, int64_t ld,
+                                                    bool ok, int h) {
+    if (ok) {
+      const float4* src = reinterpret_cast<const float4*>(base + row * ld + h * 64);
+#pragma unroll
+      for (int t = 0; t < 16; ++t) {
+        const float4 v = src[t];
+        o.u[4 * t + 0] = v.x; o.u[4 * t + 1] = v.y; o.u[4 * t + 2] = v.z; o.u[4 * t + 3] = v.w;
+      }
+    } else {
+#pragma unroll
+      for (int t = 0; t < 64; ++t) o.u[t] = 0.0f;
+    }
+  }
+  struct Stage {
+    float4 v[4];     // 16 floats of row srow from column scol
+    int srow, scol;  // set once by stage(tid), at kernel scope
+    __device__ __forceinline__ void load(const Src& s, int64_t row, bool ok, int) {
+      if (ok) {
+        const float4* src = reinterpret_cast<const float4*>(s.p + row * s.ld + scol);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = src[t];
+      } else {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) v[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    }
+    __device__ __forceinline__ void store(Tile& t, int) const {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) *reinterpret_cast<float4*>(&t[srow][scol + 4 * k]) = v[k];
+    }
+  };
+  static __device__ __forceinline__ Stage stage(int tid) {
+    Stage s;
+    s.srow = tid >> 3;
+    s.scol = (tid & 7) * 16;
+    return s;
+  }
+  static constexpr bool kStoreAfterBarrier = true;
+  // v_mfma_f32_32x32x2_f32: an exact fp32 FMA chain
+  static __device__ __forceinline__ f32x16 dots(const Tile& t, const Owner& o, OwnerLo, int c, int h) {
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+    const float* xrow = &t[c][h * 64];
+#pragma unroll
+    for (int s = 0; s < 64; s += 4) {
+      const float4 bv = *reinterpret_cast<const float4*>(xrow + s);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, o.u[s + 0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, o.u[s + 1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.z, o.u[s + 2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.w, o.u[s + 3], acc, 0, 0, 0);
+    }
+    return acc;
+  }
+  // A operand (lane (c,h), step s) = G[own = c][str = tile_row(s,h)] = G[s], straight from the
+  // dots accumulator; B operand = X[tile_row(s,h)][32kb + c]
+  static __device__ __forceinline__ void grad(f32x16 (&gacc)[4], const f32x16& G, const Tile& t, int, int c,
+                                              int h) {
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      const float* srow_p = &t[tile_row(s, h)][c];
+#pragma unroll
+      for (int kb = 0; kb < 4; ++kb)
+        gacc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(G[s], srow_p[kb * 32], gacc[kb], 0, 0, 0);
+    }
+  }
+};
 
-__device__ __forceinline__ void grad_rd(const __bf16* img, int base, int ks, int nb, bf16x8& out) {
-  const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
-  const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
-  const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
-  out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
+struct X3Prod {
+  typedef X3Tile Tile;
+  typedef X3Src Src;
+  static __device__ __forceinline__ Src src(const float*, int64_t, const __bf16* hi, const __bf16* lo) {
+    return {hi, lo};
+  }
+  typedef bf16x8 Owner[8];
+  typedef bf16x8 OwnerLo[8];
+  static __device__ __forceinline__ void load_owner(Owner& uh, OwnerLo& ul, const float* base, int64_t row, int64_t ld,
+                                                    bool ok, int h) {
+    load_owner_x3(uh, ul, base, row, ld, ok, h);
+  }
+  typedef X3Stage Stage;
+  static __device__ __forceinline__ Stage stage(int) { return Stage(); }
+  static constexpr bool kStoreAfterBarrier = false;
+  static __device__ __forceinline__ f32x16 dots(const Tile& t, const Owner& o, const OwnerLo& ul, int c, int h) {
+    return dots_x3(t, c, h, o, ul);
+  }
+  static __device__ __forceinline__ void grad(f32x16 (&gacc)[4], const f32x16& G, const Tile& t, int lane, int,
+                                              int) {
+    bf16x8 gh[2], gl[2];
+    split_tile(G, gh, gl);
+    grad_x3s(gacc, gh, gl, t, lane);
+  }
+};
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));

@@ -14,16 +14,22 @@
 //       positives M_ij = (t_i==t_j) && t_i!=0 && i!=j, loss_i = LSE_i - sum_j M_ij S_ij / sum_j M_ij
 //   * item-tower SimCSE loss       item_tower.py:1075-1082 (both directions = two calls)
 //
-// This file: the plain (ungrouped) kernels, fp32 and bf16x3, and the small kernels every family
-// launches, behind nce_common.h's launchers. Grouped form: nce_grouped*.hip; emphasis: nce_emphasis.hip.
+// This file: the plain (ungrouped) kernels and the small kernels every family launches, behind
+// nce_common.h's launchers. Grouped form: nce_grouped*.hip; emphasis: nce_emphasis.hip.
 //
-// Dot products run on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: exact f32 FMA chain,
-// no reduced-precision path on gfx950). Each wave keeps 32 rows of its "owner" operand
-// in registers (64 VGPRs, k permuted as k = 64*h + s so each lane holds a contiguous
-// half row) and streams 32-row tiles of the other operand through LDS. The accumulator
-// tile is computed transposed (streamed rows in registers, owner row on the lane), so
-// the online log-sum-exp is lane-local and the tile doubles as the A operand of the
-// gradient MFMA in the backward (no LDS round trip for dS).
+// One forward body nce_fwd_k<FL, P> and one backward body nce_bwd_k<FL, ROW_OWNED, P> over a product
+// type P (nce_mfma.h): F32Prod, the fp32-input MFMA (v_mfma_f32_32x32x2_f32: exact f32 FMA chain, no
+// reduced-precision path on gfx950), or X3Prod, bf16x3 products on hi/lo images that the drivers
+// split into ws. The objective lives in the bodies, once per direction: the per-pair rule (excl,
+// offdiag, the same-key masks, SupCon's positives, the label y) and the online log-sum-exp; P only
+// says how rows are held, staged and multiplied. The pair rule is kept as plain text in both bodies,
+// not in a helper: hipcc compiles the short-circuit form and a call differently, and at 256 VGPRs
+// that moved the backward's spills.
+//
+// Each wave keeps 32 rows of its "owner" operand in registers and streams 32-row tiles of the other
+// operand through LDS. The accumulator tile is computed transposed (streamed rows in registers,
+// owner row on the lane), so the online log-sum-exp is lane-local and the tile doubles as the A
+// operand of the gradient MFMA in the backward (no LDS round trip for dS).
 #include "nce_common.h"
 #include "nce_mfma.h"
 
@@ -31,9 +37,9 @@ using namespace rsx::nce;
 
 namespace {
 
-template <int FL>
+template <int FL, typename P>
 __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float sB[2][kTile][kLdsStride];
+  __shared__ __attribute__((aligned(16))) typename P::Tile sT[2];
   __shared__ __attribute__((aligned(16))) float sBias[2][kTile];
   __shared__ __attribute__((aligned(16))) int sK1[2][kTile];
   __shared__ __attribute__((aligned(16))) int sK2[2][kTile];
@@ -45,18 +51,9 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
   const int64_t i = (int64_t)rb * kOwnRows + wave * 32 + c;
   const bool row_ok = i < a.N;
 
-  float u[64];
-  if (row_ok) {
-    const float4* src = reinterpret_cast<const float4*>(a.A + i * a.lda + h * 64);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const float4 v = src[t];
-      u[4 * t + 0] = v.x; u[4 * t + 1] = v.y; u[4 * t + 2] = v.z; u[4 * t + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < 64; ++t) u[t] = 0.0f;
-  }
+  typename P::Owner u;
+  typename P::OwnerLo ul;
+  P::load_owner(u, ul, a.A, i, a.lda, row_ok, h);
   int k1i = 0, k2i = 0;
   if (row_ok) {
     if ((FL & (F_MASK_K1 | F_POS)) && a.k1a) k1i = a.k1a[i];
@@ -69,21 +66,13 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
 
   float m = -INFINITY, l = 0.0f, ps = 0.0f, pc = 0.0f;
 
-  const int srow = tid >> 3, scol = (tid & 7) * 16;
-  float4 stg[4];
+  typename P::Stage stg = P::stage(tid);
   float stg_bias = 0.0f;
   int stg_k1 = 0, stg_k2 = 0;
 
   auto gload = [&](int64_t j0) {
-    const int64_t j = j0 + srow;
-    if (j < j_end) {
-      const float4* src = reinterpret_cast<const float4*>(a.B + j * a.ldb + scol);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = src[t];
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    const int64_t j = j0 + (tid >> 3);
+    stg.load(P::src(a.B, a.ldb, a.shi, a.slo), j, j < j_end, tid);
     if (tid < kTile) {
       const int64_t jj = j0 + tid;
       const bool ok = jj < j_end;
@@ -93,8 +82,7 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
     }
   };
   auto lstore = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(&sB[buf][srow][scol + 4 * t]) = stg[t];
+    stg.store(sT[buf], tid);
     if (tid < kTile) {
       sBias[buf][tid] = stg_bias;
       sK1[buf][tid] = stg_k1;
@@ -111,18 +99,7 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
       const bool has_next = j0 + kTile < j_end;
       if (has_next) gload(j0 + kTile);
 
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-      const float* brow = &sB[cur][c][h * 64];
-#pragma unroll
-      for (int s = 0; s < 64; s += 4) {
-        const float4 bv = *reinterpret_cast<const float4*>(brow + s);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, u[s + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, u[s + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.z, u[s + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.w, u[s + 3], acc, 0, 0, 0);
-      }
+      const f32x16 acc = P::dots(sT[cur], u, ul, c, h);
 
       float v[16];
       float tmax = -INFINITY;
@@ -165,32 +142,13 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
         for (int r = 0; r < 16; ++r) t += __expf(v[r] - m);
         l += t;
       }
-      __syncthreads();
+      if (P::kStoreAfterBarrier) __syncthreads();
       if (has_next) lstore(cur ^ 1);
       __syncthreads();
       cur ^= 1;
     }
   }
-
-  // fold the two lane halves (same row i, complementary column sets)
-  const float m2 = __shfl_xor(m, 32, 64);
-  const float l2 = __shfl_xor(l, 32, 64);
-  const float ps2 = __shfl_xor(ps, 32, 64);
-  const float pc2 = __shfl_xor(pc, 32, 64);
-  const float mm = fmaxf(m, m2);
-  float ll = 0.0f;
-  if (mm != -INFINITY) {
-    if (m != -INFINITY) ll += l * __expf(m - mm);
-    if (m2 != -INFINITY) ll += l2 * __expf(m2 - mm);
-  }
-  if (h == 0 && row_ok) {
-    const int64_t stride = (int64_t)a.nsplit * a.N;
-    const int64_t o = (int64_t)split * a.N + i;
-    a.part[o] = mm;
-    a.part[stride + o] = ll;
-    a.part[2 * stride + o] = ps + ps2;
-    a.part[3 * stride + o] = pc + pc2;
-  }
+  fold_store_partials<true>(a.part, a.nsplit, split, a.N, i, row_ok, h, m, l, ps, pc);
 }
 
 __global__ __launch_bounds__(256) void nce_merge_k(MergeArgs a) {
@@ -264,9 +222,9 @@ __global__ __launch_bounds__(1024) void nce_reduce_k(const float* row_loss, cons
   }
 }
 
-template <int FL, bool ROW_OWNED>
+template <int FL, bool ROW_OWNED, typename P>
 __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
-  __shared__ __attribute__((aligned(16))) float sX[2][kTile][kLdsStride];
+  __shared__ __attribute__((aligned(16))) typename P::Tile sT[2];
   __shared__ __attribute__((aligned(16))) float sM0[2][kTile];  // row side: lse_i | col side: bias_j
   __shared__ __attribute__((aligned(16))) float sM1[2][kTile];  // row side: w_i
   __shared__ __attribute__((aligned(16))) float sM2[2][kTile];  // row side: inv_cnt_i
@@ -288,18 +246,9 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
 
   const int64_t o = (int64_t)ob * kOwnRows + wave * 32 + c;  // this lane's owner index
   const bool own_ok = o < n_own;
-  float u[64];
-  if (own_ok) {
-    const float4* src = reinterpret_cast<const float4*>(own + o * ld_own + h * 64);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const float4 v = src[t];
-      u[4 * t + 0] = v.x; u[4 * t + 1] = v.y; u[4 * t + 2] = v.z; u[4 * t + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int t = 0; t < 64; ++t) u[t] = 0.0f;
-  }
+  typename P::Owner u;
+  typename P::OwnerLo ul;
+  P::load_owner(u, ul, own, o, ld_own, own_ok, h);
   // owner-side metadata
   float o_lse = 0.0f, o_w = 0.0f, o_icnt = 0.0f, o_bias = 0.0f;
   int o_k1 = 0, o_k2 = 0;
@@ -327,21 +276,13 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) gacc[kb][r] = 0.0f;
 
-  const int srow = tid >> 3, scol = (tid & 7) * 16;
-  float4 stg[4];
+  typename P::Stage stg = P::stage(tid);
   float stg0 = 0.0f, stg1 = 0.0f, stg2 = 0.0f;
   int stg_k1 = 0, stg_k2 = 0;
 
   auto gload = [&](int64_t s0) {
-    const int64_t sidx = s0 + srow;
-    if (sidx < s_end) {
-      const float4* src = reinterpret_cast<const float4*>(str + sidx * ld_str + scol);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = src[t];
-    } else {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) stg[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
+    const int64_t sidx = s0 + (tid >> 3);
+    stg.load(P::src(str, ld_str, a.shi, a.slo), sidx, sidx < s_end, tid);
     if (tid < kTile) {
       const int64_t ss = s0 + tid;
       const bool ok = ss < s_end;
@@ -359,8 +300,7 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
     }
   };
   auto lstore = [&](int buf) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) *reinterpret_cast<float4*>(&sX[buf][srow][scol + 4 * t]) = stg[t];
+    stg.store(sT[buf], tid);
     if (tid < kTile) {
       sM0[buf][tid] = stg0;
       sM1[buf][tid] = stg1;
@@ -379,20 +319,8 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
       const bool has_next = s0 + kTile < s_end;
       if (has_next) gload(s0 + kTile);
 
-      f32x16 acc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-      const float* xrow = &sX[cur][c][h * 64];
-#pragma unroll
-      for (int s = 0; s < 64; s += 4) {
-        const float4 bv = *reinterpret_cast<const float4*>(xrow + s);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.x, u[s + 0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.y, u[s + 1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.z, u[s + 2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(bv.w, u[s + 3], acc, 0, 0, 0);
-      }
-
       // acc[r] = <own_o, str_s>, s = s0 + tile_row(r,h). Turn it into G (in place).
+      f32x16 acc = P::dots(sT[cur], u, ul, c, h);
 #pragma unroll
       for (int q4 = 0; q4 < 4; ++q4) {
         const int rbase = 8 * q4 + 4 * h;
@@ -440,35 +368,16 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
         }
       }
 
-      // gradient MFMA: d_own[o][kb*32 + n] += sum_s G[o][s] * str[s][kb*32 + n]
-      // A operand (lane c,h, step t) = G[own=c][str=tile_row(t,h)] = acc[t]
-      // B operand = str[tile_row(t,h)][kb*32 + c]
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const float* srow_p = &sX[cur][tile_row(t, h)][c];
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-          gacc[kb] = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[t], srow_p[kb * 32], gacc[kb], 0, 0, 0);
-      }
+      // d_own[o][kb*32 + n] += sum_s G[o][s] * str[s][kb*32 + n]
+      P::grad(gacc, acc, sT[cur], lane, c, h);
 
-      __syncthreads();
+      if (P::kStoreAfterBarrier) __syncthreads();
       if (has_next) lstore(cur ^ 1);
       __syncthreads();
       cur ^= 1;
     }
   }
-
-  // write d_own rows: D[row = own-local tile_row(r,h)][col = kb*32 + c]
-  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * n_own * kD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < n_own) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r];
-    }
-  }
+  store_d_own((int64_t)ob * kOwnRows + wave * 32, a.dout + (int64_t)split * n_own * kD, n_own, h, c, gacc);
 }
 
 // Sum split partials: out[i][k] (+)= sum_s part[s][i][k]
@@ -490,7 +399,9 @@ __global__ __launch_bounds__(256) void nce_sum_splits_k(const float* part, int n
   reinterpret_cast<float4*>(out)[idx] = s;
 }
 
-// rows x 128 fp32 (row stride ld) -> hi/lo bf16 images [rows][128]; one thread per 8 floats
+// rows x 128 fp32 (row stride ld) -> hi/lo images [rows][128], one thread per 8 floats: bf16, or
+// (HALF) the fp16 images of x * 2^8 in the same containers
+template <bool HALF>
 __global__ __launch_bounds__(256) void nce_split_k(const float* src, int64_t ld, int64_t rows, __bf16* hi,
                                                    __bf16* lo) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // 8-float chunk index
@@ -498,301 +409,10 @@ __global__ __launch_bounds__(256) void nce_split_k(const float* src, int64_t ld,
   const int64_t r = i / (kD / 8), c8 = i % (kD / 8);
   const float4* p = reinterpret_cast<const float4*>(src + r * ld + c8 * 8);
   bf16x8 h, l;
-  split8(p[0], p[1], h, l);
+  if (HALF) split8_h(p[0], p[1], h, l);
+  else split8(p[0], p[1], h, l);
   *reinterpret_cast<bf16x8*>(hi + r * kD + c8 * 8) = h;
   *reinterpret_cast<bf16x8*>(lo + r * kD + c8 * 8) = l;
-}
-
-// rows x 128 fp32 -> fp16 hi/lo images of x * 2^8 (nce_split_k's layout)
-__global__ __launch_bounds__(256) void nce_split_h_k(const float* src, int64_t ld, int64_t rows, __bf16* hi,
-                                                     __bf16* lo) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows * (kD / 8)) return;
-  const int64_t r = i / (kD / 8), c8 = i % (kD / 8);
-  const float4* p = reinterpret_cast<const float4*>(src + r * ld + c8 * 8);
-  bf16x8 h, l;
-  split8_h(p[0], p[1], h, l);
-  *reinterpret_cast<bf16x8*>(hi + r * kD + c8 * 8) = h;
-  *reinterpret_cast<bf16x8*>(lo + r * kD + c8 * 8) = l;
-}
-
-// ---- plain (ungrouped) InfoNCE in bf16x3: DuoRec unsup/sup, SimCSE -------------------
-// The objective, flags and partial layout of nce_fwd_k / nce_bwd_k; the products as in the
-// grouped bf16x3 kernels (streamed hi/lo images copied from ws into LDS, owner fragments in
-// registers, S tile on dots_x3, gradient tile split and fed to grad_x3s), one barrier per tile.
-struct X3Args {
-  const __bf16* shi;  // streamed operand's hi/lo images [rows][128]
-  const __bf16* slo;
-};
-
-template <int FL>
-__global__ __launch_bounds__(256, 2) void nce_fwd_x3_k(FwdArgs a, X3Args x) {
-  __shared__ __attribute__((aligned(16))) X3Tile sT[2];
-  __shared__ __attribute__((aligned(16))) float sBias[2][kTile];
-  __shared__ __attribute__((aligned(16))) int sK1[2][kTile];
-  __shared__ __attribute__((aligned(16))) int sK2[2][kTile];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = lane >> 5, c = lane & 31;
-  int split, rb;
-  remap_block(a.nsplit, split, rb);
-  const int64_t i = (int64_t)rb * kOwnRows + wave * 32 + c;
-  const bool row_ok = i < a.N;
-  bf16x8 uh[8], ul[8];
-  load_owner_x3(uh, ul, a.A, i, a.lda, row_ok, h);
-  int k1i = 0, k2i = 0;
-  if (row_ok) {
-    if ((FL & (F_MASK_K1 | F_POS)) && a.k1a) k1i = a.k1a[i];
-    if ((FL & F_MASK_K2) && a.k2a) k2i = a.k2a[i];
-  }
-  const int64_t j_begin = (int64_t)split * a.cols_per_split;
-  int64_t j_end = j_begin + a.cols_per_split;
-  if (j_end > a.M) j_end = a.M;
-  float m = -INFINITY, l = 0.0f, ps = 0.0f, pc = 0.0f;
-  X3Stage stg;
-  float stg_bias = 0.0f;
-  int stg_k1 = 0, stg_k2 = 0;
-  auto gload = [&](int64_t j0) {
-    const int64_t j = j0 + (tid >> 3);
-    stg.load(x.shi, x.slo, j, j < j_end, tid);
-    if (tid < kTile) {
-      const int64_t jj = j0 + tid;
-      const bool ok = jj < j_end;
-      stg_bias = (ok && a.bias) ? a.bias[jj] : 0.0f;
-      stg_k1 = (ok && a.k1b) ? a.k1b[jj] : 0;
-      stg_k2 = (ok && a.k2b) ? a.k2b[jj] : 0;
-    }
-  };
-  auto lstore = [&](int buf) {
-    stg.store(sT[buf], tid);
-    if (tid < kTile) {
-      sBias[buf][tid] = stg_bias;
-      sK1[buf][tid] = stg_k1;
-      sK2[buf][tid] = stg_k2;
-    }
-  };
-  if (j_begin < j_end) {
-    gload(j_begin);
-    lstore(0);
-    __syncthreads();
-    int cur = 0;
-    for (int64_t j0 = j_begin; j0 < j_end; j0 += kTile) {
-      const bool has_next = j0 + kTile < j_end;
-      if (has_next) gload(j0 + kTile);
-      const f32x16 acc = dots_x3(sT[cur], c, h, uh, ul);
-      float v[16];
-      float tmax = -INFINITY;
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int rbase = 8 * q4 + 4 * h;
-        const float4 bi4 = *reinterpret_cast<const float4*>(&sBias[cur][rbase]);
-        const int4 k14 = *reinterpret_cast<const int4*>(&sK1[cur][rbase]);
-        const int4 k24 = *reinterpret_cast<const int4*>(&sK2[cur][rbase]);
-        const float bia[4] = {bi4.x, bi4.y, bi4.z, bi4.w};
-        const int kk1[4] = {k14.x, k14.y, k14.z, k14.w};
-        const int kk2[4] = {k24.x, k24.y, k24.z, k24.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * q4 + e;
-          const int64_t j = j0 + rbase + e;
-          const float sv = acc[r] * a.inv_tau - bia[e];
-          bool excl = (j >= j_end) || !row_ok;
-          const bool offdiag = (j != i + a.diag_off);
-          if (FL & F_EXCL_DIAG) excl = excl || !offdiag;
-          if (FL & F_MASK_K1) excl = excl || (offdiag && kk1[e] == k1i);
-          if (FL & F_MASK_K2) excl = excl || (offdiag && kk2[e] == k2i);
-          if (FL & F_POS) {
-            if (!excl && offdiag && kk1[e] == k1i && k1i != 0) {
-              ps += sv;
-              pc += 1.0f;
-            }
-          }
-          v[r] = excl ? -INFINITY : sv;
-          tmax = fmaxf(tmax, v[r]);
-        }
-      }
-      if (tmax > m) {
-        l = (m == -INFINITY) ? 0.0f : l * __expf(m - tmax);
-        m = tmax;
-      }
-      if (m != -INFINITY) {
-        float t = 0.0f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += __expf(v[r] - m);
-        l += t;
-      }
-      if (has_next) lstore(cur ^ 1);  // cur^1: read in the previous tile, fenced by its barrier
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  const float m2 = __shfl_xor(m, 32, 64);
-  const float l2 = __shfl_xor(l, 32, 64);
-  const float ps2 = __shfl_xor(ps, 32, 64);
-  const float pc2 = __shfl_xor(pc, 32, 64);
-  const float mm = fmaxf(m, m2);
-  float ll = 0.0f;
-  if (mm != -INFINITY) {
-    if (m != -INFINITY) ll += l * __expf(m - mm);
-    if (m2 != -INFINITY) ll += l2 * __expf(m2 - mm);
-  }
-  if (h == 0 && row_ok) {
-    const int64_t stride = (int64_t)a.nsplit * a.N;
-    const int64_t o = (int64_t)split * a.N + i;
-    a.part[o] = mm;
-    a.part[stride + o] = ll;
-    a.part[2 * stride + o] = ps + ps2;
-    a.part[3 * stride + o] = pc + pc2;
-  }
-}
-
-template <int FL, bool ROW_OWNED>
-__global__ __launch_bounds__(256, 2) void nce_bwd_x3_k(BwdArgs a, X3Args x) {
-  __shared__ __attribute__((aligned(16))) X3Tile sT[2];
-  __shared__ __attribute__((aligned(16))) float sM0[2][kTile];  // row side: lse_i | col side: bias_j
-  __shared__ __attribute__((aligned(16))) float sM1[2][kTile];  // row side: w_i
-  __shared__ __attribute__((aligned(16))) float sM2[2][kTile];  // row side: inv_cnt_i
-  __shared__ __attribute__((aligned(16))) int sK1[2][kTile];
-  __shared__ __attribute__((aligned(16))) int sK2[2][kTile];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int h = lane >> 5, c = lane & 31;
-  int split, ob;
-  remap_block(a.nsplit, split, ob);
-  const int64_t n_own = ROW_OWNED ? a.N : a.M;
-  const int64_t n_str = ROW_OWNED ? a.M : a.N;
-  const float* own = ROW_OWNED ? a.A : a.B;
-  const int64_t ld_own = ROW_OWNED ? a.lda : a.ldb;
-  const float g_scale = a.gout[0] * a.inv_tau;
-  const int64_t o = (int64_t)ob * kOwnRows + wave * 32 + c;
-  const bool own_ok = o < n_own;
-  bf16x8 uh[8], ul[8];
-  load_owner_x3(uh, ul, own, o, ld_own, own_ok, h);
-  float o_lse = 0.0f, o_w = 0.0f, o_icnt = 0.0f, o_bias = 0.0f;
-  int o_k1 = 0, o_k2 = 0;
-  if (own_ok) {
-    if (ROW_OWNED) {
-      o_lse = a.lse[o];
-      o_w = a.row_valid[o] * g_scale;
-      if ((FL & F_POS) && a.inv_cnt) o_icnt = a.inv_cnt[o];
-      if ((FL & (F_MASK_K1 | F_POS)) && a.k1a) o_k1 = a.k1a[o];
-      if ((FL & F_MASK_K2) && a.k2a) o_k2 = a.k2a[o];
-    } else {
-      o_bias = a.bias ? a.bias[o] : 0.0f;
-      if ((FL & (F_MASK_K1 | F_POS)) && a.k1b) o_k1 = a.k1b[o];
-      if ((FL & F_MASK_K2) && a.k2b) o_k2 = a.k2b[o];
-    }
-  }
-  const int64_t s_begin = (int64_t)split * a.span_per_split;
-  int64_t s_end = s_begin + a.span_per_split;
-  if (s_end > n_str) s_end = n_str;
-  f32x16 gacc[4];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) gacc[kb][r] = 0.0f;
-  X3Stage stg;
-  float stg0 = 0.0f, stg1 = 0.0f, stg2 = 0.0f;
-  int stg_k1 = 0, stg_k2 = 0;
-  auto gload = [&](int64_t s0) {
-    const int64_t sidx = s0 + (tid >> 3);
-    stg.load(x.shi, x.slo, sidx, sidx < s_end, tid);
-    if (tid < kTile) {
-      const int64_t ss = s0 + tid;
-      const bool ok = ss < s_end;
-      if (ROW_OWNED) {
-        stg0 = (ok && a.bias) ? a.bias[ss] : 0.0f;
-        stg_k1 = (ok && a.k1b) ? a.k1b[ss] : 0;
-        stg_k2 = (ok && a.k2b) ? a.k2b[ss] : 0;
-      } else {
-        stg0 = ok ? a.lse[ss] : 0.0f;
-        stg1 = ok ? a.row_valid[ss] * g_scale : 0.0f;
-        stg2 = (ok && a.inv_cnt) ? a.inv_cnt[ss] : 0.0f;
-        stg_k1 = (ok && a.k1a) ? a.k1a[ss] : 0;
-        stg_k2 = (ok && a.k2a) ? a.k2a[ss] : 0;
-      }
-    }
-  };
-  auto lstore = [&](int buf) {
-    stg.store(sT[buf], tid);
-    if (tid < kTile) {
-      sM0[buf][tid] = stg0;
-      sM1[buf][tid] = stg1;
-      sM2[buf][tid] = stg2;
-      sK1[buf][tid] = stg_k1;
-      sK2[buf][tid] = stg_k2;
-    }
-  };
-  if (s_begin < s_end) {
-    gload(s_begin);
-    lstore(0);
-    __syncthreads();
-    int cur = 0;
-    for (int64_t s0 = s_begin; s0 < s_end; s0 += kTile) {
-      const bool has_next = s0 + kTile < s_end;
-      if (has_next) gload(s0 + kTile);
-      f32x16 acc = dots_x3(sT[cur], c, h, uh, ul);
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const int rbase = 8 * q4 + 4 * h;
-        const float4 m04 = *reinterpret_cast<const float4*>(&sM0[cur][rbase]);
-        const float4 m14 = *reinterpret_cast<const float4*>(&sM1[cur][rbase]);
-        const float4 m24 = *reinterpret_cast<const float4*>(&sM2[cur][rbase]);
-        const int4 k14 = *reinterpret_cast<const int4*>(&sK1[cur][rbase]);
-        const int4 k24 = *reinterpret_cast<const int4*>(&sK2[cur][rbase]);
-        const float mm0[4] = {m04.x, m04.y, m04.z, m04.w};
-        const float mm1[4] = {m14.x, m14.y, m14.z, m14.w};
-        const float mm2[4] = {m24.x, m24.y, m24.z, m24.w};
-        const int kk1[4] = {k14.x, k14.y, k14.z, k14.w};
-        const int kk2[4] = {k24.x, k24.y, k24.z, k24.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = 4 * q4 + e;
-          const int64_t sidx = s0 + rbase + e;
-          int64_t ii, jj;
-          float lse_i, w_i, icnt_i, bias_j;
-          int k1_i, k1_j, k2_i, k2_j;
-          if (ROW_OWNED) {
-            ii = o; jj = sidx;
-            lse_i = o_lse; w_i = o_w; icnt_i = o_icnt; bias_j = mm0[e];
-            k1_i = o_k1; k1_j = kk1[e]; k2_i = o_k2; k2_j = kk2[e];
-          } else {
-            ii = sidx; jj = o;
-            lse_i = mm0[e]; w_i = mm1[e]; icnt_i = mm2[e]; bias_j = o_bias;
-            k1_i = kk1[e]; k1_j = o_k1; k2_i = kk2[e]; k2_j = o_k2;
-          }
-          const float sv = acc[r] * a.inv_tau - bias_j;
-          bool excl = (sidx >= s_end) || !own_ok;
-          const bool offdiag = (jj != ii + a.diag_off);
-          if (FL & F_EXCL_DIAG) excl = excl || !offdiag;
-          if (FL & F_MASK_K1) excl = excl || (offdiag && k1_i == k1_j);
-          if (FL & F_MASK_K2) excl = excl || (offdiag && k2_i == k2_j);
-          float y = 0.0f;
-          if (FL & F_POS) {
-            if (!excl && offdiag && k1_i == k1_j && k1_i != 0) y = icnt_i;
-          } else {
-            y = offdiag ? 0.0f : 1.0f;
-          }
-          const float p = (excl || lse_i == -INFINITY) ? 0.0f : __expf(sv - lse_i);
-          acc[r] = excl ? 0.0f : w_i * (p - y);
-        }
-      }
-      bf16x8 gh[2], gl[2];
-      split_tile(acc, gh, gl);
-      grad_x3s(gacc, gh, gl, sT[cur], lane);
-      if (has_next) lstore(cur ^ 1);  // cur^1: read in the previous tile, fenced by its barrier
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
-  float* dst = a.dout + (int64_t)split * n_own * kD;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int64_t orow = own_base + tile_row(r, h);
-    if (orow < n_own) {
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb) dst[orow * kD + kb * 32 + c] = gacc[kb][r];
-    }
-  }
 }
 
 // ---- host side: the forward entry points' checks on their operands
@@ -813,7 +433,6 @@ int plain_fwd(const float* A, const float* B, const float* bias, const int* k1a,
               const int* k2b, int64_t N, int64_t M, int64_t lda, int64_t ldb, int64_t diag_offset, float tau,
               int flags, const StatsLayout& L, const Images* im, float* ws, float* out2, hipStream_t st) {
   if (N == 0) return zero_sums(out2, st);
-  const X3Args x = {im ? im->bhi : nullptr, im ? im->blo : nullptr};
   if (im) {
     launch_split(B, ldb, M, im->bhi, im->blo, false, st);
     RSX_LAUNCHED();
@@ -827,11 +446,13 @@ int plain_fwd(const float* A, const float* B, const float* bias, const int* k1a,
   fa.nsplit = L.nf;
   fa.cols_per_split = split_span(M, L.nf);
   fa.part = ws + L.part;
+  fa.shi = im ? im->bhi : nullptr;
+  fa.slo = im ? im->blo : nullptr;
   const int blocks = (int)(((N + kOwnRows - 1) / kOwnRows) * L.nf);
   with_flags(flags, [&](auto fl) {
     constexpr int FL = decltype(fl)::value;
-    if (im) hipLaunchKernelGGL(nce_fwd_x3_k<FL>, dim3(blocks), dim3(256), 0, st, fa, x);
-    else hipLaunchKernelGGL(nce_fwd_k<FL>, dim3(blocks), dim3(256), 0, st, fa);
+    if (im) hipLaunchKernelGGL((nce_fwd_k<FL, X3Prod>), dim3(blocks), dim3(256), 0, st, fa);
+    else hipLaunchKernelGGL((nce_fwd_k<FL, F32Prod>), dim3(blocks), dim3(256), 0, st, fa);
   });
   RSX_LAUNCHED();
   MergeArgs ma;
@@ -878,8 +499,8 @@ int plain_bwd(const float* A, const float* B, const float* bias, const int* k1a,
     RSX_ARG((int64_t)ps * n_own * kD <= dpart_cap, "split partials exceed their workspace region");
     ba.nsplit = ps;
     ba.span_per_split = split_span(n_str, ps);
-    X3Args x = {nullptr, nullptr};
-    if (im) x = row_owned ? X3Args{im->bhi, im->blo} : X3Args{im->ahi, im->alo};
+    ba.shi = !im ? nullptr : row_owned ? im->bhi : im->ahi;
+    ba.slo = !im ? nullptr : row_owned ? im->blo : im->alo;
     if (im && !row_owned) {
       launch_split(A, lda, N, im->ahi, im->alo, false, st);
       RSX_LAUNCHED();
@@ -887,10 +508,10 @@ int plain_bwd(const float* A, const float* B, const float* bias, const int* k1a,
     const int blocks = (int)(((n_own + kOwnRows - 1) / kOwnRows) * ps);
     with_flags(flags, [&](auto fl) {
       constexpr int FL = decltype(fl)::value;
-      if (im && row_owned) hipLaunchKernelGGL((nce_bwd_x3_k<FL, true>), dim3(blocks), dim3(256), 0, st, ba, x);
-      else if (im) hipLaunchKernelGGL((nce_bwd_x3_k<FL, false>), dim3(blocks), dim3(256), 0, st, ba, x);
-      else if (row_owned) hipLaunchKernelGGL((nce_bwd_k<FL, true>), dim3(blocks), dim3(256), 0, st, ba);
-      else hipLaunchKernelGGL((nce_bwd_k<FL, false>), dim3(blocks), dim3(256), 0, st, ba);
+      if (im && row_owned) hipLaunchKernelGGL((nce_bwd_k<FL, true, X3Prod>), dim3(blocks), dim3(256), 0, st, ba);
+      else if (im) hipLaunchKernelGGL((nce_bwd_k<FL, false, X3Prod>), dim3(blocks), dim3(256), 0, st, ba);
+      else if (row_owned) hipLaunchKernelGGL((nce_bwd_k<FL, true, F32Prod>), dim3(blocks), dim3(256), 0, st, ba);
+      else hipLaunchKernelGGL((nce_bwd_k<FL, false, F32Prod>), dim3(blocks), dim3(256), 0, st, ba);
     });
     RSX_LAUNCHED();
     launch_sum_splits(ba.dout, ps, n_own, target, accumulate, st);
@@ -917,8 +538,8 @@ void rsx::nce::launch_split(const float* src, int64_t ld, int64_t rows, __bf16* 
   const int64_t n = rows * (kD / 8);
   if (n <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256));
-  if (half) hipLaunchKernelGGL(nce_split_h_k, grid, dim3(256), 0, st, src, ld, rows, hi, lo);
-  else hipLaunchKernelGGL(nce_split_k, grid, dim3(256), 0, st, src, ld, rows, hi, lo);
+  if (half) hipLaunchKernelGGL(nce_split_k<true>, grid, dim3(256), 0, st, src, ld, rows, hi, lo);
+  else hipLaunchKernelGGL(nce_split_k<false>, grid, dim3(256), 0, st, src, ld, rows, hi, lo);
 }
 
 RSX_API int64_t rsx_nce_workspace_floats(int64_t N, int64_t M, int nsplit_fwd, int nsplit_bwd) {

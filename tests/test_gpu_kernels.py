@@ -481,6 +481,39 @@ def test_nce_diag_offset_shards(gpu, flags):
         assert c.item() == valid.sum().item()
 
 
+@pytest.mark.parametrize("flags", [0, 2, 6, 9])
+def test_nce_rectangular_shard_backward(gpu, nce_precision, flags):
+    """Both gradients of a rectangular shard: rows [130, 207) (a partial owner block) against
+    M = 300 columns (a partial last tile) with diag_offset=130, A and B independent leaves, vs
+    float64. The row pass owns A and streams B, the column pass the reverse, so a role mix-up in
+    either shows in dA or dB. Bounds of test_nce_forward_backward at n = 77."""
+    lo, hi, m, tau = 130, 207, 300, 0.1
+    n = hi - lo
+    g = torch.Generator().manual_seed(900 + flags)
+    B = F.normalize(torch.randn(m, 128, generator=g), dim=1)
+    A = B[lo:hi].clone() if flags == 9 else F.normalize(torch.randn(n, 128, generator=g), dim=1)
+    bias = torch.log_softmax(torch.randn(m, generator=g), 0) if flags in (2, 6) else None
+    k1 = torch.randint(0, 40, (m,), generator=g)
+    k1[lo + 5] = k1[hi - 1] = 0  # key 0 inside the shard whatever the draw: SupCon rows without positives
+    k2 = torch.randint(0, 15, (m,), generator=g)
+    A64, B64 = A.double().requires_grad_(), B.double().requires_grad_()
+    ref, valid = _nce_rows_ref(A64, B64, None if bias is None else bias.double(), k1[lo:hi], k1, k2[lo:hi], k2, tau,
+                               flags, lo)
+    assert (flags == 9) == (valid.sum().item() < n)
+    ref_mean = ref.sum() / valid.sum().clamp(min=1)
+    ref_mean.backward()
+    dev = lambda t: None if t is None else t.to(gpu)
+    Ad, Bd = A.to(gpu).requires_grad_(), B.to(gpu).requires_grad_()
+    s, cnt = ops.nce_sum(Ad, Bd, dev(bias), dev(k1[lo:hi]), dev(k1), dev(k2[lo:hi]), dev(k2), tau=tau, flags=flags,
+                         diag_offset=lo)
+    assert cnt.item() == valid.sum().item()
+    loss = s / cnt.clamp(min=1.0)
+    assert abs(loss.item() - ref_mean.item()) < 1e-4, (loss.item(), ref_mean.item())
+    loss.backward()
+    torch.testing.assert_close(Ad.grad.cpu().double(), A64.grad, atol=2e-6, rtol=1e-4)
+    torch.testing.assert_close(Bd.grad.cpu().double(), B64.grad, atol=2e-6, rtol=1e-4)
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16x3"])
 @pytest.mark.parametrize("n_users,max_len,n_items,seed", [(40, 30, 25, 0), (300, 50, 400, 1), (7, 3, 5, 2)])
 def test_nce_grouped_equals_plain(gpu, n_users, max_len, n_items, seed, precision):
