@@ -40,6 +40,8 @@ const char* rsx_build_hash(void);
  * over T tokens: dense [B, L] (tok_pos NULL => position = token % L) or any packed token
  * list with tok_pos[T] (int64) giving each token's position (L <= 64).
  * base      [T, D] = item_proj output (nullable => 0)
+ * base_idx  int64 [T] (nullable): token t reads base[base_idx[t]] instead of base[t] (base then
+ *           holds one row per distinct item); the backward's dbase stays per token [T, D]
  * ids/tables: ntab (<=6) device pointers, ids int64 [T], tables [rows_j, D]
  * gate      [ntab] device (s_g = sigmoid(seq_gate) * s_mask); a gate that is exactly 0
  *           skips its gather (forward-exact) and reports a zero gate/table gradient
@@ -47,10 +49,10 @@ const char* rsx_build_hash(void);
  * pos [L, D], ln_w/ln_b [D] (ln_w == NULL => no LayerNorm: out = pre-LN sum, bit-exact
  * with the reference's op order), mean/rstd [T] saved for the backward.
  * D in {64, 128, 256}. Dropout p in [0,1) via counter hash (seed). */
-int rsx_seq_embed_fwd(const float* base, const int64_t* const* ids, const float* const* tables, int ntab,
-                      const float* gate, const float* pos, const int64_t* tok_pos, const float* ln_w,
-                      const float* ln_b, float eps, int64_t T, int64_t L, int64_t D, float p_drop, uint64_t seed,
-                      float* out, float* mean, float* rstd, void* stream);
+int rsx_seq_embed_fwd(const float* base, const int64_t* base_idx, const int64_t* const* ids,
+                      const float* const* tables, int ntab, const float* gate, const float* pos,
+                      const int64_t* tok_pos, const float* ln_w, const float* ln_b, float eps, int64_t T, int64_t L,
+                      int64_t D, float p_drop, uint64_t seed, float* out, float* mean, float* rstd, void* stream);
 
 /* Backward of rsx_seq_embed_fwd. dbase [T,D] written; dtables[j], dgate [ntab], dpos [L,D],
  * dln_w/dln_b [D] accumulated (nullable). padding_idx[j]: rows excluded from the table
@@ -60,8 +62,8 @@ int rsx_seq_embed_fwd(const float* base, const int64_t* const* ids, const float*
  * are stored per workgroup and folded in block order by a second kernel (deterministic);
  * workspace NULL flushes them with global float atomics (last bits vary run to run). */
 int64_t rsx_seq_embed_bwd_workspace_floats(int64_t T, int64_t L, int64_t D);
-int rsx_seq_embed_bwd(const float* base, const int64_t* const* ids, const float* const* tables,
-                      const int64_t* table_rows, const int64_t* padding_idx, int ntab, const float* gate,
+int rsx_seq_embed_bwd(const float* base, const int64_t* base_idx, const int64_t* const* ids,
+                      const float* const* tables, const int64_t* table_rows, const int64_t* padding_idx, int ntab, const float* gate,
                       const float* pos, const int64_t* tok_pos, const float* ln_w, const float* mean,
                       const float* rstd, float eps, int64_t T, int64_t L, int64_t D, float p_drop, uint64_t seed,
                       const float* dout, float* dbase, float* const* dtables, float* dgate, float* dpos,
@@ -391,16 +393,18 @@ int rsx_ids_check(const int64_t* ids, int64_t n, int64_t lo, int64_t hi, int64_t
  *      view), N (loss rows), D (distinct target columns over tglob), E (distinct (user, target)
  *      pairs), U (distinct item ids among the tokens), C (segment-sum chunks), error flag (ids
  *      out of range), 0, then every rank's row count
- *   4. rsx_step_index_fill(sizes = totals[0..5] read on the host) writes out[0..32]:
+ *   4. rsx_step_index_fill(sizes = totals[0..5] read on the host) writes out[0..33]:
  *      0 flat [T] i64, 1 tok_user [T] i64, 2 tok_pos [T] i64, 3 tok_pad [T] u8, 4 seg_off [B+1] i32,
  *      5 seg_off [B+1] i64, 6 valid_tok [N] i64, 7 last_tok [B] i64; the doubled two-view batch:
  *      8 flat [2T], 9 tok_user [2T], 10 tok_pos [2T] i64, 11 tok_pad [2T] u8, 12 seg_off [2B+1]
  *      i32, 13 seg_off [2B+1] i64, 14 tok_ids [6][2T] i64 (seq_ids per token, both views),
- *      15 pretrained rows [2T][128] f32 (nullable; from lookup [n_items][ld_lookup]); the
+ *      15 pretrained rows of the distinct items [U][128] f32 in the order of 20 (nullable; from
+ *      lookup [n_items][ld_lookup]; token t of either view owns row 33[t]); the
  *      item-id segment-sum plan: 16 perm [2T], 17 cb [C+1], 18 chunk ids [C], 19 ch_off [U+1],
  *      20 ids [U] (all i64); the grouped-loss index: 21 uniq [D] i64, 22 colcnt [D] f32,
  *      23 row_col, 24 row_beg, 25 row_end, 26 exc_cols [N] i32, 27 exc_s, 28 exc_e, 29 exc_n [E]
- *      i32, 30 col_beg, 31 col_end [D] i32; 32 last_t [B] i32 (the SupCon keys: last targets).
+ *      i32, 30 col_beg, 31 col_end [D] i32; 32 last_t [B] i32 (the SupCon keys: last targets);
+ *      33 tok_uidx [2T] i64 (each token's slot in 20, the same for both views).
  * ws: rsx_step_index_workspace_bytes(B, L, n_items), the same buffer for all three calls. */
 int64_t rsx_step_index_workspace_bytes(int64_t B, int64_t L, int64_t n_items);
 int rsx_step_index_count(const uint8_t* pm, const int64_t* tgt, const int64_t* item, int64_t B, int64_t L,
@@ -670,6 +674,12 @@ int rsx_scatter_rows(const float* dy, const float* y, const float* nrm, const in
 int rsx_segment_sum_rows(const float* src, int64_t ld_src, const int64_t* perm, const int64_t* seg_off,
                          const int64_t* rows, int64_t nseg, int64_t D, const float* scale, int64_t skip_row,
                          float* dst, int64_t ld_dst, int accumulate, void* stream);
+/* The same, and from the same pass raw[u] = the unscaled sum of segment u, dense [nseg, D], for every
+ * segment (rows[u] == skip_row included): the item-id plan's per-item sums feed both the gated table
+ * gradient (dst) and item_proj's weight gradient over the distinct items (raw). */
+int rsx_segment_sum_rows2(const float* src, int64_t ld_src, const int64_t* perm, const int64_t* seg_off,
+                          const int64_t* rows, int64_t nseg, int64_t D, const float* scale, int64_t skip_row,
+                          float* dst, int64_t ld_dst, int accumulate, float* raw, int64_t ld_raw, void* stream);
 
 /* The contrastive step's objective from its device loss sums, one launch instead of the
  * scalar tensor ops of train_user_tower_all_time (tower_code/v1_usertower_train.py:814-845):
@@ -760,7 +770,14 @@ int64_t rsx_hnm_max_rows(void);
  *           graphic, section), token positions int64 [T], key-pad flags uint8 [T], user token
  *           offsets int32 / int64 [U+1], token user int64 [T], seq gate [6] (sigmoid(seq_gate)
  *           * s_mask), profile rows [U,128], the item-id gradient plan (perm [T], chunk bounds
- *           [C+1], chunk ids [C], chunk offsets per id [Uq+1], ids [Uq]; ops.sort_segments)
+ *           [C+1], chunk ids [C], chunk offsets per id [Uq+1], ids [Uq]; ops.sort_segments),
+ *           the tokens' distinct-item slots int64 [T] (RSX_TW_UIDX, nullable). With the slots
+ *           (and C > 0) the pretrained rows are [Uq,128], one per distinct item in the plan's id
+ *           order: item_proj runs over those Uq rows, the embedding stage reads row slot[t] of
+ *           its output for token t, and item_proj's weight / bias gradient comes from the
+ *           per-item sums of the embedding stage's per-token input gradient (the plan's segment
+ *           sums, ungated) against the same Uq rows; the pretrained rows' gradient must then be
+ *           null. Without the slots: one pretrained row per token.
  *   params  item_proj w/b, the six tables, pos_emb, emb_ln w/b; per layer norm1 w/b,
  *           in_proj w/b, out_proj w/b, norm2 w/b, linear1 w/b, linear2 w/b; output_proj[0] w/b,
  *           output_proj[1] w/b, output_proj[3] w/b
@@ -774,19 +791,21 @@ int64_t rsx_hnm_max_rows(void);
  * fargs[] p_drop, emb_ln eps, per layer norm1 eps, norm2 eps, output LayerNorm eps
  * seeds[] 1 + 4 x layers dropout seeds: embedding, then per layer attention, out-projection
  *         add, feed-forward, closing add (the per-op entry points' seed order)
- * arena   saved activations (rsx_tower_arena_bytes), read by the backward; out [T or R,128] (the
- *         backward reads it too: the F.normalize backward).
+ * arena   saved activations (rsx_tower_arena_bytes; pv_rows = the pretrained rows given: T, or Uq
+ *         with the slots), read by the backward; out [T or R,128] (the backward reads it too: the
+ *         F.normalize backward).
  * grads[] parallel to p[]: params' gradients written, except the embedding stage's (six
  *         tables, pos_emb, emb_ln w/b) and the seq gate's, which are ACCUMULATED (caller
  *         zeroes); the profile's [U,128] written; the pretrained rows' nullable (written).
- * ws      backward scratch (rsx_tower_bwd_workspace_bytes). */
+ * ws      backward scratch (rsx_tower_bwd_workspace_bytes); it includes a [C,128] buffer for the
+ *         per-item sums of the embedding stage's input gradient (Uq <= C rows used, slots form). */
 enum {
   RSX_TW_PV = 0, RSX_TW_IDS = 1, RSX_TW_TOK_POS = 7, RSX_TW_TOK_PAD = 8, RSX_TW_SEG32 = 9, RSX_TW_SEG64 = 10,
-  RSX_TW_TOK_USER = 11, RSX_TW_GATE = 12, RSX_TW_PROFILE = 13, RSX_TW_ITEMSEG = 14, RSX_TW_ITEM_PROJ = 19,
-  RSX_TW_TABLES = 21, RSX_TW_POS = 27, RSX_TW_EMB_LN = 28, RSX_TW_LAYER0 = 30
+  RSX_TW_TOK_USER = 11, RSX_TW_GATE = 12, RSX_TW_PROFILE = 13, RSX_TW_ITEMSEG = 14, RSX_TW_UIDX = 19,
+  RSX_TW_ITEM_PROJ = 20, RSX_TW_TABLES = 22, RSX_TW_POS = 28, RSX_TW_EMB_LN = 29, RSX_TW_LAYER0 = 31
 };
 int64_t rsx_tower_n_ptrs(int layers);
-int64_t rsx_tower_arena_bytes(int64_t T, int64_t U, int layers);
+int64_t rsx_tower_arena_bytes(int64_t T, int64_t U, int layers, int64_t pv_rows);
 int64_t rsx_tower_bwd_workspace_bytes(int64_t T, int64_t U, int64_t L, int layers, int64_t C);
 int rsx_tower_fwd(const void* const* p, const int64_t* dims, const float* fargs, const uint64_t* seeds, void* arena,
                   int64_t arena_bytes, float* out, void* stream);

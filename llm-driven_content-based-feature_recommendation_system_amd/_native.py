@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 9  # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 10  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -33,10 +33,10 @@ _SIGS = {
     "rsx_abi_version": (c_i, []),
     "rsx_target_arch": (ctypes.c_char_p, []),
     "rsx_build_hash": (ctypes.c_char_p, []),
-    "rsx_seq_embed_fwd": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i64, c_i64, c_f, c_u64,
+    "rsx_seq_embed_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i64, c_i64, c_f, c_u64,
                                 c_p, c_p, c_p, c_p]),
     "rsx_seq_embed_bwd_workspace_floats": (c_i64, [c_i64, c_i64, c_i64]),
-    "rsx_seq_embed_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i64,
+    "rsx_seq_embed_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_i64, c_i64,
                                 c_i64, c_f, c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
     "rsx_mha_fwd": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i, c_f, c_u64, c_p, c_p, c_p]),
     "rsx_mha_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i, c_f, c_u64, c_p, c_p]),
@@ -118,7 +118,7 @@ _SIGS = {
     "rsx_clip_adamw": (c_i, [c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_i64,
                              c_p, c_p]),
     "rsx_tower_n_ptrs": (c_i64, [c_i]),
-    "rsx_tower_arena_bytes": (c_i64, [c_i64, c_i64, c_i]),
+    "rsx_tower_arena_bytes": (c_i64, [c_i64, c_i64, c_i, c_i64]),
     "rsx_tower_bwd_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64, c_i, c_i64]),
     "rsx_tower_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
     "rsx_tower_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
@@ -147,6 +147,8 @@ _SIGS = {
     "rsx_dcn_train_head": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p,
                                  c_p]),
     "rsx_segment_sum_rows": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p]),
+    "rsx_segment_sum_rows2": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_p, c_i64,
+                                    c_p]),
     "rsx_scatter_rows": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_f, c_i, c_i64, c_p, c_i64, c_p]),
     "rsx_hnm_mine": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_f, c_f, c_p, ctypes.c_size_t, c_p, c_p, c_p, c_p]),
     "rsx_hnm_workspace_bytes": (c_i64, [c_i64]),

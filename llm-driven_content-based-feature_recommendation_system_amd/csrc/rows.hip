@@ -122,13 +122,16 @@ unsigned grid_for(int64_t n, int D) {
 // destination row is known (the embedding-table gradient of the user tower's item ids, whose
 // Zipf-hot rows made the atomic form contend): one row group of lanes per segment, summed in
 // segment order. rows[u] == skip (padding_idx) is left untouched; scale: device scalar.
-template <int D>
+// RAW: the same sums also stored unscaled and dense, raw[u] for every segment (the skipped one
+// included): a second consumer of the sums without a second pass over src.
+template <int D, bool RAW = false>
 __global__ __launch_bounds__(256) void segsum_rows_k(const float* __restrict__ src, int64_t ld_src,
                                                     const int64_t* __restrict__ perm,
                                                     const int64_t* __restrict__ seg,
                                                     const int64_t* __restrict__ rows, int64_t nseg,
                                                     const float* __restrict__ scale, int64_t skip,
-                                                    float* __restrict__ dst, int64_t ld_dst, int accumulate) {
+                                                    float* __restrict__ dst, int64_t ld_dst, int accumulate,
+                                                    float* __restrict__ raw = nullptr, int64_t ld_raw = 0) {
   constexpr int LPR = RowGeo<D>::LPR, RPW = RowGeo<D>::RPW;
   const int lane = threadIdx.x & 63, sub = lane / LPR, c = lane % LPR;
   const int64_t wave_g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void segsum_rows_k(const float* __restrict__ s
     const int64_t u = u0 + sub;
     if (u >= nseg) continue;
     const int64_t row = rows ? rows[u] : u;
-    if (row == skip) continue;
+    if (!RAW && row == skip) continue;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     const int64_t k1 = seg[u + 1];
     int64_t k = seg[u];
@@ -168,6 +171,10 @@ __global__ __launch_bounds__(256) void segsum_rows_k(const float* __restrict__ s
 #pragma unroll
       for (int i = 0; i < 15; ++i)
         if (i < n) { acc.x += x[i].x; acc.y += x[i].y; acc.z += x[i].z; acc.w += x[i].w; }
+    }
+    if (RAW) {
+      reinterpret_cast<float4*>(raw + u * ld_raw)[c] = acc;
+      if (row == skip) continue;
     }
     float4* d = reinterpret_cast<float4*>(dst + row * ld_dst) + c;
     float4 v = make_float4(sc * acc.x, sc * acc.y, sc * acc.z, sc * acc.w);
@@ -298,7 +305,30 @@ RSX_API int rsx_segment_sum_rows(const float* src, int64_t ld_src, const int64_t
 #define RSX_SS(DD)                                                                                            \
   if (D == DD)                                                                                                \
     hipLaunchKernelGGL(segsum_rows_k<DD>, dim3(g), dim3(256), 0, st, src, ld_src, perm, seg_off, rows, nseg, \
-                       scale, skip_row, dst, ld_dst, accumulate);
+                       scale, skip_row, dst, ld_dst, accumulate, (float*)nullptr, (int64_t)0);
+  RSX_SS(64) RSX_SS(128) RSX_SS(256)
+#undef RSX_SS
+  RSX_LAUNCHED();
+  return 0;
+}
+
+// rsx_segment_sum_rows that also stores the unscaled sums densely: raw[u] = the sum of segment u,
+// for every u (rows[u] == skip_row included), from the same pass (segsum_rows_k<D, true>).
+RSX_API int rsx_segment_sum_rows2(const float* src, int64_t ld_src, const int64_t* perm, const int64_t* seg_off,
+                                  const int64_t* rows, int64_t nseg, int64_t D, const float* scale, int64_t skip_row,
+                                  float* dst, int64_t ld_dst, int accumulate, float* raw, int64_t ld_raw,
+                                  void* stream) {
+  RSX_ARG(src && seg_off && dst && raw, "null tensor");
+  RSX_ARG(D == 64 || D == 128 || D == 256, "D must be 64, 128 or 256");
+  RSX_ARG(ld_src >= D && ld_dst >= D && ld_raw >= D && ld_src % 4 == 0 && ld_dst % 4 == 0 && ld_raw % 4 == 0,
+          "bad leading dimensions");
+  if (nseg == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned g = grid_for(nseg, (int)D);
+#define RSX_SS(DD)                                                                                                  \
+  if (D == DD)                                                                                                      \
+    hipLaunchKernelGGL((segsum_rows_k<DD, true>), dim3(g), dim3(256), 0, st, src, ld_src, perm, seg_off, rows, nseg, \
+                       scale, skip_row, dst, ld_dst, accumulate, raw, ld_raw);
   RSX_SS(64) RSX_SS(128) RSX_SS(256)
 #undef RSX_SS
   RSX_LAUNCHED();

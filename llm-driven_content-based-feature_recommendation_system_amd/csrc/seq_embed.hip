@@ -18,6 +18,7 @@ constexpr int kMaxTab = 6;
 
 struct FwdArgs {
   const float* base;
+  const int64_t* base_idx;  // [T] row of base read by each token, nullptr => the token's own row
   const int64_t* ids[kMaxTab];
   const float* tab[kMaxTab];
   const float* gate;  // [ntab] on device, nullptr => 1.0
@@ -101,7 +102,7 @@ __device__ __forceinline__ float4 f4_add_rn(float4 x, float4 p) {
 template <int D>
 __device__ __forceinline__ float4 build_row(const FwdArgs& a, int64_t r, int c, const float* g) {
   float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (a.base) x = ldg4(a.base + r * D + 4 * c);
+  if (a.base) x = ldg4(a.base + (a.base_idx ? ldg8(a.base_idx + r) : r) * D + 4 * c);
 #pragma unroll
   for (int j = 0; j < kMaxTab; ++j) {
     if (j < a.ntab && g[j] != 0.0f) {
@@ -163,19 +164,23 @@ __device__ __forceinline__ void ln_drop_store(const FwdArgs& a, float4 x, int64_
 // with every operand's presence known at compile time. With the presence tests as run-time branches
 // hipcc closed each of their blocks with a vmcnt(0), so the id -> row chains of one iteration ran
 // one after another instead of all in flight (same loads, same op order, same results).
-template <int D, int U, int NL, bool FULL = false>
+// BI (FULL only): the base row comes through base_idx, one more id -> row chain per group, its index
+// load issued with the table ids'; the other forms test base_idx at run time.
+template <int D, int U, int NL, bool FULL = false, bool BI = false>
 __device__ __forceinline__ void fwd_groups(const FwdArgs& a, const int64_t* const* ids_l, const float* const* tab_l,
                                            const float* g_l, int64_t r0, int sub, int c, float4 w, float4 bb,
                                            bool do_ln) {
   constexpr int RPW = 64 / (D / 4);
   const bool has_pos = FULL || a.pos, has_base = FULL || a.base;
-  int64_t rr[U];
+  int64_t rr[U], rb[U];
   int64_t id[U][NL > 0 ? NL : 1];
   int lp[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int64_t r = r0 + u * RPW + sub;
     rr[u] = r < a.T ? r : a.T - 1;  // clamped: out-of-range slots recompute the last row, store nothing
+    if (FULL) rb[u] = BI ? ldg8(a.base_idx + rr[u]) : rr[u];
+    else rb[u] = (a.base && a.base_idx) ? ldg8(a.base_idx + rr[u]) : rr[u];
 #pragma unroll
     for (int k = 0; k < NL; ++k) id[u][k] = ldg8(ids_l[k] + rr[u]);
     if (FULL) lp[u] = (int)ldg8(a.tok_pos + rr[u]);
@@ -184,7 +189,7 @@ __device__ __forceinline__ void fwd_groups(const FwdArgs& a, const int64_t* cons
   float4 x[U];
 #pragma unroll
   for (int u = 0; u < U; ++u)
-    x[u] = has_base ? ldg4(a.base + rr[u] * D + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    x[u] = has_base ? ldg4(a.base + rb[u] * D + 4 * c) : make_float4(0.f, 0.f, 0.f, 0.f);
   float4 e[U][NL > 0 ? NL : 1];
 #pragma unroll
   for (int k = 0; k < NL; ++k)
@@ -251,6 +256,11 @@ __global__ __launch_bounds__(256) void seq_embed_fwd_k(FwdArgs a) {
     return;
   }
   if (nl == 2 && a.base && a.pos && a.tok_pos && do_ln) {  // the packed tower's configuration
+    if (a.base_idx) {  // ... with the projected rows kept per distinct item
+      for (int64_t r0 = wave_g * (RPW * U); r0 < a.T; r0 += nwaves * (RPW * U))
+        fwd_groups<D, U, 2, true, true>(a, ids_l, tab_l, g_l, r0, sub, c, w, bb, true);
+      return;
+    }
     for (int64_t r0 = wave_g * (RPW * U); r0 < a.T; r0 += nwaves * (RPW * U))
       fwd_groups<D, U, 2, true>(a, ids_l, tab_l, g_l, r0, sub, c, w, bb, true);
     return;
@@ -317,13 +327,15 @@ __device__ __forceinline__ void bwd_groups(const BwdArgs& a, const BwdLive& lv, 
   const int c = cx.c;
   const bool need_e = cx.do_ln || a.dgate;
   const bool need_l = (f.pos && cx.do_ln) || a.dpos;
-  int64_t rc[U];
+  int64_t rc[U], rb[U];
   int lp[U];
   int64_t id[U][NS];
+  const bool base_ix = cx.do_ln && f.base && f.base_idx;  // the recompute reads base through base_idx
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int64_t ru = r00 + (u * NW + cx.wave) * RPW + cx.sub;
     rc[u] = ru < cx.r_end ? ru : cx.r_begin;  // out-of-range slots re-read a valid row, store nothing
+    rb[u] = base_ix ? ldg8(f.base_idx + rc[u]) : rc[u];
     lp[u] = need_l ? (f.tok_pos ? (int)f.tok_pos[rc[u]] : (int)(rc[u] % f.L)) : 0;
 #pragma unroll
     for (int k = 0; k < NS; ++k)
@@ -337,7 +349,7 @@ __device__ __forceinline__ void bwd_groups(const BwdArgs& a, const BwdLive& lv, 
     xv[u] = make_float4(0.f, 0.f, 0.f, 0.f);
     muv[u] = 0.0f; rsv[u] = 0.0f;
     if (cx.do_ln) {
-      if (f.base) xv[u] = ldg4(f.base + rc[u] * D + 4 * c);
+      if (f.base) xv[u] = ldg4(f.base + rb[u] * D + 4 * c);
       muv[u] = f.mean[rc[u]];
       rsv[u] = f.rstd[rc[u]];
     }
@@ -883,11 +895,13 @@ int small_layout(const int64_t* table_rows, int ntab, int64_t D, bool has_grad_j
   return o;
 }
 
-bool fill_fwd(FwdArgs& a, const float* base, const int64_t* const* ids, const float* const* tabs, int ntab,
-              const float* gate, const float* pos, const int64_t* tok_pos, const float* ln_w, const float* ln_b,
-              float eps, int64_t T, int64_t L, float* out, float* mean, float* rstd, float p_drop, uint64_t seed) {
+bool fill_fwd(FwdArgs& a, const float* base, const int64_t* base_idx, const int64_t* const* ids,
+              const float* const* tabs, int ntab, const float* gate, const float* pos, const int64_t* tok_pos,
+              const float* ln_w, const float* ln_b, float eps, int64_t T, int64_t L, float* out, float* mean,
+              float* rstd, float p_drop, uint64_t seed) {
   if (ntab < 0 || ntab > kMaxTab) return false;
   a.base = base;
+  a.base_idx = base ? base_idx : nullptr;
   for (int j = 0; j < kMaxTab; ++j) {
     a.ids[j] = (j < ntab) ? ids[j] : nullptr;
     a.tab[j] = (j < ntab) ? tabs[j] : nullptr;
@@ -958,10 +972,11 @@ RSX_API int rsx_gather_events_read(float* ms, int64_t* tokens, int max_n) {
   return n;
 }
 
-RSX_API int rsx_seq_embed_fwd(const float* base, const int64_t* const* ids, const float* const* tables, int ntab,
-                              const float* gate, const float* pos, const int64_t* tok_pos, const float* ln_w,
-                              const float* ln_b, float eps, int64_t T, int64_t L, int64_t D, float p_drop,
-                              uint64_t seed, float* out, float* mean, float* rstd, void* stream) {
+RSX_API int rsx_seq_embed_fwd(const float* base, const int64_t* base_idx, const int64_t* const* ids,
+                              const float* const* tables, int ntab, const float* gate, const float* pos,
+                              const int64_t* tok_pos, const float* ln_w, const float* ln_b, float eps, int64_t T,
+                              int64_t L, int64_t D, float p_drop, uint64_t seed, float* out, float* mean,
+                              float* rstd, void* stream) {
   RSX_ARG(out != nullptr, "out is null");
   RSX_ARG(T >= 0 && L > 0 && L <= 64, "need T >= 0 and 0 < L <= 64");
   RSX_ARG(D == 64 || D == 128 || D == 256, "D must be 64, 128 or 256");
@@ -971,7 +986,8 @@ RSX_API int rsx_seq_embed_fwd(const float* base, const int64_t* const* ids, cons
   for (int j = 0; j < ntab; ++j) RSX_ARG(ids[j] != nullptr && tables[j] != nullptr, "null table/ids");
   if (T == 0) return 0;
   FwdArgs a;
-  fill_fwd(a, base, ids, tables, ntab, gate, pos, tok_pos, ln_w, ln_b, eps, T, L, out, mean, rstd, p_drop, seed);
+  fill_fwd(a, base, base_idx, ids, tables, ntab, gate, pos, tok_pos, ln_w, ln_b, eps, T, L, out, mean, rstd, p_drop,
+           seed);
   hipStream_t st = (hipStream_t)stream;
   GatherEvents& ge = gather_events();
   std::pair<hipEvent_t, hipEvent_t> evp{nullptr, nullptr};
@@ -1006,8 +1022,8 @@ RSX_API int64_t rsx_seq_embed_bwd_workspace_floats(int64_t T, int64_t L, int64_t
   return blocks * (L * D + kSmallMax + 2 * D + kMaxTab) + kKeyBlocksMax * 64 * D;
 }
 
-RSX_API int rsx_seq_embed_bwd(const float* base, const int64_t* const* ids, const float* const* tables,
-                              const int64_t* table_rows, const int64_t* padding_idx, int ntab, const float* gate,
+RSX_API int rsx_seq_embed_bwd(const float* base, const int64_t* base_idx, const int64_t* const* ids,
+                              const float* const* tables, const int64_t* table_rows, const int64_t* padding_idx, int ntab, const float* gate,
                               const float* pos, const int64_t* tok_pos, const float* ln_w, const float* mean,
                               const float* rstd, float eps, int64_t T, int64_t L, int64_t D, float p_drop,
                               uint64_t seed, const float* dout, float* dbase, float* const* dtables, float* dgate,
@@ -1021,7 +1037,7 @@ RSX_API int rsx_seq_embed_bwd(const float* base, const int64_t* const* ids, cons
   RSX_ARG(L > 0 && L <= 64, "need 0 < L <= 64");
   if (T == 0) return 0;
   BwdArgs a;
-  fill_fwd(a.f, base, ids, tables, ntab, gate, pos, tok_pos, ln_w, nullptr, eps, T, L, nullptr,
+  fill_fwd(a.f, base, base_idx, ids, tables, ntab, gate, pos, tok_pos, ln_w, nullptr, eps, T, L, nullptr,
            const_cast<float*>(mean), const_cast<float*>(rstd), p_drop, seed);
   a.dout = dout;
   a.dbase = dbase;

@@ -23,7 +23,7 @@
 //   ids, loss rows and their column / user ranges, per-user sorted columns, pair keys), a stable
 //   radix sort of the view-1 tokens by item id and of the (user, target) pairs by column,
 //   si_itemseg_k (the two-view segmented-sum plan), si_cols_k, si_pairs_k, si_pv_k (pretrained
-//   rows of both views).
+//   rows of the distinct items; si_tokens_k writes each token's slot among them).
 #include "rsx_common.h"
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
@@ -271,13 +271,15 @@ struct FillOut {
   int64_t* tok_ids;  // [6][2T]
   int *row_col, *row_beg, *row_end, *exc_cols;
   int* last_t;  // int32: the SupCon kernel's key type (ids < n_items < 2^31)
+  int64_t* tok_uidx;  // [2T] slot of the token's item id among the distinct ids (nullable)
 };
 
 __global__ __launch_bounds__(256) void si_tokens_k(const uint8_t* pm, const int64_t* tgt, const int64_t* ids0,
                                                    const int64_t* ids1, const int64_t* ids2, const int64_t* ids3,
                                                    const int64_t* ids4, const int64_t* ids5, int64_t B, int L,
                                                    int64_t T, const int* offT, const int* offN, const int* offE,
-                                                   const int* srt, const int* colidx, FillOut f, unsigned* ikeys,
+                                                   const int* srt, const int* colidx, const int* itemidx, FillOut f,
+                                                   unsigned* ikeys,
                                                    int* ivals, unsigned* pkeys, int* pvals, int* pair_b, int* pair_n) {
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -308,6 +310,11 @@ __global__ __launch_bounds__(256) void si_tokens_k(const uint8_t* pm, const int6
       f.tok_ids[(2 * k + 1) * T + tok] = v;
     }
     ikeys[tok] = (unsigned)ids0[o];  // range-checked in phase A
+    if (f.tok_uidx) {  // the id's rank among the batch's distinct ids = its row in uniq_items
+      const int64_t ui = itemidx[ids0[o]];
+      f.tok_uidx[tok] = ui;
+      f.tok_uidx[T + tok] = ui;
+    }
     ivals[tok] = (int)tok;
     if (u.valid) {
       const int64_t r = offN[b] + below(u.vm, lane);
@@ -413,15 +420,13 @@ __global__ __launch_bounds__(256) void si_pairs_k(const int* spvals, int64_t E, 
   }
 }
 
-// pretrained rows of the view-1 tokens' item ids into both halves of [2T, 128]
-__global__ __launch_bounds__(256) void si_pv_k(const float* lookup, int64_t ld, const int64_t* ids_tok, int64_t T,
+// pretrained rows of the U distinct item ids (uniq_items' order) into [U, 128]: one row per item
+// instead of one per token of each view (the tower projects them once per item)
+__global__ __launch_bounds__(256) void si_pv_k(const float* lookup, int64_t ld, const int64_t* uniq_items, int64_t U,
                                                float* pv) {
   const int lane = threadIdx.x & 31;
-  for (int64_t t = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5; t < T; t += ((int64_t)gridDim.x * 256) >> 5) {
-    const float4 v = reinterpret_cast<const float4*>(lookup + ids_tok[t] * ld)[lane];
-    reinterpret_cast<float4*>(pv + t * 128)[lane] = v;
-    reinterpret_cast<float4*>(pv + (T + t) * 128)[lane] = v;
-  }
+  for (int64_t u = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 5; u < U; u += ((int64_t)gridDim.x * 256) >> 5)
+    reinterpret_cast<float4*>(pv + u * 128)[lane] = reinterpret_cast<const float4*>(lookup + uniq_items[u] * ld)[lane];
 }
 
 int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
@@ -587,10 +592,12 @@ RSX_API int rsx_step_index_fill(const uint8_t* pm, const int64_t* tgt, const int
   f.seg2 = (int*)out[12]; f.seg2_64 = (int64_t*)out[13]; f.tok_ids = (int64_t*)out[14];
   f.row_col = (int*)out[23]; f.row_beg = (int*)out[24]; f.row_end = (int*)out[25]; f.exc_cols = (int*)out[26];
   f.last_t = (int*)out[32];
+  f.tok_uidx = (int64_t*)out[33];
   const unsigned gu = (unsigned)((B + 3) / 4);
   hipLaunchKernelGGL(si_tokens_k, dim3(gu), dim3(256), 0, st, pm, tgt, seq_ids[0], seq_ids[1], seq_ids[2],
                      seq_ids[3], seq_ids[4], seq_ids[5], B, (int)L, T, at<int>(ws, l.offT), at<int>(ws, l.offN),
-                     at<int>(ws, l.offE), at<int>(ws, l.srt), at<int>(ws, l.colidx), f, at<unsigned>(ws, l.ikeys),
+                     at<int>(ws, l.offE), at<int>(ws, l.srt), at<int>(ws, l.colidx), at<int>(ws, l.itemidx), f,
+                     at<unsigned>(ws, l.ikeys),
                      at<int>(ws, l.ivals), at<unsigned>(ws, l.pkeys), at<int>(ws, l.pvals), at<int>(ws, l.pair_b),
                      at<int>(ws, l.pair_n));
   RSX_LAUNCHED();
@@ -625,8 +632,8 @@ RSX_API int rsx_step_index_fill(const uint8_t* pm, const int64_t* tgt, const int
   }
   if (lookup && out[15]) {
     RSX_ARG(ld_lookup >= 128 && ld_lookup % 4 == 0, "pretrained lookup rows must be 128 floats (stride % 4 == 0)");
-    hipLaunchKernelGGL(si_pv_k, dim3(grid_for(T * 32)), dim3(256), 0, st, lookup, ld_lookup, f.tok_ids, T,
-                       (float*)out[15]);
+    hipLaunchKernelGGL(si_pv_k, dim3(grid_for(U * 32)), dim3(256), 0, st, lookup, ld_lookup,
+                       (const int64_t*)out[20], U, (float*)out[15]);
     RSX_LAUNCHED();
   }
   return 0;

@@ -38,11 +38,12 @@ struct Layout {  // float offsets into the arena
   int64_t prof, hp, g, mo, ro, o, nrm, aR, xR, tidx, tinv, tuser, tseg, lseq, total;
 };
 
-Layout layout(int64_t T, int64_t U, int nl) {
+// pv_rows: rows of item_proj's output (T, or the distinct items' Uq when the tokens read it by slot)
+Layout layout(int64_t T, int64_t U, int nl, int64_t pv_rows) {
   Layout s{};
   int64_t o = 0;
   auto take = [&](int64_t n) { const int64_t r = o; o += al(n); return r; };
-  s.base = take(T * kD); s.x0 = take(T * kD); s.m0 = take(T); s.r0 = take(T);
+  s.base = take(pv_rows * kD); s.x0 = take(T * kD); s.m0 = take(T); s.r0 = take(T);
   s.h0 = take(T * kD); s.mh0 = take(T); s.rh0 = take(T);
   for (int i = 0; i < nl; ++i) {
     LayerAct& a = s.l[i];
@@ -62,7 +63,8 @@ Layout layout(int64_t T, int64_t U, int nl) {
 }
 
 struct BwdLayout {  // float offsets into the workspace
-  int64_t dO, dG, dHp, dX, dXs, dH, dHs, dF, dPre, dRes, dA, dQKV, dProf, dBase, part, dAR, dXR, wsw, wsl, wse, total;
+  int64_t dO, dG, dHp, dX, dXs, dH, dHs, dF, dPre, dRes, dA, dQKV, dProf, dBase, part, dBaseU, dAR, dXR, wsw, wsl, wse,
+      total;
   int64_t n_wsw, n_wsl, n_wse;
 };
 
@@ -74,6 +76,7 @@ BwdLayout bwd_layout(int64_t T, int64_t U, int64_t L, int64_t C) {
   s.dH = take(T * kD); s.dHs = take(T * kD); s.dF = take(T * kD); s.dPre = take(T * kF); s.dRes = take(T * kD);
   s.dA = take(T * kD); s.dQKV = take(T * kQKV); s.dProf = take(U * kD); s.dBase = take(T * kD);
   s.part = take((C > 0 ? C : 1) * kD);
+  s.dBaseU = take((C > 0 ? C : 1) * kD);  // per-distinct-item sums of dBase: Uq <= C rows
   s.dAR = take((T + 1) * kD); s.dXR = take((T + 1) * kD);  // tail rows + one zero row (the expand's source)
   int64_t w = 0;
   const int64_t nk[5][3] = {{T, kD, kD}, {T, kQKV, kD}, {T, kD, kF}, {T, kF, kD}, {U, kD, kD}};
@@ -281,10 +284,15 @@ __global__ __launch_bounds__(256) void tw_lastq_bwd_k(LastQ a) {
 
 RSX_API int64_t rsx_tower_n_ptrs(int layers) { return n_ptrs(layers); }
 
-RSX_API int64_t rsx_tower_arena_bytes(int64_t T, int64_t U, int layers) {
-  if (layers < 1 || layers > kMaxLayers || T < 0 || U < 0) return -1;
-  return layout(T, U, layers).total * 4;
+RSX_API int64_t rsx_tower_arena_bytes(int64_t T, int64_t U, int layers, int64_t pv_rows) {
+  if (layers < 1 || layers > kMaxLayers || T < 0 || U < 0 || pv_rows < 0) return -1;
+  return layout(T, U, layers, pv_rows).total * 4;
 }
+
+namespace {
+// the pretrained rows are kept once per distinct item (p[RSX_TW_UIDX], see recsys_amd.h)
+bool per_item(const void* const* p, const int64_t* dims) { return p[RSX_TW_UIDX] != nullptr && dims[4] > 0; }
+}  // namespace
 
 RSX_API int64_t rsx_tower_bwd_workspace_bytes(int64_t T, int64_t U, int64_t L, int layers, int64_t C) {
   if (layers < 1 || layers > kMaxLayers || T < 0 || U < 0) return -1;
@@ -298,7 +306,10 @@ RSX_API int rsx_tower_fwd(const void* const* p, const int64_t* dims, const float
   const int nl = (int)dims[3];
   RSX_ARG(nl >= 1 && nl <= kMaxLayers, "1 <= layers <= 8");
   RSX_ARG(T > 0 && U > 0 && L > 0 && L <= 64, "need T, U > 0 and 0 < L <= 64");
-  const Layout s = layout(T, U, nl);
+  const bool uq = per_item(p, dims);
+  const int64_t Uq = dims[5];
+  RSX_ARG(!uq || Uq > 0, "per-item pretrained rows need Uq > 0");
+  const Layout s = layout(T, U, nl, uq ? Uq : T);
   RSX_ARG(arena_bytes >= s.total * 4, "arena too small (rsx_tower_arena_bytes)");
   for (int64_t i = 0; i < n_ptrs(nl) - 1; ++i)
     if (i < RSX_TW_ITEMSEG || i >= RSX_TW_ITEM_PROJ) RSX_ARG(p[i] != nullptr, "null input / parameter pointer");
@@ -312,9 +323,9 @@ RSX_API int rsx_tower_fwd(const void* const* p, const int64_t* dims, const float
   float* A = static_cast<float*>(arena);
   const float pd = fargs[0];
   const int pl = RSX_TW_LAYER0 + 12 * nl;  // output head
-  // item_proj (ops.linear_tok -> rsx_gemm_x3)
-  TW_CALL(rsx_gemm_x3(v.f(RSX_TW_PV), kD, v.f(RSX_TW_ITEM_PROJ), kD, v.f(RSX_TW_ITEM_PROJ + 1), T, kD, kD, kEpiBias,
-                      nullptr, 0, 0.0f, 0, A + s.base, kD, stream));
+  // item_proj (ops.linear_tok -> rsx_gemm_x3): over the tokens' rows, or once per distinct item
+  TW_CALL(rsx_gemm_x3(v.f(RSX_TW_PV), kD, v.f(RSX_TW_ITEM_PROJ), kD, v.f(RSX_TW_ITEM_PROJ + 1), uq ? Uq : T, kD, kD,
+                      kEpiBias, nullptr, 0, 0.0f, 0, A + s.base, kD, stream));
   // embedding stage (ops.seq_embed, packed form)
   const int64_t* ids[6];
   const float* tabs[6];
@@ -322,9 +333,9 @@ RSX_API int rsx_tower_fwd(const void* const* p, const int64_t* dims, const float
     ids[j] = v.i64(RSX_TW_IDS + j);
     tabs[j] = v.f(RSX_TW_TABLES + j);
   }
-  TW_CALL(rsx_seq_embed_fwd(A + s.base, ids, tabs, 6, v.f(RSX_TW_GATE), v.f(RSX_TW_POS), v.i64(RSX_TW_TOK_POS),
-                            v.f(RSX_TW_EMB_LN), v.f(RSX_TW_EMB_LN + 1), fargs[1], T, L, kD, pd, seeds[0], A + s.x0,
-                            A + s.m0, A + s.r0, stream));
+  TW_CALL(rsx_seq_embed_fwd(A + s.base, uq ? v.i64(RSX_TW_UIDX) : nullptr, ids, tabs, 6, v.f(RSX_TW_GATE),
+                            v.f(RSX_TW_POS), v.i64(RSX_TW_TOK_POS), v.f(RSX_TW_EMB_LN), v.f(RSX_TW_EMB_LN + 1), fargs[1],
+                            T, L, kD, pd, seeds[0], A + s.x0, A + s.m0, A + s.r0, stream));
   // first norm1 (ops.layer_norm_pass)
   TW_CALL(rsx_ln_fwd(A + s.x0, nullptr, 0.0f, 0, v.f(RSX_TW_LAYER0), v.f(RSX_TW_LAYER0 + 1), fargs[2], 0, T, kD,
                      nullptr, A + s.h0, A + s.mh0, A + s.rh0, stream));
@@ -414,7 +425,10 @@ RSX_API int rsx_tower_bwd(const void* const* p, const int64_t* dims, const float
   const int nl = (int)dims[3];
   RSX_ARG(nl >= 1 && nl <= kMaxLayers, "1 <= layers <= 8");
   RSX_ARG(T > 0 && U > 0 && L > 0 && L <= 64 && C >= 0 && Uq >= 0, "bad sizes");
-  const Layout s = layout(T, U, nl);
+  const bool uq = per_item(p, dims);
+  RSX_ARG(!uq || (Uq > 0 && Uq <= C && !grads[RSX_TW_PV]),
+          "per-item pretrained rows: need 0 < Uq <= C and no pretrained-row gradient");
+  const Layout s = layout(T, U, nl, uq ? Uq : T);
   const BwdLayout b = bwd_layout(T, U, L, C);
   RSX_ARG(ws_bytes >= b.total * 4, "workspace too small (rsx_tower_bwd_workspace_bytes)");
   const int pl = RSX_TW_LAYER0 + 12 * nl;
@@ -547,17 +561,30 @@ RSX_API int rsx_tower_bwd(const void* const* p, const int64_t* dims, const float
   const int64_t rows[6] = {dims[6], dims[7], dims[8], dims[9], dims[10], dims[11]};
   const int64_t pad[6] = {0, 0, 0, 0, 0, 0};
   float* dBase = W + b.dBase;
-  TW_CALL(rsx_seq_embed_bwd(A + s.base, ids, tabs, rows, pad, 6, v.f(RSX_TW_GATE), v.f(RSX_TW_POS),
-                            v.i64(RSX_TW_TOK_POS), v.f(RSX_TW_EMB_LN), A + s.m0, A + s.r0, fargs[1], T, L, kD, pd,
+  TW_CALL(rsx_seq_embed_bwd(A + s.base, uq ? v.i64(RSX_TW_UIDX) : nullptr, ids, tabs, rows, pad, 6, v.f(RSX_TW_GATE),
+                            v.f(RSX_TW_POS), v.i64(RSX_TW_TOK_POS), v.f(RSX_TW_EMB_LN), A + s.m0, A + s.r0, fargs[1], T, L, kD, pd,
                             seeds[0], dX0, dBase, dtabs, G(RSX_TW_GATE), G(RSX_TW_POS), G(RSX_TW_EMB_LN),
                             G(RSX_TW_EMB_LN + 1), W + b.wse, b.n_wse, stream));
   if (C > 0) {
     const int64_t* plan = v.i64(RSX_TW_ITEMSEG);  // perm
     TW_CALL(rsx_segment_sum_rows(dBase, kD, plan, v.i64(RSX_TW_ITEMSEG + 1), v.i64(RSX_TW_ITEMSEG + 2), C, kD, nullptr,
                                  -1, W + b.part, kD, 0, stream));
-    TW_CALL(rsx_segment_sum_rows(W + b.part, kD, v.i64(RSX_TW_ITEMSEG + 2), v.i64(RSX_TW_ITEMSEG + 3),
-                                 v.i64(RSX_TW_ITEMSEG + 4), Uq, kD, v.f(RSX_TW_GATE), 0, G(RSX_TW_TABLES), kD, 1,
-                                 stream));
+    if (uq) {
+      // item_proj over the distinct items: its output row u feeds every token of item u, so its
+      // gradient is the per-item sum of dBase -- the sums of the pass below before the gate, stored
+      // in id order beside the gated table-0 gradient (_SeqEmbed with base_idx)
+      TW_CALL(rsx_segment_sum_rows2(W + b.part, kD, v.i64(RSX_TW_ITEMSEG + 2), v.i64(RSX_TW_ITEMSEG + 3),
+                                    v.i64(RSX_TW_ITEMSEG + 4), Uq, kD, v.f(RSX_TW_GATE), 0, G(RSX_TW_TABLES), kD, 1,
+                                    W + b.dBaseU, kD, stream));
+    } else {
+      TW_CALL(rsx_segment_sum_rows(W + b.part, kD, v.i64(RSX_TW_ITEMSEG + 2), v.i64(RSX_TW_ITEMSEG + 3),
+                                   v.i64(RSX_TW_ITEMSEG + 4), Uq, kD, v.f(RSX_TW_GATE), 0, G(RSX_TW_TABLES), kD, 1,
+                                   stream));
+    }
+  }
+  if (uq) {  // dW / db over the Uq rows
+    TW_CALL(wgrad(W + b.dBaseU, kD, v.f(RSX_TW_PV), kD, Uq, kD, kD, G(RSX_TW_ITEM_PROJ), kD, G(RSX_TW_ITEM_PROJ + 1)));
+    return 0;
   }
   // item_proj (_TokLinear): d(pretrained rows) when asked, dW / db
   if (grads[RSX_TW_PV]) TW_CALL(tn(dBase, kD, v.f(RSX_TW_ITEM_PROJ), kD, T, kD, kD, G(RSX_TW_PV), kD));

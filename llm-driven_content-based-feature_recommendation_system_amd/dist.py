@@ -380,11 +380,11 @@ def _prepare_step_index_device(batch, pretrained_vecs, pretrained_lookup, n_item
     i64, i32, u8, f32 = torch.int64, torch.int32, torch.uint8, torch.float32
     specs = [((T,), i64), ((T,), i64), ((T,), i64), ((T,), u8), ((B + 1,), i32), ((B + 1,), i64), ((Nr,), i64),
              ((B,), i64), ((2 * T,), i64), ((2 * T,), i64), ((2 * T,), i64), ((2 * T,), u8), ((2 * B + 1,), i32),
-             ((2 * B + 1,), i64), ((6, 2 * T), i64), (((2 * T, 128), f32) if pretrained_vecs is None else None),
+             ((2 * B + 1,), i64), ((6, 2 * T), i64), (((U, 128), f32) if pretrained_vecs is None else None),
              ((2 * T,), i64), ((C + 1,), i64), ((C,), i64), ((U + 1,), i64), ((U,), i64), ((D,), i64), ((D,), f32),
              ((Nr,), i32), ((Nr,), i32), ((Nr,), i32), ((Nr,), i32), ((E,), i32), ((E,), i32), ((E,), i32),
-             ((D,), i32), ((D,), i32), ((B,), i32)]
-    out = _carve(specs, dev)  # the 33 index arrays out of ONE allocation
+             ((D,), i32), ((D,), i32), ((B,), i32), ((2 * T,), i64)]
+    out = _carve(specs, dev)  # the 34 index arrays out of ONE allocation
     lk = ops._c(pretrained_lookup) if pretrained_vecs is None else None
     N.check(lib.rsx_step_index_fill(N.ptr(pm8), N.ptr(tgt), N.ptr_array(seq), N.ptr(lk),
                                     lk.stride(0) if lk is not None else 0, B, L, n_items,
@@ -398,7 +398,9 @@ def _prepare_step_index_device(batch, pretrained_vecs, pretrained_lookup, n_item
     pk2.item_seg = tuple(out[16:21])
     tok_ids = list(out[14].unbind(0))
     if pretrained_vecs is None:
-        pv_tok = out[15]
+        # the lookup's rows of the U distinct items (uniq_items' order) and each token's slot in
+        # them: the tower projects every distinct item once (ops.ItemRows)
+        pv_tok = ops.ItemRows(out[15], out[33])
     else:
         pv_tok = pk.take(pretrained_vecs)
         pv_tok = torch.cat([pv_tok, pv_tok])
@@ -419,7 +421,8 @@ def _prepare_step_index_device(batch, pretrained_vecs, pretrained_lookup, n_item
 
 def _device_lookup_ok(pretrained_vecs, lookup, device) -> bool:
     """The device builder gathers the pretrained rows itself (si_pv_k: fp32 rows of exactly 128
-    columns, read through a device pointer, no autograd). Any other lookup -- on the host, of
+    columns, read through a device pointer, no autograd; one row per distinct item of the batch,
+    ops.ItemRows). Any other lookup -- on the host, of
     another dtype or width, or one that requires grad -- takes the torch builders, whose
     ops.gather_rows handles those (and carries the gradient)."""
     if pretrained_vecs is not None:

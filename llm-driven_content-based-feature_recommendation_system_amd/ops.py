@@ -158,29 +158,81 @@ def _zeros_group(likes):
     return out
 
 
+class ItemRows:
+    """The pretrained rows of a packed token list kept once per distinct item: token t's row is
+    rows[idx[t]] (rows [Uq, D] fp32 = the lookup's rows of the step index's uniq_items, idx [T]
+    int64 = each token's slot in them; both dropout views share the slots). item_proj, the
+    embedding stage and item_proj's weight gradient then run over the Uq rows
+    (SASRecUserTower.forward_packed), and the [T, D] per-token matrix is never written.
+
+    The fields to use are rows, idx and materialize() (a fresh rows[idx] gather, [T, D]). The object
+    stands where the step index used to carry that [T, D] tensor (StepIndex.packed[3]), so it also
+    answers shape / dtype / device / len / indexing like it, and any other tensor attribute or torch
+    function is served by a materialised copy -- never cached (the index does not end up holding the
+    matrix it exists to avoid) and counted in ItemRows.materialized, so a path that falls back to the
+    per-token matrix by accident shows up (tests/test_gpu_item_proj_unique.py holds the step at 0)."""
+
+    requires_grad = False
+    materialized = 0  # materialize() calls so far, process-wide
+
+    def __init__(self, rows, idx):
+        self.rows, self.idx = rows, idx
+
+    shape = property(lambda self: torch.Size((self.idx.numel(), self.rows.shape[1])))
+    dtype = property(lambda self: self.rows.dtype)
+    device = property(lambda self: self.rows.device)
+    is_cuda = property(lambda self: self.rows.is_cuda)
+
+    def materialize(self):
+        ItemRows.materialized += 1
+        return gather_rows(self.rows, self.idx)
+
+    def __len__(self):
+        return self.idx.numel()
+
+    def __getitem__(self, key):
+        return self.materialize()[key]
+
+    def __getattr__(self, name):  # only reached for attributes not defined above
+        if name.startswith("__"):
+            raise AttributeError(name)
+        return getattr(self.materialize(), name)
+
+    @classmethod
+    def __torch_function__(cls, func, types, args=(), kwargs=None):
+        def tok(a):
+            return a.materialize() if isinstance(a, ItemRows) else a
+        return func(*[tok(a) for a in args], **{k: tok(v) for k, v in (kwargs or {}).items()})
+
+
 class _SeqEmbed(torch.autograd.Function):
     @staticmethod
     def forward(ctx, base, gate, pos, ln_w, ln_b, ids, cfg, tok_pos, *tables):
-        eps, p_drop, seed, padding_idx, L, tab0_seg = cfg
+        eps, p_drop, seed, padding_idx, L, tab0_seg, base_idx = cfg
         N.ensure_device(base)
         D = base.shape[-1]
-        T = base.numel() // D
         base = _c(base)
         ids = [_c(t) for t in ids]
         tables = [_c(t) for t in tables]
-        out = torch.empty_like(base)
+        if base_idx is None:
+            T = base.numel() // D
+            out = torch.empty_like(base)
+        else:  # token t reads base[base_idx[t]]
+            T = base_idx.numel()
+            out = torch.empty(T, D, device=base.device, dtype=torch.float32)
         mean = torch.empty(T, device=base.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         gate = _c(gate)
         with timed("seq_embed_fwd"):
             rc = N.lib().rsx_seq_embed_fwd(
-                N.ptr(base), N.ptr_array(ids), N.ptr_array(tables), len(tables), N.ptr(gate), N.ptr(pos),
-                N.ptr(tok_pos), N.ptr(ln_w), N.ptr(ln_b), eps, T, L, D, p_drop, seed, N.ptr(out), N.ptr(mean),
-                N.ptr(rstd), N.stream())
+                N.ptr(base), N.ptr(base_idx), N.ptr_array(ids), N.ptr_array(tables), len(tables), N.ptr(gate),
+                N.ptr(pos), N.ptr(tok_pos), N.ptr(ln_w), N.ptr(ln_b), eps, T, L, D, p_drop, seed, N.ptr(out),
+                N.ptr(mean), N.ptr(rstd), N.stream())
         N.check(rc, "seq_embed_fwd")
         ctx.save_for_backward(base, gate, pos, ln_w, mean, rstd, tok_pos, *ids, *tables)
         ctx.cfg = (eps, p_drop, seed, padding_idx, len(tables), T, L, D)
         ctx.tab0_seg = tab0_seg
+        ctx.base_idx = base_idx
         return out
 
     @staticmethod
@@ -192,35 +244,49 @@ class _SeqEmbed(torch.autograd.Function):
         tables = list(saved[7 + nt:7 + 2 * nt])
         dout = _c(dout)
         need = ctx.needs_input_grad
-        dbase = torch.empty_like(base) if need[0] else None
+        base_idx = ctx.base_idx
+        dbase = torch.empty_like(dout) if need[0] else None  # per token, also with base_idx
         dgate, dpos, dlnw, dlnb, *dtabs = _zeros_group(
             [gate if need[1] else None, pos if need[2] else None, ln_w if need[3] else None,
              ln_w if need[4] else None] + [t if need[8 + j] else None for j, t in enumerate(tables)])
         rows = N.i64_array([t.shape[0] for t in tables])
         # table 0 with a prepared sort by id: segmented sums of dx (= dbase) instead of atomics
         seg0 = ctx.tab0_seg if (nt > 0 and dtabs[0] is not None) else None
+        seg_b = ctx.tab0_seg if (base_idx is not None and need[0]) else None  # per-row sums of an indexed base
         if seg0 is not None and dbase is None:
-            dbase = torch.empty_like(base)
+            dbase = torch.empty_like(dout)
         kern_tabs = ([None] + dtabs[1:]) if seg0 is not None else dtabs
         nws = N.lib().rsx_seq_embed_bwd_workspace_floats(T, L, D)
         ws = torch.empty(nws, device=base.device, dtype=torch.float32)
         with timed("seq_embed_bwd"):
             rc = N.lib().rsx_seq_embed_bwd(
-                N.ptr(base), N.ptr_array(ids), N.ptr_array(tables), rows,
+                N.ptr(base), N.ptr(base_idx), N.ptr_array(ids), N.ptr_array(tables), rows,
                 N.i64_array(padding_idx), nt, N.ptr(gate), N.ptr(pos), N.ptr(tok_pos), N.ptr(ln_w), N.ptr(mean),
                 N.ptr(rstd), eps, T, L, D, p_drop, seed, N.ptr(dout), N.ptr(dbase), N.ptr_array(kern_tabs),
                 N.ptr(dgate), N.ptr(dpos), N.ptr(dlnw), N.ptr(dlnb), N.ptr(ws), nws, N.stream())
         N.check(rc, "seq_embed_bwd")
-        if seg0 is not None:  # chunk partials, then per-id sums of its chunks (both deterministic)
-            perm, cb, chunk_ids, ch_off, uniq = seg0
+        if seg0 is not None or seg_b is not None:  # chunk partials, then per-id sums of its chunks (both deterministic)
+            perm, cb, chunk_ids, ch_off, uniq = ctx.tab0_seg
             part = torch.empty(chunk_ids.numel(), D, device=base.device, dtype=torch.float32)
             rc = N.lib().rsx_segment_sum_rows(N.ptr(dbase), D, N.ptr(perm), N.ptr(cb), N.ptr(chunk_ids),
                                               chunk_ids.numel(), D, None, -1, N.ptr(part), D, 0, N.stream())
             N.check(rc, "segment_sum_rows(chunks)")
-            rc = N.lib().rsx_segment_sum_rows(N.ptr(part), D, N.ptr(chunk_ids), N.ptr(ch_off), N.ptr(uniq),
-                                              uniq.numel(), D, N.ptr(gate), padding_idx[0], N.ptr(dtabs[0]),
-                                              dtabs[0].stride(0), 1, N.stream())
-            N.check(rc, "segment_sum_rows(ids)")
+            if seg_b is not None:  # the per-id sums ungated, in segment order: the gradient of base's rows
+                dbase = torch.empty_like(base)
+            if seg0 is not None and seg_b is not None:  # one pass: gated into table 0, raw into dbase
+                rc = N.lib().rsx_segment_sum_rows2(N.ptr(part), D, N.ptr(chunk_ids), N.ptr(ch_off), N.ptr(uniq),
+                                                   uniq.numel(), D, N.ptr(gate), padding_idx[0], N.ptr(dtabs[0]),
+                                                   dtabs[0].stride(0), 1, N.ptr(dbase), D, N.stream())
+                N.check(rc, "segment_sum_rows2(ids)")
+            elif seg0 is not None:
+                rc = N.lib().rsx_segment_sum_rows(N.ptr(part), D, N.ptr(chunk_ids), N.ptr(ch_off), N.ptr(uniq),
+                                                  uniq.numel(), D, N.ptr(gate), padding_idx[0], N.ptr(dtabs[0]),
+                                                  dtabs[0].stride(0), 1, N.stream())
+                N.check(rc, "segment_sum_rows(ids)")
+            else:
+                rc = N.lib().rsx_segment_sum_rows(N.ptr(part), D, N.ptr(chunk_ids), N.ptr(ch_off), None,
+                                                  uniq.numel(), D, None, -1, N.ptr(dbase), D, 0, N.stream())
+                N.check(rc, "segment_sum_rows(base)")
         if not need[0]:
             dbase = None
         return (dbase, dgate, dpos, dlnw, dlnb, None, None, None, *dtabs)
@@ -255,7 +321,7 @@ def sort_segments(ids):
 
 
 def seq_embed(base, ids, tables, gate, pos, ln_w, ln_b, eps=1e-5, p_drop=0.0, padding_idx=None, tok_pos=None,
-              tab0_seg=None):
+              tab0_seg=None, base_idx=None):
     """x = base + sum_j tables[j][ids[j]] * gate[j] + pos[l] ; LayerNorm ; dropout.
 
     Dense: base [B, L, D], ids [B, L], pos [>= L, D] (position = token % L).
@@ -263,6 +329,10 @@ def seq_embed(base, ids, tables, gate, pos, ln_w, ln_b, eps=1e-5, p_drop=0.0, pa
     gate [ntab]; ln_w/ln_b [D]. padding_idx: per-table row excluded from the table gradient
     (nn.Embedding semantics). tab0_seg: sort_segments(ids[0]) — table 0's gradient then comes
     from rsx_segment_sum_rows (deterministic, no atomics) instead of the kernel's scatter-add.
+    base_idx (packed form with tab0_seg): base holds one row per distinct ids[0] value, in
+    tab0_seg's uniq order, and token t reads base[base_idx[t]] (base_idx[t] = the slot of
+    ids[0][t] in uniq); base's gradient is then the per-slot sum of the per-token one, from the
+    same sorted segment sums.
     """
     if padding_idx is None:
         padding_idx = [-1] * len(tables)
@@ -274,7 +344,12 @@ def seq_embed(base, ids, tables, gate, pos, ln_w, ln_b, eps=1e-5, p_drop=0.0, pa
     else:
         L = pos.shape[0]
         tok_pos = _c(tok_pos)
-    cfg = (float(eps), float(p_drop), seed, padding_idx, int(L), tab0_seg)
+    if base_idx is not None:
+        if tok_pos is None or tab0_seg is None or base.dim() != 2 or base.shape[0] != tab0_seg[4].numel():
+            raise RuntimeError("seq_embed: base_idx needs the packed form, tab0_seg and one base row per "
+                               "distinct ids[0] value")
+        base_idx = _c(_index("seq_embed", "base_idx", base_idx, base, ids[0].numel()))
+    cfg = (float(eps), float(p_drop), seed, padding_idx, int(L), tab0_seg, base_idx)
     return _SeqEmbed.apply(base, gate, pos, ln_w, ln_b, list(ids), cfg, tok_pos, *tables)
 
 
@@ -1785,16 +1860,19 @@ class _TowerPacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pv, gate, profile, cfg, *params):
-        packed, tok_ids, p_drop, eps, nl, tail_last = cfg
-        T, D = pv.shape
+        packed, tok_ids, p_drop, eps, nl, tail_last, tok_uidx = cfg
+        T, D = tok_ids[0].numel(), pv.shape[1]
         U = packed.seg_off.numel() - 1
         dev = pv.device
         pv = _c(pv)
         gate = _c(gate)
         profile = _c(profile)
         perm, cb, chunk_ids, ch_off, uniq = packed.item_seg
+        # tok_uidx: pv holds one row per distinct item (uniq's order), token t reads row tok_uidx[t]
+        assert pv.shape[0] == (T if tok_uidx is None else uniq.numel())
         inputs = ([pv] + list(tok_ids) + [packed.tok_pos, packed.tok_pad, packed.seg_off, packed.seg_off64,
-                                            packed.tok_user, gate, profile, perm, cb, chunk_ids, ch_off, uniq])
+                                            packed.tok_user, gate, profile, perm, cb, chunk_ids, ch_off, uniq,
+                                            tok_uidx])
         tail_last = None if tail_last is None else _c(tail_last)
         ptrs = N.ptr_array(inputs + list(params) + [tail_last])
         tabs = params[2:8]
@@ -1805,7 +1883,7 @@ class _TowerPacked(torch.autograd.Function):
         fargs = (ctypes.c_float * (len(eps) + 1))(p_drop, *eps)
         seeds = [next_seed() if p_drop > 0 else 0 for _ in range(1 + 4 * nl)]
         seeds_arr = (ctypes.c_uint64 * len(seeds))(*seeds)
-        nbytes = N.lib().rsx_tower_arena_bytes(T, U, nl)
+        nbytes = N.lib().rsx_tower_arena_bytes(T, U, nl, pv.shape[0])
         arena = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         out = torch.empty(R, D, device=dev, dtype=torch.float32)
         with timed("tower_fwd"):
@@ -1834,7 +1912,7 @@ class _TowerPacked(torch.autograd.Function):
         dprofile = written[-1]
         dparams = [written[0], written[1]] + acc + written[2:-1]
         dpv = torch.empty_like(pv) if ctx.needs_input_grad[0] else None
-        grads = [dpv] + [None] * 11 + [dgate, dprofile] + [None] * 5 + dparams + [None]
+        grads = [dpv] + [None] * 11 + [dgate, dprofile] + [None] * 6 + dparams + [None]
         nws = N.lib().rsx_tower_bwd_workspace_bytes(T, U, L, nl, C)
         ws = torch.empty(nws, device=dev, dtype=torch.uint8)
         with timed("tower_bwd"):
@@ -1863,13 +1941,17 @@ def _empty_group(likes):
 def tower_packed(model, packed, pv_tok, tok_ids, s_g, profile, p_drop, params=None, tail_last=None):
     """The native form of SASRecUserTower.forward_packed after the static profile: [T, 128], or with
     tail_last (view 1's "last" token per user, [B]) the [T/2 + B, 128] tail rows (see
-    rsx_tower_fwd). params: tower_native_ok's list (else rebuilt)."""
+    rsx_tower_fwd). params: tower_native_ok's list (else rebuilt). pv_tok: the [T, 128] rows, or
+    ItemRows: item_proj and its weight gradient then run once per distinct item."""
     layers = model.transformer_encoder.layers
     eps = [model.emb_ln.eps]
     for layer in layers:
         eps += [layer.norm1.eps, layer.norm2.eps]
     eps.append(model.output_proj[1].eps)
-    cfg = (packed, [_c(t) for t in tok_ids], float(p_drop), [float(e) for e in eps], len(layers), tail_last)
+    tok_uidx = None
+    if isinstance(pv_tok, ItemRows):
+        pv_tok, tok_uidx = pv_tok.rows, _c(pv_tok.idx)
+    cfg = (packed, [_c(t) for t in tok_ids], float(p_drop), [float(e) for e in eps], len(layers), tail_last, tok_uidx)
     return _TowerPacked.apply(pv_tok, s_g, profile, cfg, *(params if params is not None else tower_params(model)))
 
 

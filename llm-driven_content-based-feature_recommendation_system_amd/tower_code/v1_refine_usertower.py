@@ -355,18 +355,28 @@ class SASRecUserTower(nn.Module):
         # the static profile first (its dropout seed is drawn before the tower's, on both paths)
         profile = self._static_profile(age_bucket, price_bucket, cnt_bucket, recency_bucket, channel_ids,
                                        club_status_ids, news_freq_ids, fn_ids, active_ids, cont_feats, p, packed.B)
+        # pretrained rows kept per distinct item (ops.ItemRows, the device-built step index): item_proj
+        # runs over those rows and the embedding stage reads its output through the tokens' slots;
+        # without the item-id sort plan (which sums the gradient per item) the per-token form runs.
+        # With gradients off the per-op path below runs the same per-item form.
+        item_seg = getattr(packed, "item_seg", None)
+        tok_uidx = None
+        if isinstance(pretrained_tok, ops.ItemRows) and item_seg is None:
+            pretrained_tok = pretrained_tok.materialize()
         params = ops.tower_native_ok(self, packed, pretrained_tok) if torch.is_grad_enabled() else None
         if params is not None:
             # the same kernels in the same order as below, issued by the library in one call per
             # direction (rsx_tower_fwd / rsx_tower_bwd)
             return ops.tower_packed(self, packed, pretrained_tok, tok_ids, s_g, profile, p, params, tail_last)
+        if isinstance(pretrained_tok, ops.ItemRows):
+            pretrained_tok, tok_uidx = pretrained_tok.rows, pretrained_tok.idx
         base = ops.linear_tok(pretrained_tok, self.item_proj.weight, self.item_proj.bias)
         x = ops.seq_embed(
             base, tok_ids,
             [self.item_id_emb.weight, self.time_emb.weight, self.type_emb.weight, self.color_emb.weight,
              self.graphic_emb.weight, self.section_emb.weight],
             s_g, self.pos_emb.weight, self.emb_ln.weight, self.emb_ln.bias, eps=self.emb_ln.eps, p_drop=p,
-            padding_idx=[0, 0, 0, 0, 0, 0], tok_pos=packed.tok_pos, tab0_seg=getattr(packed, "item_seg", None))
+            padding_idx=[0, 0, 0, 0, 0, 0], tok_pos=packed.tok_pos, tab0_seg=item_seg, base_idx=tok_uidx)
         x = self._encoder_stack(x, packed.tok_pad, p, seg_off=packed.seg_off)
         lin0, ln, lin3 = self.output_proj[0], self.output_proj[1], self.output_proj[3]
         D = self.d_model
