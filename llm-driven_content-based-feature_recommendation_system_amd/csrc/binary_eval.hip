@@ -26,10 +26,13 @@
 // are integers (any order gives the same bits); the only floating-point sum is the Logloss, whose
 // order is fixed.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <limits.h>
 
 namespace {
+
+using rsx::score_key;
 
 constexpr int kThreads = 256, kPer = 8, kTile = kThreads * kPer;
 constexpr int kLossSlots = 1024;  // workgroups of the key pass (each one Logloss partial)
@@ -86,12 +89,6 @@ __device__ __forceinline__ int block_scan_excl(int x, Op op, int ident, int* sm,
   if (lane == (REV ? 63 : 0)) e = ident;
   __syncthreads();  // sm is free for the next scan
   return op(pre, e);
-}
-
-__device__ __forceinline__ unsigned score_key(float z) {
-  unsigned u = __float_as_uint(z);
-  if (z == 0.0f) u = 0u;  // -0.0 and +0.0 tie
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 template <bool VEC>

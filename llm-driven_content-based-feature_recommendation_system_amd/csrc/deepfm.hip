@@ -13,11 +13,12 @@
 //                   64 rows x up to 256 output columns per workgroup, K streamed through
 //                   LDS in 32-wide chunks; optional fused final dot + add + sigmoid.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rsx::f32x16;
 constexpr int kMaxFields = 64;
 
 struct EmbedArgs {
@@ -99,7 +100,7 @@ struct LinArgs {
 
 __device__ __forceinline__ float act_fn(float v, int act) {
   if (act == 1) return v > 0.0f ? v : 0.0f;
-  if (act == 2) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752f));
+  if (act == 2) return rsx::gelu_erf(v);
   return v;
 }
 

@@ -23,14 +23,11 @@
 // Barriers (both roles, in order): one per staged chunk (nchunk + 1 in all), then two per n2
 // half of layer 2.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+using rsx::bf16x4, rsx::bf16x8, rsx::f32x16, rsx::u32x2, rsx::u32x4, rsx::x3_lo;
 
 constexpr int kMaxF = 64;
 constexpr int kFC = 13;          // fields per chunk
@@ -67,12 +64,7 @@ struct FArgs {
 
 __device__ __forceinline__ void split4(const float4& v, bf16x4& h, bf16x4& l) {
   const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const __bf16 hk = (__bf16)f[k];
-    h[k] = hk;
-    l[k] = (__bf16)(f[k] - (float)hk);
-  }
+  rsx::split_x3(f, h, l);
 }
 
 struct Lds {
@@ -261,7 +253,7 @@ __global__ __launch_bounds__(512, 1) void deepfm_fused_k(FArgs a) {
           const __bf16 hv = (__bf16)v;
           const int t = 2 * j + (g >> 1), el = 4 * (g & 1) + e;
           gh[i][t][el] = hv;
-          gl[i][t][el] = (__bf16)(v - (float)hv);
+          gl[i][t][el] = x3_lo(v, hv);
         }
     }
 
@@ -316,7 +308,7 @@ __global__ __launch_bounds__(256) void deepfm_prep_k(const float* w1, int F, int
     const float v = f < F ? w1[(int64_t)n * F * 16 + f * 16 + k] : 0.0f;
     const __bf16 hv = (__bf16)v;
     w1hi[i] = hv;
-    w1lo[i] = (__bf16)(v - (float)hv);
+    w1lo[i] = x3_lo(v, hv);
     return;
   }
   const int64_t j = i - n1;
@@ -327,7 +319,7 @@ __global__ __launch_bounds__(256) void deepfm_prep_k(const float* w1, int F, int
     const float v = w2[(int64_t)n2 * kN1 + k];
     const __bf16 hv = (__bf16)v;
     w2hi[j] = hv;
-    w2lo[j] = (__bf16)(v - (float)hv);
+    w2lo[j] = x3_lo(v, hv);
   }
 }
 
@@ -667,7 +659,7 @@ __global__ __launch_bounds__(256) void deepfm_prep2_k(const float* w1, int F, in
   }
   const __bf16 hv = (__bf16)v;
   *dh = hv;
-  *dl = (__bf16)(v - (float)hv);
+  *dl = x3_lo(v, hv);
 }
 
 // packed table of one field: out[id][0..15] = V[id], out[id][16] = W[id] (0 if W is null),
@@ -846,7 +838,7 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
         fq += v[k] * v[k];
         const __bf16 hv = (__bf16)v[k];
         bh[k] = hv;
-        bl[k] = (__bf16)(v[k] - (float)hv);
+        bl[k] = x3_lo(v[k], hv);
       }
       fw += (w.x + w.y) + (w.z + w.w);  // W on h = 0, zeros elsewhere (issue)
     }
@@ -907,7 +899,7 @@ __global__ __launch_bounds__(320, 1) void deepfm_rows5_k(RArgs a) {
         v = v > 0.0f ? v : 0.0f;
         const __bf16 hv = (__bf16)v;
         gh[4 * p + e] = hv;
-        gl[4 * p + e] = (__bf16)(v - (float)hv);
+        gl[4 * p + e] = x3_lo(v, hv);
       }
     }
 #pragma unroll
@@ -1114,7 +1106,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
         fq[m] += v[k] * v[k];
         const __bf16 hv = (__bf16)v[k];
         bh[st][m][k] = hv;
-        bl[st][m][k] = (__bf16)(v[k] - (float)hv);
+        bl[st][m][k] = x3_lo(v[k], hv);
       }
       // bytes 64..95 of the line: W then zeros (deepfm_pack_k), so the whole 16-B piece sums
       // to W on h = 0 and to 0 on h = 1 (all four components used: a dword load of the same
@@ -1257,7 +1249,7 @@ __global__ __launch_bounds__(512 / MT, 1) void deepfm_rows2m_k(RArgs a) {
           v = v > 0.0f ? v : 0.0f;
           const __bf16 hv = (__bf16)v;
           gh[set][m][4 * p + e] = hv;
-          gl[set][m][4 * p + e] = (__bf16)(v - (float)hv);
+          gl[set][m][4 * p + e] = x3_lo(v, hv);
         }
       }
     }
@@ -1342,7 +1334,7 @@ __global__ __launch_bounds__(256) void deepfm_prep3_k(const float* w1, int F, __
   const __bf16 hv = (__bf16)v;
   __bf16* img = out + (int64_t)f * kW1Field;
   img[w1_idx(n, s)] = hv;
-  img[4096 + w1_idx(n, s)] = (__bf16)(v - (float)hv);
+  img[4096 + w1_idx(n, s)] = x3_lo(v, hv);
 }
 
 size_t persist_lds_bytes(int id_stride) {

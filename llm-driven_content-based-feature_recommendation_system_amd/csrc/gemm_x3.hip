@@ -29,13 +29,12 @@
 // for three workgroups per CU (the GEMMs are latency-bound at two). XCD-aware order: the N tiles of one
 // M block run back to back on one XCD, so A's rows are re-read from that XCD's L2.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using rsx::bf16x8, rsx::f32x16, rsx::tile_row, rsx::u32x4;
 
 #ifndef RSX_GEMM_BK
 #define RSX_GEMM_BK 16  // measured (tools/gemm_micro.py): 16 beats 32 by 10-15 % (48 KB LDS: 3 workgroups/CU)
@@ -47,8 +46,6 @@ constexpr int EPI_BIAS = 0, EPI_GELU_DROP = 1, EPI_DGELU_DROP = 2, EPI_ROWADD = 
 #ifndef RSX_GEMM_BLOCKS
 #define RSX_GEMM_BLOCKS (1 << 30)  // workgroup budget of the multi-tile stream: at BK 16 one tile each measured best
 #endif
-
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // gelu(x) = x Phi(x) and gelu'(x) = Phi(x) + x phi(x), branch-free for the weight-stationary
 // epilogue: Phi from erfc(z) ~ t P(t) e^{-z^2}, t = 1 / (1 + p z), z = |x| / sqrt 2 (Abramowitz &
@@ -70,16 +67,15 @@ __device__ __forceinline__ void gelu_pair(float x, float& g, float& d) {
   d = fmaf(x * 0.3989422804014327f, e, cdf);
 }
 
-// rsx::hash_u32(seed, idx) for idx < 2^32 (the high-word terms vanish), in 32-bit ops
+// gelu'(v) from cdf = rsx::gelu_erf_cdf(v) in the epilogues that also want gelu(v) = v cdf. Left local:
+// rsx::gelu_erf / gelu_erf_grad associate the products differently ((0.5 v)(1 + erf), v (c e)),
+// which changes the kernels' assembly.
+__device__ __forceinline__ float gelu_grad_cdf(float v, float cdf) {
+  return cdf + v * 0.3989422804014327f * __expf(-0.5f * v * v);
+}
+
 __device__ __forceinline__ bool keep(const rsx::Dropout& d, uint32_t idx) {
-  uint32_t x = idx ^ (uint32_t)d.seed;
-  x ^= (uint32_t)(d.seed >> 32) * 0x85EBCA77u;
-  x ^= x >> 16;
-  x *= 0x85EBCA6Bu;
-  x ^= x >> 13;
-  x *= 0xC2B2AE35u;
-  x ^= x >> 16;
-  return x >= d.thresh;
+  return rsx::hash_u32_idx32(d.seed, idx) >= d.thresh;
 }
 
 template <int BK>
@@ -117,12 +113,7 @@ struct GArgs {
 __device__ __forceinline__ void split8(const float4& x, const float4& y, u32x4& hi, u32x4& lo) {
   const float f[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
   bf16x8 h, l;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 hk = (__bf16)f[k];
-    h[k] = hk;
-    l[k] = (__bf16)(f[k] - (float)hk);
-  }
+  rsx::split_x3(f, h, l);
   hi = __builtin_bit_cast(u32x4, h);
   lo = __builtin_bit_cast(u32x4, l);
 }
@@ -165,8 +156,8 @@ __device__ __forceinline__ void epilogue(const GArgs& a, f32x16 (&acc)[2][2], in
           v += bn;
         } else if (EPI == EPI_GELU_DROP) {
           v += bn;
-          const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
-          if (a.aux) a.aux[m * a.ldaux + n] = cdf + v * 0.3989422804014327f * __expf(-0.5f * v * v);  // gelu'(v)
+          const float cdf = rsx::gelu_erf_cdf(v);
+          if (a.aux) a.aux[m * a.ldaux + n] = gelu_grad_cdf(v, cdf);
           v *= cdf;  // gelu(v)
           if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
         } else if (a.drop.active()) {
@@ -343,9 +334,9 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_k(GArgs a) {
     v += bn;
   } else if (EPI == EPI_GELU_DROP) {
     v += bn;
-    const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752f));
-    if (a.aux) a.aux[m * a.ldaux + n] = cdf + v * 0.3989422804014327f * __expf(-0.5f * v * v);
-    v *= cdf;
+    const float cdf = rsx::gelu_erf_cdf(v);
+    if (a.aux) a.aux[m * a.ldaux + n] = gelu_grad_cdf(v, cdf);
+    v *= cdf;  // gelu(v)
     if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
   } else if (a.drop.active()) {
     v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;

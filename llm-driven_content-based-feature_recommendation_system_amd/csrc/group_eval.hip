@@ -32,10 +32,13 @@
 // The double sums have a fixed order (the scans' trees depend on the sizes only) and the integer sums
 // are exact: the outputs are the same bits every run. No float atomics.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <string.h>
 
 namespace {
+
+using rsx::score_key;
 
 constexpr int kThreads = 256, kPer = 8, kTile = kThreads * kPer;
 constexpr int kGroupBlocks = 256;  // most workgroups of ge_group_k (each one partial of the summary)
@@ -131,12 +134,6 @@ struct SegOp {
 __device__ __forceinline__ i64 pack(int64_t row, int cx) { return (i64)((u64)row << 32 | (unsigned)cx); }
 __device__ __forceinline__ int64_t pack_row(i64 p) { return (int64_t)(p >> 32); }
 __device__ __forceinline__ int pack_cx(i64 p) { return (int)(unsigned)(p & 0xffffffffll); }
-
-__device__ __forceinline__ unsigned score_key(float z) {
-  unsigned u = __float_as_uint(z);
-  if (z == 0.0f) u = 0u;  // -0.0 and +0.0 tie
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 __global__ __launch_bounds__(kThreads) void ge_key_k(const float* __restrict__ logit, const float* __restrict__ y,
                                                       const int* __restrict__ gid, int64_t R, int64_t max_gid,

@@ -16,22 +16,15 @@
 // Output order: mining value descending, then column index ascending (torch.topk leaves tie
 // order unspecified; ties need equal fp32 quotients, which random cosines do not produce).
 #include "rsx_common.h"
+#include "rsx_x3.h"
 
 namespace {
 
+using rsx::f32x16, rsx::ordered_key, rsx::tile_row;
+
 constexpr int kThreads = 256;
-
-__device__ __forceinline__ uint32_t f2key(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kRowsPerBlock = 128;
 constexpr int kTileCols = 32;
-
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 int64_t ws_ld(int64_t N) { return (N + kTileCols - 1) / kTileCols * kTileCols; }
 
@@ -205,7 +198,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t row0 = (int64_t)blockIdx.x * R;
-  const uint32_t kNegInf = f2key(-INFINITY);
+  const uint32_t kNegInf = ordered_key(-INFINITY);
 
   for (int e = tid; e < R * D; e += kThreads) {
     const int r = e / D, c = e % D;
@@ -224,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
       const float* src = ws + (row0 + r) * ldw;
       for (int64_t j = tid; j < N; j += kThreads) {
         const float x = src[j] / tau;
-        const uint32_t key = f2key(x);
+        const uint32_t key = ordered_key(x);
         if (key != kNegInf) {
           ++avail;
           mx = max(mx, key);
@@ -287,7 +280,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
             slot0 = (uint32_t)__shfl((int)slot0, 0, 64);
             if (take)
               s_sort[slot0 + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] =
-                  ((unsigned long long)f2key(x) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)j);
+                  ((unsigned long long)ordered_key(x) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)j);
           }
           __syncthreads();
           nsort = 1;
@@ -308,7 +301,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
         const uint32_t prefix = s_sel[0];
         const uint32_t rem = s_sel[1];
         for (int64_t j = tid; j < N; j += kThreads) {
-          const uint32_t key = f2key(v[j]);
+          const uint32_t key = ordered_key(v[j]);
           if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -328,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
       for (int64_t j0 = 0; j0 < N; j0 += kThreads) {
         const int64_t j = j0 + tid;
         uint32_t key = 0u;
-        if (j < N) key = f2key(v[j]);
+        if (j < N) key = ordered_key(v[j]);
         const unsigned long long code = ((unsigned long long)key << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)j);
         const bool gt = j < N && key > T, eq = j < N && key == T;
         uint32_t e_gt, e_eq;

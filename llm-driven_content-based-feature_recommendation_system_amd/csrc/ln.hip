@@ -24,12 +24,7 @@ struct Geo {
   static constexpr int RPW = 64 / LPR;
 };
 
-__device__ __forceinline__ float gelu_erf(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
-__device__ __forceinline__ float gelu_erf_grad(float z) {
-  const float cdf = 0.5f * (1.0f + erff(z * 0.70710678118654752f));
-  const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
-  return cdf + z * pdf;
-}
+using rsx::gelu_erf, rsx::gelu_erf_grad;
 
 struct FArgs {
   const float* x;

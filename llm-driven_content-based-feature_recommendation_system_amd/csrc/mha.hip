@@ -16,6 +16,7 @@
 // One 64-lane workgroup per (batch, head): lane i owns query row i. K/V rows of the head
 // are staged in LDS and read by broadcast; scores live in registers (L <= 64).
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -428,8 +429,7 @@ __global__ __launch_bounds__(64) void mha_bwd64_k(BwdArgs a) {
 //   query on the lane (dQ):    S^T = K Q^T, dP'^T = V dO^T -> dS^T   -> dQ^T += K^T dS^T
 // S and dP' are computed in both orientations (the MFMA work is small; no transposes). The
 // per-element mask, dropout hash, softmax and dS formulas are those of mha_bwd_k.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+using rsx::f32x16, rsx::tile_row;
 
 // 16 dims (16h .. 16h+15) of token row `row` of matrix base (row stride ld), zeros if !ok
 __device__ __forceinline__ void load_row16(float (&x)[16], const float* base, int64_t ld, int64_t row, bool ok,
@@ -623,10 +623,8 @@ __global__ __launch_bounds__(256) void mha_bwd_mfma_k(BwdArgs a) {
 // the tile than 32 on the H&M lengths (mean ~19 tokens). MFMA cycles per 16x16 block pair:
 // fwd 3x16 + 6x8, bwd (two passes) 12x16 + 18x8, against 8x(16x4 f32) = 256 per product on
 // the fp32 MFMA.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using rsx::bf16x4, rsx::bf16x8, rsx::f32x4, rsx::u32x4;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct Row8 {  // dims 8g .. 8g+7 of one token row, split
   bf16x8 hi, lo;
@@ -637,12 +635,7 @@ struct Col4 {  // 4 consecutive token rows of one column, split
 
 __device__ __forceinline__ Col4 split4(const float (&f)[4]) {
   bf16x4 h, l;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const __bf16 hk = (__bf16)f[k];
-    h[k] = hk;
-    l[k] = (__bf16)(f[k] - (float)hk);
-  }
+  rsx::split_x3(f, h, l);
   Col4 c;
   c.hi = __builtin_bit_cast(s16x4, h);
   c.lo = __builtin_bit_cast(s16x4, l);
@@ -669,17 +662,11 @@ __device__ __forceinline__ f32x4 sum16_x3(const Col4& a, const Col4& b, f32x4 ac
 // sequence's rows (rows >= L read as zero by the range check: no branches, no per-load waits),
 // so a wave pays one memory latency instead of one or two per query block (loading K / V per
 // query block behind data-dependent branches).
-typedef unsigned int u32x4b __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ Row8 split_row8(const u32x4b& x0, const u32x4b& x1) {
+__device__ __forceinline__ Row8 split_row8(const u32x4& x0, const u32x4& x1) {
   const float f[8] = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w),
                       __uint_as_float(x1.x), __uint_as_float(x1.y), __uint_as_float(x1.z), __uint_as_float(x1.w)};
   Row8 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 h = (__bf16)f[k];
-    r.hi[k] = h;
-    r.lo[k] = (__bf16)(f[k] - (float)h);
-  }
+  rsx::split_x3(f, r.hi, r.lo);
   return r;
 }
 template <int NB>
@@ -693,7 +680,7 @@ __device__ __forceinline__ void mha_fwd_x3b_seq(const FwdArgs& a, int hd, int64_
   const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * ld * 4));
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
-  u32x4b qr[NB][2], kr[NB][2];
+  u32x4 qr[NB][2], kr[NB][2];
   unsigned vr[NB][2][4];
 #pragma unroll
   for (int bb = 0; bb < NB; ++bb) {
@@ -795,7 +782,7 @@ __device__ __forceinline__ void mha_fwd_x3b64_seq(const FwdArgs& a, int hd, int6
   const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * ld * 4));
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
-  u32x4b qr[NB][2][2], kr[NB][2][2];
+  u32x4 qr[NB][2][2], kr[NB][2][2];
   unsigned vr[NB][4][4];
 #pragma unroll
   for (int bb = 0; bb < NB; ++bb) {
@@ -934,7 +921,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t seq_rsrc(const void* base, uns
                                            (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
 }
 struct RawRow {  // dims 8g .. 8g+7 of one token row, as loaded
-  u32x4b x0, x1;
+  u32x4 x0, x1;
 };
 __device__ __forceinline__ RawRow load_rawrow(__amdgpu_buffer_rsrc_t rs, unsigned off) {
   RawRow r;
@@ -1366,12 +1353,7 @@ __device__ __forceinline__ f32x4 dot16_x3_acc(const Row8& a, const Row8& b, f32x
 
 __device__ __forceinline__ Row8 split_f8(const float (&f)[8]) {
   Row8 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 h = (__bf16)f[k];
-    r.hi[k] = h;
-    r.lo[k] = (__bf16)(f[k] - (float)h);
-  }
+  rsx::split_x3(f, r.hi, r.lo);
   return r;
 }
 
@@ -1386,7 +1368,7 @@ __device__ __forceinline__ void mha_qkv_fwd_x3_seq(const QArgs& a, int hd, int64
   const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * D * 4));
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
-  u32x4b xr[KS][NB][2];
+  u32x4 xr[KS][NB][2];
 #pragma unroll
   for (int s = 0; s < KS; ++s)
 #pragma unroll

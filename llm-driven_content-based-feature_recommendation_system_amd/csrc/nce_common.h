@@ -2,6 +2,7 @@
 // Kernels stay in an anonymous namespace of their own file; only host launchers cross files.
 #pragma once
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <math.h>
 #include <algorithm>
 #include <type_traits>
@@ -9,7 +10,8 @@
 namespace rsx {
 namespace nce {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+// named here so that the units' `using namespace rsx::nce` finds them
+using rsx::bf16x2, rsx::bf16x4, rsx::bf16x8, rsx::f32x16, rsx::f32x2, rsx::f32x4, rsx::tile_row, rsx::u32x4;
 
 constexpr int kD = 128;        // embedding width (fixed by the reference: d_model=128)
 constexpr int kTile = 32;      // streamed rows per tile
@@ -38,8 +40,6 @@ struct FwdArgs {
   const __bf16* shi;  // bf16x3: hi/lo images [M][128] of the streamed rows
   const __bf16* slo;
 };
-
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // Block-id remap: all workgroups of one column split share an XCD group (b % 8), so the
 // split's streamed operand is re-read from that XCD's L2. Speed only, never correctness.

@@ -319,14 +319,14 @@ __device__ __forceinline__ void grad_half_x3(f32x16 (&gacc)[4], const bf16x8& gh
                                              int base, int ks, const f32x16& x, int xh, float m, uint32_t (&oh)[4],
                                              uint32_t (&ol)[4], f32x2& sum) {
   bf16x8 bh, bl;
-  grad_rd(t.hi, base, ks, 0, bh);
-  grad_rd(t.lo, base, ks, 0, bl);
+  bh = img_read_tr(t.hi, base, ks, 0);
+  bl = img_read_tr(t.lo, base, ks, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     bf16x8 nh = bh, nl = bl;
     if (nb < 3) {
-      grad_rd(t.hi, base, ks, nb + 1, nh);
-      grad_rd(t.lo, base, ks, nb + 1, nl);
+      nh = img_read_tr(t.hi, base, ks, nb + 1);
+      nl = img_read_tr(t.lo, base, ks, nb + 1);
     }
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, bh, gacc[nb], 0, 0, 0);
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, bl, gacc[nb], 0, 0, 0);
@@ -414,14 +414,14 @@ __device__ __forceinline__ void grad_half_g_x3(f32x16 (&gacc)[4], const bf16x8& 
                                                const float* m1, float o_m2, float it2, float fo, uint32_t (&oh)[4],
                                                uint32_t (&ol)[4]) {
   bf16x8 bh, bl;
-  grad_rd(t.hi, base, ks, 0, bh);
-  grad_rd(t.lo, base, ks, 0, bl);
+  bh = img_read_tr(t.hi, base, ks, 0);
+  bl = img_read_tr(t.lo, base, ks, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     bf16x8 nh = bh, nl = bl;
     if (nb < 3) {
-      grad_rd(t.hi, base, ks, nb + 1, nh);
-      grad_rd(t.lo, base, ks, nb + 1, nl);
+      nh = img_read_tr(t.hi, base, ks, nb + 1);
+      nl = img_read_tr(t.lo, base, ks, nb + 1);
     }
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl, bh, gacc[nb], 0, 0, 0);
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gh, bl, gacc[nb], 0, 0, 0);
@@ -757,7 +757,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_x3_k(GArgs a) {
         gh[0] = __builtin_bit_cast(bf16x8, h0);
         gl[0] = __builtin_bit_cast(bf16x8, l0);
         uint32_t oh[4], ol[4];
-        const int gbase = grad_lane_base(lane);
+        const int gbase = img_tr_base(lane);
         grad_half_g_x3<ROW_OWNED, true>(gacc, gh[0], gl[0], sT[cur], gbase, 0, acc, h, sM0[cur], sM1[cur], o_m2, it2,
                                         fo, oh, ol);
         gh[1] = __builtin_bit_cast(bf16x8, u32x4{oh[0], oh[1], oh[2], oh[3]});
@@ -840,7 +840,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwdg_x3p_k(GArgs a) {
       pgh[k] = (__bf16)0.0f;
       pgl[k] = (__bf16)0.0f;
     }
-    const int gbase = grad_lane_base(lane);
+    const int gbase = img_tr_base(lane);
     for (int64_t j0 = j_begin; j0 < j_end; j0 += kTile) {
       const bool has_next = j0 + kTile < j_end;
       const bool exc = (int64_t)next < j0 + kTile;  // before the prefetch (see the backward)

@@ -116,14 +116,14 @@ template <bool WORK, int GP>
 __device__ __forceinline__ void grad_half_h(f32x16 (&gacc)[4], const bf16x8& g, const X3Tile& t, int base, int ks,
                                             const f32x16& x, int xh, float m, uint32_t (&og)[4], f32x2& sum) {
   bf16x8 bh, bl;
-  grad_rd(t.hi, base, ks, 0, bh);
-  if (GP == 2) grad_rd(t.lo, base, ks, 0, bl);
+  bh = img_read_tr(t.hi, base, ks, 0);
+  if (GP == 2) bl = img_read_tr(t.lo, base, ks, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     bf16x8 nh = bh, nl = bl;
     if (nb < 3) {
-      grad_rd(t.hi, base, ks, nb + 1, nh);
-      if (GP == 2) grad_rd(t.lo, base, ks, nb + 1, nl);
+      nh = img_read_tr(t.hi, base, ks, nb + 1);
+      if (GP == 2) nl = img_read_tr(t.lo, base, ks, nb + 1);
     }
     if (GP == 2) gacc[nb] = mfma_h(g, bl, gacc[nb]);
     gacc[nb] = mfma_h(g, bh, gacc[nb]);
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_fwdg_h_k(GArgs a) {
     bf16x8 pg;
 #pragma unroll
     for (int k = 0; k < 8; ++k) pg[k] = (__bf16)0.0f;  // zero bits = fp16 zero
-    const int gbase = grad_lane_base(lane);
+    const int gbase = img_tr_base(lane);
     for (int64_t j0 = j_begin; j0 < j_end; j0 += kTile) {
       const bool has_next = j0 + kTile < j_end;
       const bool exc = (int64_t)next < j0 + kTile;
@@ -338,14 +338,14 @@ __device__ __forceinline__ void grad_half_gh(f32x16 (&gacc)[4], const bf16x8& g,
                                              const f32x16& S, int h, const float* m0, float o_m2s, float it2,
                                              uint32_t (&og)[4]) {
   bf16x8 bh, bl;
-  grad_rd(t.hi, base, ks, 0, bh);
-  if (GP == 2) grad_rd(t.lo, base, ks, 0, bl);
+  bh = img_read_tr(t.hi, base, ks, 0);
+  if (GP == 2) bl = img_read_tr(t.lo, base, ks, 0);
 #pragma unroll
   for (int nb = 0; nb < 4; ++nb) {
     bf16x8 nh = bh, nl = bl;
     if (nb < 3) {
-      grad_rd(t.hi, base, ks, nb + 1, nh);
-      if (GP == 2) grad_rd(t.lo, base, ks, nb + 1, nl);
+      nh = img_read_tr(t.hi, base, ks, nb + 1);
+      if (GP == 2) nl = img_read_tr(t.lo, base, ks, nb + 1);
     }
     if (GP == 2) gacc[nb] = mfma_h(g, bl, gacc[nb]);
     gacc[nb] = mfma_h(g, bh, gacc[nb]);
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
     lstore(0);
     __syncthreads();
     int cur = 0;
-    const int gbase = grad_lane_base(lane);
+    const int gbase = img_tr_base(lane);
     for (int t = 0; t < ntile; ++t) {
       const int64_t s0 = s_begin + (int64_t)t * kTile;
       const bool has_next = t + 1 < ntile;

@@ -18,22 +18,14 @@ namespace nce {
 //             rows (B, ds_read_b64_tr_b16 transposed reads of the same LDS image)
 // 3 x 32 cycles per 16 k per 32x32 tile instead of 8 x 64 for the fp32 MFMA (5.3x fewer
 // MFMA cycles). The log-sum-exp runs in base 2 (v_exp_f32 without the log2e multiply).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+using rsx::img_off, rsx::img_read_tr, rsx::img_tr_base;
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
 // s_waitcnt vmcnt(0) (expcnt, lgkmcnt left at their maxima): gfx9 encoding
 constexpr int kVmcnt0 = 0x0F70;
 
-// [32][128] bf16 image: 320-B rows plus a 16-B skew per 8-row group, i.e. byte offset
-// 320*row + 16*(row>>3) + 2*col. Conflict-free for the row reads (ds_read_b128, lane (c,h)
-// -> row c, chunk 8h+s), the transposed reads (ds_read_b64_tr_b16) and the staging stores
-// (ds_write_b128), and every read address is a per-lane base + an immediate (no per-step
-// address registers); checked with tools/lds_banks.py.
-constexpr int kImgRow = 160;  // bf16 elements per image row
-constexpr int kImgElems = 5120;
-__device__ __forceinline__ int img_off(int row, int col) { return row * kImgRow + 8 * (row >> 3) + col; }
+// [32][128] bf16 tile in the transposed-read image layout of rsx_x3.h
+constexpr int kImgElems = kTile * rsx::kImgRow;
 
 struct X3Tile {
   __bf16 hi[kImgElems];
@@ -42,12 +34,7 @@ struct X3Tile {
 
 __device__ __forceinline__ void split8(const float4& a, const float4& b, bf16x8& h, bf16x8& l) {
   const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 hk = (__bf16)f[k];
-    h[k] = hk;
-    l[k] = (__bf16)(f[k] - (float)hk);
-  }
+  split_x3(f, h, l);
 }
 
 // owner row (dims 64h .. 64h+63 on lane half h) -> hi/lo fragments of k-steps s = 0..7
@@ -68,7 +55,6 @@ __device__ __forceinline__ void load_owner_x3(bf16x8 (&uh)[8], bf16x8 (&ul)[8], 
 // Streamed operands are split once per call into global hi/lo bf16 images ([rows][128] each,
 // nce_split_k), so staging a tile is a plain copy: thread tid moves row tid>>3, 16-B chunks
 // tid&7 and 8+(tid&7) of both images (4 x 16-B loads, 4 ds_write_b128).
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 struct X3Src {
   const __bf16* hi;  // the streamed operand's hi/lo images [rows][128]
   const __bf16* lo;
@@ -144,36 +130,22 @@ __device__ __forceinline__ f32x16 dots_x3(const X3Tile& t, int c, int h, const b
   return acc;
 }
 
-// transposed reads of the gradient product: the lane's base offset (+ img_off(16ks + 8half, 32nb)
-// - img_off(0,0) per read) and the B fragment of step (ks, nb), two 4-row reads of one image
-__device__ __forceinline__ int grad_lane_base(int lane) {
-  const int q = (lane >> 2) & 3, p = lane & 3, h = lane >> 5, cb = (lane >> 4) & 1;
-  return img_off(4 * h + q, 16 * cb + 4 * p);
-}
-
-__device__ __forceinline__ void grad_rd(const __bf16* img, int base, int ks, int nb, bf16x8& out) {
-  const int o0 = base + img_off(16 * ks, 32 * nb), o1 = base + img_off(16 * ks + 8, 32 * nb);
-  const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
-  const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
-  out = __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
 // gacc[nb] += G^T X over the tile, G given as its hi/lo bf16 fragments (acc layout: streamed
 // row tile_row(r,h) in register r, owner on the lane; k-step ks takes registers 8ks..8ks+7,
 // i.e. streamed rows 16ks + 8(j>>2) + 4h + (j&3)). The B fragment is those rows of dims
 // 32nb + c, two transposed 4-row reads per image. Steps (ks, nb) are software-pipelined by one.
 __device__ __forceinline__ void grad_x3s(f32x16 (&gacc)[4], const bf16x8 (&gh)[2], const bf16x8 (&gl)[2],
                                          const X3Tile& t, int lane) {
-  const int base = grad_lane_base(lane);
+  const int base = img_tr_base(lane);
   bf16x8 bh, bl;
-  grad_rd(t.hi, base, 0, 0, bh);
-  grad_rd(t.lo, base, 0, 0, bl);
+  bh = img_read_tr(t.hi, base, 0, 0);
+  bl = img_read_tr(t.lo, base, 0, 0);
 #pragma unroll
   for (int step = 0; step < 8; ++step) {
     bf16x8 nh = bh, nl = bl;
     if (step < 7) {
-      grad_rd(t.hi, base, (step + 1) >> 2, (step + 1) & 3, nh);
-      grad_rd(t.lo, base, (step + 1) >> 2, (step + 1) & 3, nl);
+      nh = img_read_tr(t.hi, base, (step + 1) >> 2, (step + 1) & 3);
+      nl = img_read_tr(t.lo, base, (step + 1) >> 2, (step + 1) & 3);
     }
     const int ks = step >> 2, nb = step & 3;
     gacc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gl[ks], bh, gacc[nb], 0, 0, 0);
@@ -189,7 +161,6 @@ __device__ __forceinline__ void grad_x3s(f32x16 (&gacc)[4], const bf16x8 (&gh)[2
 // one pair conversion for hi, its two halves unpacked as fp32 by a shift and a mask, two
 // subtractions and one pair conversion for lo (the per-element form converted every element
 // twice and re-packed).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_pair(float a, float b, uint32_t& hi, uint32_t& lo) {
   const bf16x2 h = {(__bf16)a, (__bf16)b};
   hi = __builtin_bit_cast(uint32_t, h);
@@ -338,9 +309,6 @@ struct X3Prod {
     grad_x3s(gacc, gh, gl, t, lane);
   }
 };
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // fused forwards: the running max is raised only when a tile max exceeds it by more than 2^8
 constexpr float kLazyLog2 = 8.0f;

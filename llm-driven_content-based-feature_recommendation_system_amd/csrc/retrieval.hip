@@ -15,17 +15,16 @@
 // (score desc, index asc) and the first k are written. Ties therefore resolve to the lower
 // item index (documented tie-break; torch.topk leaves tie order unspecified).
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <math.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rsx::f32x16, rsx::ordered_key, rsx::ordered_key_inv, rsx::tile_row;
 constexpr int kD = 128;
 constexpr int kTile = 32;
 constexpr int kOwnRows = 128;
 constexpr int kLdsStride = kD + 4;
-
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 struct ScanArgs {
   const int* gate;  // nullptr, or: run only if *gate != 0 (the exact fallback of the fast path)
@@ -441,8 +440,7 @@ __global__ __launch_bounds__(256) void topk_final_k(const float* bs, const int* 
 //     fp32 and sorted by (e desc, index asc); the first k are written. A stream buffer overflow or
 //     more than kSelMax entries sends the query to the exact list-based kernels above (a device
 //     list of query ids; their grid exits past its count: no host sync).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using rsx::bf16x8, rsx::u32x4;
 constexpr int kImgStride = 272;   // bytes per staged item row: 256 + 16 (conflict-free ds_read_b128)
 constexpr int kStreamCap = 32;    // P3 entries per lane stream
 constexpr int kSelMax = 8192;     // P4 entries per query (LDS sort)
@@ -816,16 +814,7 @@ __device__ __forceinline__ float query_delta(const float* U, int64_t ldu, int64_
   return (nu * D + nd * W + 3.0f * nd * D + 0.000244140625f * nu * W) * 1.00001f + 1e-30f;
 }
 
-// Order-preserving uint key of a float (larger float <=> larger key).
-__device__ __forceinline__ unsigned okey(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float from_okey(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// K-th largest (1 <= K <= n) of v[0, n) in LDS, by an 8-bit radix select over okey (integer LDS
+// K-th largest (1 <= K <= n) of v[0, n) in LDS, by an 8-bit radix select over ordered_key (integer LDS
 // histograms; wave 0 finds each pass's digit with a 64-lane scan over 4 bins per lane). Replaces a
 // full bitonic sort where only the K-th value is needed. The passes start at the highest bit in
 // which the keys differ (block min / max first): scores of one query share their sign and top
@@ -835,7 +824,7 @@ __device__ float block_kth_largest(const float* v, int n, int K, int* hist, int*
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   unsigned kmin = 0xffffffffu, kmax = 0u;
   for (int t = threadIdx.x; t < n; t += blockDim.x) {
-    const unsigned k = okey(v[t]);
+    const unsigned k = ordered_key(v[t]);
     kmin = min(kmin, k);
     kmax = max(kmax, k);
   }
@@ -855,7 +844,7 @@ __device__ float block_kth_largest(const float* v, int n, int K, int* hist, int*
     kmax = max(kmax, red[4 + w]);
   }
   const unsigned diff = kmin ^ kmax;
-  if (diff == 0u) return from_okey(kmin);  // block-uniform: every key equal
+  if (diff == 0u) return ordered_key_inv(kmin);  // block-uniform: every key equal
   const int hb = 31 - __clz((int)diff);
   unsigned mask = ~((2u << hb) - 1u);       // hb = 31: 2u << 31 wraps to 0, mask 0
   unsigned prefix = kmin & mask;
@@ -866,7 +855,7 @@ __device__ float block_kth_largest(const float* v, int n, int K, int* hist, int*
     for (int t = threadIdx.x; t < 256; t += blockDim.x) hist[t] = 0;
     __syncthreads();
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
-      const unsigned k = okey(v[t]);
+      const unsigned k = ordered_key(v[t]);
       if ((k & mask) == prefix) atomicAdd(&hist[(k >> lo) & dm], 1);
     }
     __syncthreads();
@@ -904,7 +893,7 @@ __device__ float block_kth_largest(const float* v, int n, int K, int* hist, int*
     krem = sel[1];
     __syncthreads();  // sel / hist are rewritten by the next pass
   }
-  return from_okey(prefix);
+  return ordered_key_inv(prefix);
 }
 
 // P2: t_q = c_r - 2 delta_q (c_r: r-th best sampled candidate, r <= k (thr_rank); -inf if fewer
@@ -1089,13 +1078,13 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
       if (t < n && c == 0) ms[t] = e;
     }
   }
-  // rank-sort keys (n <= 512): okey(e) << 32 | ~id, so "beats" is one unsigned 64-bit compare
+  // rank-sort keys (n <= 512): ordered_key(e) << 32 | ~id, so "beats" is one unsigned 64-bit compare
   // (e desc, then id asc); padded to a multiple of two with 0 (beats nothing). ss is free now.
   unsigned long long* rk = reinterpret_cast<unsigned long long*>(ss);
   __syncthreads();  // every rescored ms[t] written
   if (n <= 512)
     for (int t = tid; t < ((n + 1) & ~1); t += 256)
-      rk[t] = t < n ? ((unsigned long long)okey(ms[t]) << 32) | (unsigned)(~mi[t]) : 0ull;
+      rk[t] = t < n ? ((unsigned long long)ordered_key(ms[t]) << 32) | (unsigned)(~mi[t]) : 0ull;
   __syncthreads();
   if (n <= 512) {
     // rank sort: an entry's output position is the number of entries that beat it under (e desc,

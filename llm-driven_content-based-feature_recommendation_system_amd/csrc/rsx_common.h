@@ -1,6 +1,7 @@
 // Shared device/host helpers for the recsys_amd C-ABI library (gfx950 / CDNA4 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stddef.h>
 
@@ -17,6 +18,19 @@ constexpr int kWave = 64;
 // same (seed, index).
 __device__ __forceinline__ uint32_t hash_u32(uint64_t seed, uint64_t idx) {
   uint32_t x = (uint32_t)idx ^ ((uint32_t)(idx >> 32) * 0x9E3779B1u) ^ (uint32_t)seed;
+  x ^= (uint32_t)(seed >> 32) * 0x85EBCA77u;
+  x ^= x >> 16;
+  x *= 0x85EBCA6Bu;
+  x ^= x >> 13;
+  x *= 0xC2B2AE35u;
+  x ^= x >> 16;
+  return x;
+}
+// hash_u32(seed, idx) for idx < 2^32, where the high-word term vanishes, in 32-bit ops only (the
+// GEMM epilogues' flat index m*N + n). The two must agree bit for bit there: the tests rebuild the
+// keep masks on the host from hash_u32's formula.
+__device__ __forceinline__ uint32_t hash_u32_idx32(uint64_t seed, uint32_t idx) {
+  uint32_t x = idx ^ (uint32_t)seed;
   x ^= (uint32_t)(seed >> 32) * 0x85EBCA77u;
   x ^= x >> 16;
   x *= 0x85EBCA6Bu;
@@ -60,6 +74,15 @@ __device__ __forceinline__ T wave_sum_width(T v, int width) {
 }
 
 __device__ __forceinline__ float fmax_nan(float a, float b) { return a > b ? a : b; }
+
+// GELU in its exact erf form (torch's default): gelu(z) = z Phi(z), gelu'(z) = Phi(z) + z phi(z)
+__device__ __forceinline__ float gelu_erf_cdf(float z) { return 0.5f * (1.0f + erff(z * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_erf(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_erf_grad(float z) {
+  const float cdf = gelu_erf_cdf(z);
+  const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
+  return cdf + z * pdf;
+}
 
 // compute units of the current device (grid sizing, speed only); 256 when the query fails
 inline int cu_count() {

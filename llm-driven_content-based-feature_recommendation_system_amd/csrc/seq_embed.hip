@@ -8,6 +8,7 @@
 // by D/4 lanes, each holding one float4, so every global access is 16 B/lane.
 // HBM-bound: per token the live bytes are base row + gathered rows + output row.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <mutex>
 #include <utility>
 #include <vector>
@@ -42,11 +43,10 @@ struct FwdArgs {
 // outstanding row loads. Casting to the global address space gives global loads (vmcnt only).
 // (through a native vector type: a float4 struct load through an address-space-1 pointer still
 // came out as a flat load)
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const f4v gf4v;
+typedef __attribute__((address_space(1))) const rsx::f32x4 gf4v;
 typedef __attribute__((address_space(1))) const int64_t gint64;
 __device__ __forceinline__ float4 ldg4(const float* p) {
-  const f4v v = *(gf4v*)(p);
+  const rsx::f32x4 v = *(gf4v*)(p);
   return make_float4(v.x, v.y, v.z, v.w);
 }
 __device__ __forceinline__ int64_t ldg8(const int64_t* p) { return *(gint64*)(p); }
@@ -644,8 +644,7 @@ __global__ __launch_bounds__(256) void seq_embed_bwd_k(BwdArgs a) {
 // bits), so every product is exact and only the fp32 accumulation rounds. The four waves of a
 // workgroup meet in LDS in wave order; one partial row [nkeys][D] per workgroup, folded by
 // seq_embed_bwd_reduce_k (deterministic).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using rsx::bf16x8, rsx::f32x16;
 
 struct KeyArgs {
   const float* dx;            // [T][128]
@@ -663,9 +662,8 @@ struct KeyArgs {
 
 __device__ __forceinline__ void split3(float x, __bf16& a, __bf16& b, __bf16& c) {
   a = (__bf16)x;
-  const float r = x - (float)a;
-  b = (__bf16)r;
-  c = (__bf16)(r - (float)b);
+  b = rsx::x3_lo(x, a);
+  c = rsx::x3_lo(x - (float)a, b);
 }
 
 // TP: tok_pos given (else r % L); NS: small tables (0..2). Compile-time so the loop has no

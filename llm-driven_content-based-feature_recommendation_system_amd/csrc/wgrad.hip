@@ -17,15 +17,14 @@
 // The A operand of token pair (2s, 2s+1) is dY[2s+h][n] on lane (n, h): a plain row read of
 // the token-major LDS tile, so no transpose is needed anywhere.
 #include "rsx_common.h"
+#include "rsx_x3.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using rsx::bf16x8, rsx::f32x16, rsx::img_off, rsx::kImgRow, rsx::tile_row, rsx::u32x4;
 constexpr int kTile = 128;   // output tile (n and k)
 constexpr int kStage = 32;   // tokens per LDS stage
-
-__device__ __forceinline__ int tile_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 struct WArgs {
   const float* dY;  // [T, ldy], columns 0..N-1
@@ -142,14 +141,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_k(WArgs a) {
 // bf16x3 loss). Both MFMA operands have the token axis as their k index, so both come from
 // ds_read_b64_tr_b16 transposed reads of the token-major images: lane (c, h) element j of
 // k-step ks is token 16ks + 8(j>>2) + 4h + (j&3), column c of the 32-wide block. Image
-// layout (as nce_mfma.h): 320-B rows + a 16-B skew per 8 rows, conflict-free for the
-// transposed reads. db is summed in fp32 from the staged registers.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-constexpr int kImgRow = 160;
-__device__ __forceinline__ int img_off(int row, int col) { return row * kImgRow + 8 * (row >> 3) + col; }
+// layout: the transposed-read image of rsx_x3.h. db is summed in fp32 from the staged registers.
 // One staged operand: STAGE tokens x 128 columns as bf16 hi/lo images (row stride 160 + 8 per 8 rows).
 template <int STAGE>
 struct X3Img {
@@ -162,12 +154,7 @@ struct X3Img {
 __device__ __forceinline__ void split8(const float4& a, const float4& b, u32x4& hi, u32x4& lo) {
   const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
   bf16x8 h, l;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const __bf16 hk = (__bf16)f[k];
-    h[k] = hk;
-    l[k] = (__bf16)(f[k] - (float)hk);
-  }
+  rsx::split_x3(f, h, l);
   hi = __builtin_bit_cast(u32x4, h);
   lo = __builtin_bit_cast(u32x4, l);
 }
@@ -249,14 +236,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_k(WArgs a) {
     }
   };
   // transposed fragment reads: lane (c, h) gets column 32nb + c of tokens 16ks + 8(j>>2) + 4h + (j&3)
+  // rsx::img_tr_base(lane), written out: through the helper (h recomputed from the lane) one v_or's operands swap
   const int q4 = (lane >> 2) & 3, p4 = lane & 3, cb = (lane >> 4) & 1;
   const int tbase = img_off(4 * h + q4, 16 * cb + 4 * p4);
-  auto rd = [&](const __bf16* img, int ks, int nb) -> bf16x8 {
-    const int o0 = tbase + img_off(16 * ks, 32 * nb), o1 = tbase + img_off(16 * ks + 8, 32 * nb);
-    const bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o0]));
-    const bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(&img[o1]));
-    return __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
-  };
   auto compute = [&](int cur) {
     if (!live) return;
 #pragma unroll
@@ -264,10 +246,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_x3_k(WArgs a) {
       bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        ah[i] = rd(sY[cur].hi, ks, 2 * wn + i);
-        al[i] = rd(sY[cur].lo, ks, 2 * wn + i);
-        bh[i] = rd(sX[cur].hi, ks, 2 * wk + i);
-        bl[i] = rd(sX[cur].lo, ks, 2 * wk + i);
+        ah[i] = rsx::img_read_tr(sY[cur].hi, tbase, ks, 2 * wn + i);
+        al[i] = rsx::img_read_tr(sY[cur].lo, tbase, ks, 2 * wn + i);
+        bh[i] = rsx::img_read_tr(sX[cur].hi, tbase, ks, 2 * wk + i);
+        bl[i] = rsx::img_read_tr(sX[cur].lo, tbase, ks, 2 * wk + i);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
