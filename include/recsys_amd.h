@@ -813,6 +813,49 @@ int rsx_tower_bwd(const void* const* p, const int64_t* dims, const float* fargs,
                   const void* arena, const float* out, const float* dout, void* const* grads, void* ws,
                   int64_t ws_bytes, void* stream);
 
+/* ---- LightGCL: graph propagation and the low-rank view (csrc/lightgcl.hip) -------------
+ * fp32, no float atomics, every sum in a fixed order: each call is bit-reproducible.
+ *
+ * rsx_spmm_norm: Y = alpha (R + A^ X) with A^ = diag(dinv) B diag(dinv), B the binary symmetric
+ * bipartite adjacency in CSR (row_ptr int64 [n+1], col int32 [nnz], ascending within a row) and
+ * dinv [n] = deg^-1/2 (0 for an isolated node). Replaces torch.sparse.mm(self.adj, x) of
+ * gnn_model/v1_lightgcl.py:171 (the normalised values of :123-135 are never stored) and, A^ being
+ * symmetric, its autograd backward; with R and alpha also the stack / mean of :166-173 (Horner).
+ *   y_r = alpha (R_r + dinv_r sum_{c in row r} dinv_c x_c), neighbours in CSR order.
+ * X [n, D] (ldx), R [n, D] (ldr) nullable, D in {64, 128}; Y must not alias X.
+ * rows NULL (then n_rows == 0): every row, Y [n, D] (ldy). A row with more than rsx_spmm_norm_chunk_len() neighbours is
+ * cut into chunks of that length (the last one shorter) summed by separate lane groups into the
+ * partial slots ws [n_chunks, D], which a second pass adds in chunk order. The plan is built once with
+ * the graph: long_rows int64 [n_long] ascending, part_off int64 [n_long + 1] (row l owns the slots
+ * [part_off[l], part_off[l+1])), chunk_beg / chunk_end int64 [n_chunks] (CSR positions of each slot's
+ * neighbours); ws >= rsx_spmm_norm_workspace_bytes(n_chunks, D).
+ * rows int64 [n_rows]: only those destinations, into the dense Y [n_rows, D] (ldy); repeats allowed, a
+ * row outside [0, n) gives zeros; R is still indexed by the graph row. The plan and ws are not used:
+ * a long row's chunks are summed one after the other by its lane group, the same arithmetic.
+ * Workgroup b takes the rsx_spmm_norm_rows_per_workgroup() destinations from b times that on. */
+int64_t rsx_spmm_norm_chunk_len(void);
+int64_t rsx_spmm_norm_rows_per_workgroup(void);
+int64_t rsx_spmm_norm_workspace_bytes(int64_t n_chunks, int64_t D);
+int rsx_spmm_norm(const int64_t* row_ptr, const int32_t* col, const float* dinv, int64_t n, const float* X,
+                  int64_t ldx, const float* R, int64_t ldr, int64_t D, float alpha, const int64_t* rows,
+                  int64_t n_rows, const int64_t* long_rows, const int64_t* part_off, const int64_t* chunk_beg,
+                  const int64_t* chunk_end, int64_t n_long, int64_t n_chunks, void* ws, int64_t ws_bytes,
+                  float* Y, int64_t ldy, void* stream);
+/* P [q, D] = V^T X over n rows, V [n, q] (ldv), X [n, D] (ldx), 1 <= q <= 8, D in {64, 128}: one
+ * streaming pass, replacing torch.matmul(self.V.t(), x_g) of gnn_model/v1_lightgcl.py:180. Workgroup b
+ * sums the tiles b, b + G, ... of rsx_lowrank_rows_per_workgroup() rows into slot b of ws (G = min(tiles,
+ * 512), a function of n alone); a second kernel adds the slots in slot order. n == 0 gives zeros.
+ * ws >= rsx_lowrank_proj_workspace_bytes(n, q, D). */
+int64_t rsx_lowrank_rows_per_workgroup(void);
+int64_t rsx_lowrank_proj_workspace_bytes(int64_t n, int64_t q, int64_t D);
+int rsx_lowrank_proj(const float* V, int64_t ldv, const float* X, int64_t ldx, int64_t n, int64_t q, int64_t D,
+                     void* ws, int64_t ws_bytes, float* P, void* stream);
+/* Y [n, D] (ldy) += V W, V [n, q] (ldv), W [q, D] contiguous, the terms of a row added for j = 0..q-1:
+ * the dense rank-q update torch.matmul(self.U, temp) of gnn_model/v1_lightgcl.py:182 as its own
+ * streaming pass (not fused into the last rsx_spmm_norm: the two views are separate outputs). */
+int rsx_lowrank_update(const float* V, int64_t ldv, const float* W, int64_t n, int64_t q, int64_t D, float* Y,
+                       int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 10  # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 11  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -168,6 +168,15 @@ _SIGS = {
     "rsx_binary_eval": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "rsx_group_eval_workspace_bytes": (c_i64, [c_i64]),
     "rsx_group_eval": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_spmm_norm_chunk_len": (c_i64, []),
+    "rsx_spmm_norm_rows_per_workgroup": (c_i64, []),
+    "rsx_spmm_norm_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rsx_spmm_norm": (c_i, [c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_f, c_p, c_i64, c_p, c_p, c_p, c_p,
+                            c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_p]),
+    "rsx_lowrank_rows_per_workgroup": (c_i64, []),
+    "rsx_lowrank_proj_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "rsx_lowrank_proj": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    "rsx_lowrank_update": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -1,0 +1,1 @@
+"""Drop-in mirrors of the reference gnn_model/ modules (LightGCL)."""

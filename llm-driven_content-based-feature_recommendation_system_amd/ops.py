@@ -2967,6 +2967,264 @@ def hnm_mine(u_norm, i_norm, target_ids, k, hnm_threshold=0.90, temperature=1.0,
 
 
 # ----------------------------------------------------------------------------------------
+# LightGCL (gnn_model/v1_lightgcl.py:163-186): normalised SpMM, low-rank view (csrc/lightgcl.hip)
+# The kernels' shape constants, for the graph's chunk plan (built without the library) and the tests:
+SPMM_CHUNK = 512          # rsx_spmm_norm_chunk_len(): neighbours per chunk of a long row
+SPMM_ROWS_PER_WG = 64     # rsx_spmm_norm_rows_per_workgroup()
+LOWRANK_ROWS_PER_WG = 256  # rsx_lowrank_rows_per_workgroup(): rows per tile of rsx_lowrank_proj
+LOWRANK_MAX_SLOTS = 512   # its partial slots: min(tiles, 512)
+
+
+def _rows16(fn, name, t):
+    """t as fp32 [n, D] rows the lightgcl kernels read: unit column stride, row stride a multiple of
+    4 floats, 16-B aligned (anything else is copied)."""
+    D = _rows2(fn, name, t)
+    if D not in (64, 128):
+        raise ValueError(f"{fn}: {name} must have 64 or 128 columns, got {D}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < D or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t
+
+
+def spmm_norm(adj, X, R=None, alpha=1.0, rows=None, out=None):
+    """alpha (R + A^ X) for the graph adj (gnn_model.v1_lightgcl.NormAdjacency: row_ptr, col, dinv and
+    the long-row chunk plan), A^ = diag(dinv) B diag(dinv) never stored. rows None: every row, [n, D]
+    (into out when given); rows int64 [m]: those destination rows only, dense [m, D]. No autograd
+    (lightgcl_propagate is the differentiable form); deterministic."""
+    fn = "spmm_norm"
+    X = _rows16(fn, "X", X)
+    N.ensure_device(X)
+    n, D = adj.n, X.shape[1]
+    if X.shape[0] != n or adj.row_ptr.device != X.device:
+        raise ValueError(f"{fn}: X must be [{n}, D] on the graph's device {adj.row_ptr.device}")
+    if R is not None:
+        R = _rows16(fn, "R", R)
+        if R.shape != X.shape or R.device != X.device:
+            raise ValueError(f"{fn}: R must match X")
+    if rows is not None:
+        rows = _c(_index(fn, "rows", rows, X))
+        m = rows.numel()
+    else:
+        m = n
+    if out is None:
+        out = torch.empty(m, D, device=X.device, dtype=torch.float32)
+    elif out.shape != (m, D) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != X.device:
+        raise ValueError(f"{fn}: out must be a contiguous fp32 [{m}, {D}] tensor on X's device")
+    if m == 0:   # an empty rows list has no storage: its null pointer would read as "every row"
+        return out
+    if out.data_ptr() == X.data_ptr():
+        raise ValueError(f"{fn}: out must not alias X")
+    ws = adj.workspace(D) if rows is None else None
+    with timed("lightgcl/spmm_norm"):
+        rc = N.lib().rsx_spmm_norm(N.ptr(adj.row_ptr), N.ptr(adj.col), N.ptr(adj.dinv), n, N.ptr(X), X.stride(0),
+                                   N.ptr(R), R.stride(0) if R is not None else 0, D, float(alpha), N.ptr(rows),
+                                   m if rows is not None else 0, N.ptr(adj.long_rows), N.ptr(adj.part_off),
+                                   N.ptr(adj.chunk_beg), N.ptr(adj.chunk_end), adj.long_rows.numel(),
+                                   adj.chunk_beg.numel(), N.ptr(ws), ws.numel() if ws is not None else 0,
+                                   N.ptr(out), D, N.stream())
+    N.check(rc, fn)
+    return out
+
+
+def lowrank_proj(V, X):
+    """V^T X [q, D] for V [n, q] (q <= 8) and X [n, D] in one streaming pass; deterministic."""
+    fn = "lowrank_proj"
+    X = _rows16(fn, "X", X)
+    N.ensure_device(X)
+    _f32(fn, "V", V, X)
+    if V.dim() != 2 or V.shape[0] != X.shape[0] or not 1 <= V.shape[1] <= 8:
+        raise ValueError(f"{fn}: V must be [{X.shape[0]}, q <= 8], got {tuple(V.shape)}")
+    V = _c(V)
+    n, q, D = X.shape[0], V.shape[1], X.shape[1]
+    nws = N.lib().rsx_lowrank_proj_workspace_bytes(n, q, D)
+    ws = torch.empty(nws, device=X.device, dtype=torch.uint8)
+    P = torch.empty(q, D, device=X.device, dtype=torch.float32)
+    with timed("lightgcl/lowrank_proj"):
+        rc = N.lib().rsx_lowrank_proj(N.ptr(V), q, N.ptr(X), X.stride(0), n, q, D, N.ptr(ws), nws, N.ptr(P),
+                                      N.stream())
+    N.check(rc, fn)
+    return P
+
+
+def lowrank_update_(Y, V, W):
+    """Y += V W in place, Y [n, D] contiguous, V [n, q], W [q, D]; deterministic."""
+    fn = "lowrank_update_"
+    D = _rows2(fn, "Y", Y)
+    N.ensure_device(Y)
+    _f32(fn, "V", V, Y)
+    _f32(fn, "W", W, Y)
+    if D not in (64, 128) or not Y.is_contiguous():
+        raise ValueError(f"{fn}: Y must be contiguous with 64 or 128 columns")
+    if V.dim() != 2 or V.shape[0] != Y.shape[0] or not 1 <= V.shape[1] <= 8 or W.shape != (V.shape[1], D):
+        raise ValueError(f"{fn}: V must be [{Y.shape[0]}, q <= 8] and W [q, {D}]")
+    V, W = _c(V), _c(W)
+    with timed("lightgcl/lowrank_update"):
+        rc = N.lib().rsx_lowrank_update(N.ptr(V), V.shape[1], N.ptr(W), Y.shape[0], V.shape[1], D, N.ptr(Y), D,
+                                        N.stream())
+    N.check(rc, fn)
+    return Y
+
+
+def _propagate(E, adj, n_layers, rows=None):
+    """(1/(L+1)) sum_{k<=L} A^^k E by Horner, T <- E + A^ T: one rsx_spmm_norm per layer with R = E, the
+    last one scaled (and restricted to `rows` when given); the output and one scratch [n, D] alternate
+    as T."""
+    if n_layers == 0:
+        return E.clone() if rows is None else E[rows]
+    bufs = [None, None]
+    T = E
+    for j in range(n_layers):
+        if j == n_layers - 1:
+            return spmm_norm(adj, T, R=E, alpha=1.0 / (n_layers + 1), rows=rows,
+                             out=bufs[0] if rows is None else None)
+        k = (n_layers - 1 - j) % 2
+        if bufs[k] is None:
+            bufs[k] = torch.empty(E.shape[0], E.shape[1], device=E.device, dtype=torch.float32)
+        T = spmm_norm(adj, T, R=E, out=bufs[k])
+
+
+class _LightGCLPropagate(torch.autograd.Function):
+    """A^ is symmetric, so the backward is the forward on the gradient; nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, E, adj, n_layers):
+        ctx.adj, ctx.n_layers = adj, n_layers
+        return _propagate(E, adj, n_layers)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _propagate(_rows16("lightgcl_propagate", "grad", g), ctx.adj, ctx.n_layers), None, None
+
+
+def lightgcl_propagate(E, adj, n_layers, rows=None):
+    """LightGCL's local view (gnn_model/v1_lightgcl.py:166-173): the mean of E, A^ E, ..., A^^L E.
+    rows (in-range int64, no autograd): only those rows of it, the last layer computed for them alone."""
+    if int(n_layers) < 0:
+        raise ValueError("lightgcl_propagate: n_layers must be >= 0")
+    E = _rows16("lightgcl_propagate", "E", E)
+    N.ensure_device(E)
+    if rows is not None:
+        with torch.no_grad():
+            return _propagate(E, adj, int(n_layers), _c(_index("lightgcl_propagate", "rows", rows, E)))
+    return _LightGCLPropagate.apply(E, adj, int(n_layers))
+
+
+def _scatter_add_sorted(dst, src, idx):
+    """dst[idx[k]] += src[k] with repeated indices summed in a fixed order (ops.sort_segments' two-level
+    plan and rsx_segment_sum_rows: no atomics). dst [rows, D] contiguous, src [m, D] contiguous."""
+    if idx.numel() == 0:
+        return
+    D = dst.shape[1]
+    perm, cb, chunk_ids, ch_off, uniq = sort_segments(idx)
+    part = torch.empty(chunk_ids.numel(), D, device=dst.device, dtype=torch.float32)
+    rc = N.lib().rsx_segment_sum_rows(N.ptr(src), D, N.ptr(perm), N.ptr(cb), N.ptr(chunk_ids), chunk_ids.numel(), D,
+                                      None, -1, N.ptr(part), D, 0, N.stream())
+    N.check(rc, "segment_sum_rows(chunks)")
+    rc = N.lib().rsx_segment_sum_rows(N.ptr(part), D, N.ptr(chunk_ids), N.ptr(ch_off), N.ptr(uniq), uniq.numel(), D,
+                                      None, -1, N.ptr(dst), D, 1, N.stream())
+    N.check(rc, "segment_sum_rows(rows)")
+
+
+class _GatherRowsSorted(torch.autograd.Function):
+    """src[idx] whose backward sums repeated indices through the sorted segment sums (deterministic),
+    where _GatherRows scatters them with float atomics."""
+
+    @staticmethod
+    def forward(ctx, src, idx):
+        n, D = idx.numel(), src.shape[1]
+        out = torch.empty(n, D, device=src.device, dtype=torch.float32)
+        rc = N.lib().rsx_gather_rows(N.ptr(src), src.stride(0), N.ptr(idx), n, D, 0, 0.0, N.ptr(out), None, N.stream())
+        N.check(rc, "gather_rows")
+        ctx.rows = src.shape[0]
+        ctx.save_for_backward(idx)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        dsrc = torch.zeros(ctx.rows, dy.shape[1], device=dy.device, dtype=torch.float32)
+        _scatter_add_sorted(dsrc, _c(dy), idx)
+        return dsrc, None
+
+
+def gather_rows_sorted(src, idx):
+    """src[idx] for fp32 rows of 64 / 128 columns and in-range int64 idx; the gradient of src is summed
+    per row in a fixed order (a host synchronisation in the backward: ops.sort_segments)."""
+    src = _rows16("gather_rows_sorted", "src", src)
+    N.ensure_device(src)
+    return _GatherRowsSorted.apply(src, _c(_index("gather_rows_sorted", "idx", idx, src)))
+
+
+def _small_matmul(K, C):
+    """K [q, q] @ C [q, D] as a broadcast product and a sum (fixed order; q <= 8)."""
+    return (K.unsqueeze(2) * C.unsqueeze(0)).sum(1)
+
+
+class _LightGCLGlobalRows(torch.autograd.Function):
+    """global_final[rows] of gnn_model/v1_lightgcl.py:175-185 reassociated: with P = V^T E, C_1 = S.P,
+    C_{j+1} = S.(K C_j), K = V^T U, it is (E[rows] + U[rows] sum_j C_j) / (L + 1). Nothing of the
+    graph's size is saved or formed but the gradient of E. rows None: every row (the full view)."""
+
+    @staticmethod
+    def forward(ctx, E, view, rows, n_layers):
+        inv = 1.0 / (n_layers + 1)
+        S = view.S.unsqueeze(1)
+        n, D = (rows.numel() if rows is not None else E.shape[0]), E.shape[1]
+        out = torch.empty(n, D, device=E.device, dtype=torch.float32)
+        rc = N.lib().rsx_gather_rows(N.ptr(E), E.stride(0), N.ptr(rows), n, D, 0, 0.0, N.ptr(out), None, N.stream())
+        N.check(rc, "gather_rows")
+        out *= inv
+        Ur = view.U[rows] if rows is not None else view.U
+        if n_layers > 0:
+            C = S * lowrank_proj(view.V, E)
+            W = C
+            for _ in range(n_layers - 1):
+                C = S * _small_matmul(view.K, C)
+                W = W + C
+            lowrank_update_(out, Ur, W * inv)
+        ctx.view, ctx.n_layers, ctx.shape = view, n_layers, E.shape
+        ctx.rows = rows
+        ctx.save_for_backward(Ur)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (Ur,) = ctx.saved_tensors
+        view, L, rows = ctx.view, ctx.n_layers, ctx.rows
+        g = _c(g) * (1.0 / (L + 1))
+        if rows is None:
+            dE = g
+        else:
+            dE = torch.zeros(ctx.shape, device=g.device, dtype=torch.float32)
+            _scatter_add_sorted(dE, g, rows)
+        if L > 0 and g.shape[0] > 0:
+            S = view.S.unsqueeze(1)
+            dW = lowrank_proj(Ur, g)          # d(sum_j C_j) = U[rows]^T g
+            dC = dW
+            Kt = view.K.t()
+            for _ in range(L - 1):            # dC_j = dW + K^T (S . dC_{j+1})
+                dC = dW + _small_matmul(Kt, S * dC)
+            lowrank_update_(dE, view.V, S * dC)
+        return dE, None, None, None
+
+
+def lightgcl_global_rows(E, view, rows, n_layers):
+    """The low-rank (SVD) view's rows of LightGCL without forming the [n, D] view. view: U [n, q],
+    S [q], V [n, q] and K = V^T U [q, q] (gnn_model.v1_lightgcl.LowRankView); rows: in-range int64
+    (repeats allowed), or None for the whole [n, D] view."""
+    fn = "lightgcl_global_rows"
+    if int(n_layers) < 0:
+        raise ValueError(f"{fn}: n_layers must be >= 0")
+    E = _rows16(fn, "E", E)
+    N.ensure_device(E)
+    if view.U.shape[0] != E.shape[0] or view.U.device != E.device:
+        raise ValueError(f"{fn}: the view's factors must have E's {E.shape[0]} rows on its device")
+    if rows is not None:
+        rows = _c(_index(fn, "rows", rows, E))
+    return _LightGCLGlobalRows.apply(E, view, rows, int(n_layers))
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 
