@@ -856,6 +856,50 @@ int rsx_lowrank_proj(const float* V, int64_t ldv, const float* X, int64_t ldx, i
 int rsx_lowrank_update(const float* V, int64_t ldv, const float* W, int64_t n, int64_t q, int64_t D, float* Y,
                        int64_t ldy, void* stream);
 
+/* ---- Distillation of dot-product scores into unit vectors (csrc/distill.hip) -----------
+ * Replaces gnn_model/distill_mag_to_cos_l2.py: MagnitudeEncoder = Linear(64, 128) + LeakyReLU(slope) +
+ * Dropout(p) + Linear(128, 64) + F.normalize (:16-35), and one step of train_projector (:63-103) as two
+ * launches. w1 [128, 64], b1 [128], w2 [64, 128], b2 [64], logit_scale [1], all on the device, 16-B
+ * aligned matrices. Exact fp32 products (f32-input MFMA), no float atomics, every sum in a fixed
+ * order: each call is bit-reproducible. With the stacked rows X = [U[users]; I[items]] ([2B, 64]):
+ *   P = X W1^T + b1; A = P > 0 ? P : slope P; H = A keep / (1 - p), keep from (seed, r 128 + c) over the
+ *   stacked row r; Z = H W2^T + b2; n = max(|Z_r|, eps); Y = Z / n; s_k = <Y_k, Y_{B+k}> exp(logit_scale);
+ *   t_k = <X_k, X_{B+k}>; loss = mean_k (s_k - t_k)^2; no gradient to X.
+ * rsx_distill_rows_per_workgroup(): the pairs of one tile T (a tile of the forward is 2 T rows).
+ * rsx_distill_slots(B): the workgroups and partial slots of a step, min(ceil(B / T), 256); workgroup g
+ * takes the tiles g, g + slots, ... ws >= rsx_distill_workspace_bytes(B), 8-B aligned.
+ *
+ * rsx_magnitude_encode: Y [N, 64] (ldy) = the forward of X [N, 64] (ldx) without dropout; the same
+ * arithmetic as the step's forward at p = 0, bit for bit. N == 0 does nothing.
+ *
+ * rsx_distill_grads: gather, forward, loss and backward of the B pairs (users[k], items[k]) (int64) over
+ * the tables [n_users, 64] (ldu) / [n_items, 64] (ldi) into ws: per workgroup one slot of the 16,577
+ * gradients in parameter order (w1, b1, w2, b2, logit_scale) and a double loss partial. A pair with an
+ * id outside its table sets flag[0] = 1 (the caller zeroes it) and contributes nothing; the mean still
+ * divides by B. Nullable outputs: student_scores / teacher_scores [B] (s_k, t_k) and rows_out [2B, 64]
+ * (Y, 16-B aligned, for tests).
+ *
+ * rsx_distill_apply: every gradient = its slots added in slot order; grads [16,577] (nullable) and
+ * loss [1] double (nullable) written; update != 0 applies torch.optim.Adam's step number `step`
+ * (>= 1; no weight decay, bias-corrected, double scalars, float state) to the five parameters with the
+ * flat moments exp_avg / exp_avg_sq [16,577] in parameter order. */
+int64_t rsx_distill_rows_per_workgroup(void);
+int64_t rsx_distill_slots(int64_t B);
+int64_t rsx_distill_workspace_bytes(int64_t B);
+int rsx_magnitude_encode(const float* X, int64_t ldx, int64_t N, const float* w1, const float* b1,
+                         const float* w2, const float* b2, float slope, float eps, float* Y, int64_t ldy,
+                         void* stream);
+int rsx_distill_grads(const float* user_table, int64_t ldu, int64_t n_users, const float* item_table,
+                      int64_t ldi, int64_t n_items, const int64_t* users, const int64_t* items, int64_t B,
+                      const float* w1, const float* b1, const float* w2, const float* b2,
+                      const float* logit_scale, float slope, float p_drop, uint64_t seed, float eps, void* ws,
+                      int64_t ws_bytes, float* student_scores, float* teacher_scores, float* rows_out,
+                      int32_t* flag, void* stream);
+int rsx_distill_apply(const void* ws, int64_t ws_bytes, int64_t B, float* w1, float* b1, float* w2, float* b2,
+                      float* logit_scale, float* exp_avg, float* exp_avg_sq, float* grads, double* loss,
+                      int update, double lr, double beta1, double beta2, double eps, int64_t step,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 11  # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 12 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -177,6 +177,14 @@ _SIGS = {
     "rsx_lowrank_proj_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "rsx_lowrank_proj": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
     "rsx_lowrank_update": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p]),
+    "rsx_distill_rows_per_workgroup": (c_i64, []),
+    "rsx_distill_slots": (c_i64, [c_i64]),
+    "rsx_distill_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_magnitude_encode": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_i64, c_p]),
+    "rsx_distill_grads": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_f,
+                                c_f, c_u64, c_f, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_distill_apply": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_d, c_d, c_d,
+                                c_d, c_i64, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

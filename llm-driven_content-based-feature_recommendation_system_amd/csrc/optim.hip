@@ -13,6 +13,7 @@
 // HBM traffic per element: 4 B (norm) + 28 B read/write (p, g, m, v; g written only when the
 // coefficient is < 1): memory-bound, ~50 us for the 12.5M parameters of the headline step.
 #include "rsx_common.h"
+#include "rsx_adam.h"
 #include "recsys_amd.h"
 
 #include <math.h>
@@ -82,15 +83,7 @@ __global__ __launch_bounds__(kThreads) void clip_sumsq_k(OptChunk c, float* __re
   if (threadIdx.x == 0) partials[c.part0 + blockIdx.x] = s;
 }
 
-__device__ __forceinline__ void adam_elem(float& p, float& g, float& m, float& v, float coef, double lr, double wd,
-                                          double b1, double b2, double eps, double step_size, double bc2_sqrt) {
-  g = g * coef;
-  if (wd != 0.0) p = (float)(p - lr * wd * p);
-  m = (float)(b1 * m + (1.0 - b1) * g);
-  v = (float)(b2 * v + (1.0 - b2) * g * g);
-  const float denom = (float)(sqrtf(v) / bc2_sqrt + eps);
-  p -= (float)step_size * m / denom;
-}
+using rsx::adam_elem;  // rsx_adam.h
 
 __global__ __launch_bounds__(kThreads) void adamw_apply_k(OptChunk c, const float* __restrict__ partials, int n_part,
                                                           float max_norm, float* __restrict__ norm_out) {

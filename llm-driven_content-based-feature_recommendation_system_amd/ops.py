@@ -3225,6 +3225,152 @@ def lightgcl_global_rows(E, view, rows, n_layers):
 
 
 # ----------------------------------------------------------------------------------------
+# Distillation of dot-product scores into unit vectors (gnn_model/distill_mag_to_cos_l2.py,
+# csrc/distill.hip): MagnitudeEncoder's forward and one fused training step
+DISTILL_WIDTHS = (64, 128, 64)      # input, hidden, output width of the kernels
+DISTILL_PARAMS = 128 * 64 + 128 + 64 * 128 + 64 + 1   # w1, b1, w2, b2, logit_scale: 16,577
+
+
+def distill_supported(input_dim, hidden_dim, output_dim):
+    """None when the distillation kernels cover the widths, else the text naming the limit."""
+    if (int(input_dim), int(hidden_dim), int(output_dim)) != DISTILL_WIDTHS:
+        return (f"the MagnitudeEncoder kernels need the widths (input, hidden, output) = {DISTILL_WIDTHS} "
+                f"(got {(int(input_dim), int(hidden_dim), int(output_dim))})")
+    return None
+
+
+def _distill_weights(fn, w1, b1, w2, b2, ref):
+    """The encoder's four tensors: fp32 on ref's device, Linear shapes, the kernels' widths."""
+    for name, t in (("w1", w1), ("w2", w2)):
+        _rows2(fn, name, t)
+        _f32(fn, name, t, ref)
+    if w2.shape[1] != w1.shape[0]:
+        raise ValueError(f"{fn}: w2 {tuple(w2.shape)} does not follow w1 {tuple(w1.shape)}")
+    _f32_vec(fn, "b1", b1, w1.shape[0], ref)
+    _f32_vec(fn, "b2", b2, w2.shape[0], ref)
+    why = distill_supported(w1.shape[1], w1.shape[0], w2.shape[0])
+    if why:
+        raise NotImplementedError(f"{fn}: {why}")
+
+
+def _rows64(fn, name, t):
+    """t as fp32 [n, 64] rows the distillation kernels read (unit column stride, row stride a multiple
+    of 4 floats, 16-B aligned; anything else is copied)."""
+    D = _rows2(fn, name, t)
+    if D != DISTILL_WIDTHS[0]:
+        raise ValueError(f"{fn}: {name} must have {DISTILL_WIDTHS[0]} columns, got {D}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < D or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t
+
+
+def magnitude_encode(x, w1, b1, w2, b2, slope=0.2, eps=1e-12):
+    """F.normalize(Linear(w2, b2)(leaky_relu(Linear(w1, b1)(x), slope)), eps=eps) over the rows of x
+    [N, 64] in one kernel (MagnitudeEncoder's eval forward): [N, 64]. No autograd; deterministic; the
+    arithmetic of distill_step's forward at p = 0, bit for bit."""
+    fn = "magnitude_encode"
+    x = _rows64(fn, "x", x)
+    _distill_weights(fn, w1, b1, w2, b2, x)
+    if not float(eps) > 0.0:
+        raise ValueError(f"{fn}: eps must be positive (got {eps})")
+    N.ensure_device(x)
+    w1, b1, w2, b2 = (_c(t.detach()) for t in (w1, b1, w2, b2))
+    y = torch.empty(x.shape[0], DISTILL_WIDTHS[2], device=x.device, dtype=torch.float32)
+    with timed("distill/encode"):
+        rc = N.lib().rsx_magnitude_encode(N.ptr(x), x.stride(0), x.shape[0], N.ptr(w1), N.ptr(b1), N.ptr(w2),
+                                          N.ptr(b2), float(slope), float(eps), N.ptr(y), y.stride(0), N.stream())
+    N.check(rc, fn)
+    return y
+
+
+class DistillStep:
+    """What distill_step returns: loss (0-d float64 device tensor) and, on request, grads (w1, b1, w2,
+    b2, logit_scale, views of one flat buffer), student_scores [B] (cos exp(logit_scale)),
+    teacher_scores [B] (<u, i>) and rows [2B, 64] (the normalised student rows, users first); flag is the
+    int32 [1] device flag the kernel sets for an id outside its table."""
+
+    def __init__(self, loss, flag, grads=None, student_scores=None, teacher_scores=None, rows=None):
+        self.loss, self.flag, self.grads = loss, flag, grads
+        self.student_scores, self.teacher_scores, self.rows = student_scores, teacher_scores, rows
+
+
+def distill_step(user_table, item_table, users, items, w1, b1, w2, b2, logit_scale, slope=0.2, p_drop=0.0, seed=0,
+                 eps=1e-12, update=True, exp_avg=None, exp_avg_sq=None, step=1, lr=1e-3, betas=(0.9, 0.999),
+                 adam_eps=1e-8, return_grads=False, return_scores=False, return_rows=False, flag=None):
+    """One step of the projector's distillation over raw tensors in two launches, no host
+    synchronisation: the rows user_table[users] / item_table[items] ([n, 64] fp32 tables, B int64 ids
+    each) through the encoder (w1 [128, 64], b1, w2 [64, 128], b2, dropout (p_drop, seed) on the hidden
+    layer), loss = mean_k (cos_k exp(logit_scale) - <u_k, i_k>)^2 and its gradients (none to the tables).
+    update=True applies torch.optim.Adam's step number `step` (>= 1) in place to the five parameters and
+    the flat moments exp_avg / exp_avg_sq [16,577] (parameter order); update=False computes the loss and
+    the gradients only. A pair with an id outside its table sets flag (int32 [1], created zeroed when
+    not given) and contributes nothing; the mean still divides by B. Returns a DistillStep."""
+    fn = "distill_step"
+    user_table = _rows64(fn, "user_table", user_table)
+    item_table = _rows64(fn, "item_table", item_table)
+    if item_table.device != user_table.device:
+        raise RuntimeError(f"{fn}: item_table is on {item_table.device}, expected {user_table.device}")
+    users = _index(fn, "users", users, user_table)
+    items = _index(fn, "items", items, user_table, users.numel())
+    B = users.numel()
+    if B < 1:
+        raise ValueError(f"{fn} needs at least one pair")
+    _distill_weights(fn, w1, b1, w2, b2, user_table)
+    _f32_vec(fn, "logit_scale", logit_scale, 1, user_table)
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError(f"{fn}: p_drop must be in [0, 1) (got {p_drop})")
+    if not float(eps) > 0.0:
+        raise ValueError(f"{fn}: eps must be positive (got {eps})")
+    if update:
+        if exp_avg is None or exp_avg_sq is None:
+            raise ValueError(f"{fn}: update=True needs exp_avg and exp_avg_sq")
+        _f32_vec(fn, "exp_avg", exp_avg, DISTILL_PARAMS, user_table)
+        _f32_vec(fn, "exp_avg_sq", exp_avg_sq, DISTILL_PARAMS, user_table)
+        if int(step) < 1:
+            raise ValueError(f"{fn}: step counts from 1 (got {step})")
+        for name, t in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("logit_scale", logit_scale),
+                        ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            if not t.is_contiguous():
+                raise ValueError(f"{fn}: {name} is updated in place and must be contiguous")
+    if flag is not None and (flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != user_table.device):
+        raise ValueError(f"{fn}: flag must be an int32 tensor of one element on the tables' device")
+    N.ensure_device(user_table)
+    dev, lib, st = user_table.device, N.lib(), N.stream()
+    users, items = _c(users), _c(items)
+    w1, b1, w2, b2, ls = (_c(t.detach()) for t in (w1, b1, w2, b2, logit_scale))
+    if flag is None:
+        flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    nws = lib.rsx_distill_workspace_bytes(B)
+    ws = torch.empty(nws // 8, device=dev, dtype=torch.float64)
+    loss = torch.empty((), device=dev, dtype=torch.float64)
+    f32 = dict(device=dev, dtype=torch.float32)
+    flat = torch.empty(DISTILL_PARAMS, **f32) if return_grads else None
+    s_out = torch.empty(B, **f32) if return_scores else None
+    t_out = torch.empty(B, **f32) if return_scores else None
+    rows = torch.empty(2 * B, DISTILL_WIDTHS[2], **f32) if return_rows else None
+    with timed("distill/grads"):
+        rc = lib.rsx_distill_grads(N.ptr(user_table), user_table.stride(0), user_table.shape[0], N.ptr(item_table),
+                                   item_table.stride(0), item_table.shape[0], N.ptr(users), N.ptr(items), B,
+                                   N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(ls), float(slope),
+                                   float(p_drop), int(seed), float(eps), N.ptr(ws), nws, N.ptr(s_out), N.ptr(t_out),
+                                   N.ptr(rows), N.ptr(flag), st)
+    N.check(rc, "distill_grads")
+    with timed("distill/apply"):
+        rc = lib.rsx_distill_apply(N.ptr(ws), nws, B, N.ptr(w1), N.ptr(b1), N.ptr(w2), N.ptr(b2), N.ptr(ls),
+                                   N.ptr(exp_avg) if update else None, N.ptr(exp_avg_sq) if update else None,
+                                   N.ptr(flat), N.ptr(loss), 1 if update else 0, float(lr), float(betas[0]),
+                                   float(betas[1]), float(adam_eps), int(step) if update else 0, st)
+    N.check(rc, "distill_apply")
+    grads = None
+    if flat is not None:
+        grads, o = [], 0
+        for t in (w1, b1, w2, b2, ls):
+            grads.append(flat[o:o + t.numel()].view(t.shape))
+            o += t.numel()
+    return DistillStep(loss, flag, grads, s_out, t_out, rows)
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 
