@@ -900,6 +900,55 @@ int rsx_distill_apply(const void* ws, int64_t ws_bytes, int64_t B, float* w1, fl
                       int update, double lr, double beta1, double beta2, double eps, int64_t step,
                       void* stream);
 
+/* ---- Late fusion of two retrievers: pool, fuse, hits (csrc/ensemble.hip) ---------------
+ * Replaces the per-batch body of tower_code/mined_inference.py's evaluators:
+ * evaluate_weighted_score_ensemble (:1103-1189), evaluate_rrf_ensemble (:1330-1410) and the hit test
+ * of evaluate_multi_vector_ensemble (:926-953). Floats compare through the score key (-0.0 and +0.0
+ * tie); every input float must be finite (a NaN or an infinity is ordered by its bits, not refused).
+ * No float atomics; each call is bit-reproducible.
+ *
+ * rsx_select_topk_rows: the k largest of each row of S [Q, N] (row stride ld >= N floats), replacing
+ * torch.topk(scores, k=pool_k, dim=1) of :1104 / :1108. 1 <= k <= min(N, 2048), N <= 2^30. idx [Q, k]
+ * int32 and val [Q, k] in the order (value descending, index ascending): among equal values the lower
+ * indices are taken, and come first. One workgroup per row: radix select of the k-th key (four
+ * 8-bit passes over the row), a counting and a collecting pass, a sort of the k pairs in LDS.
+ *
+ * rsx_fuse_rank: per user q the fusion of retrievers a and b over the pool cand [Q, C] int32 (corpus
+ * rows in [0, NI), 1 <= C <= 2048, the reference's cat([pool_a, pool_b]), duplicates kept). ua [Q, Da]
+ * (ldua), Ia [NI, Da] (ldia), ub [Q, Db] (ldub), Ib [NI, Db] (ldib); Da, Db in {64, 128}; rows 16-B
+ * aligned, strides multiples of 4. wa / wb [A] (HOST arrays, A <= 32): the weights of each alpha, for
+ * the reference wa = float(alpha), wb = float(1.0 - alpha). ks [nK] (HOST, nK <= 16, ascending,
+ * 1 <= ks[0], ks[nK-1] <= cut); cut in [1, C], for the reference min(C, max_k + 20) (:1170).
+ * truth_off int64 [Q+1] / truth int32 [n_truth]: user q's items truth[truth_off[q] .. truth_off[q+1]),
+ * ascending and distinct, any length (offsets are clamped into [0, n_truth]).
+ * The fp32 operations, in this order and uncontracted:
+ *   sa[c] = <ua_q, Ia[cand[c]]>, sb[c] = <ub_q, Ib[cand[c]]>        (summation order unspecified)
+ *   RSX_FUSE_MINMAX  na = (sa - min sa) / ((max sa - min sa) + 1e-9f), likewise nb            (:1139-1145)
+ *   RSX_FUSE_RRF     ra = 0-based rank of entry c by (key(sa) descending, c ascending),
+ *                    na = 1.0f / ((k_rrf + ra) + 1.0f), likewise nb                          (:1358-1380)
+ *   per alpha a      f = wa[a] * na + wb[a] * nb (each product rounded, then the sum); the entries in
+ *                    the order (key(f) descending, c ascending); the first `cut` of them; their corpus
+ *                    ids; later repeats of an id dropped (:1170-1183). The cut precedes the removal
+ *                    of repeats, as in the reference: an item first seen beyond `cut` is a miss.
+ *   hits [Q, A] int32: bit j set when one of the first ks[j] ids of that list is in the user's truth.
+ * Optional outputs (nullable): lists [Q, A, ks[nK-1]] int32, the list's head padded with -1; sa / sb
+ * [Q, C]. A pool entry outside [0, NI) sets flag[0] |= 1 (int32, the caller zeroes it) and scores 0.
+ *
+ * rsx_first_hit: out [Q] int32 = the smallest j with lists[q, j] (int32 [Q, K], row stride ld) in user
+ * q's truth (CSR as above), or K: the hit test `actual & set(indices[u, :n])` of :944-952 is
+ * out[q] < n. */
+enum { RSX_FUSE_MINMAX = 0, RSX_FUSE_RRF = 1 };
+int rsx_select_topk_rows(const float* S, int64_t ld, int64_t Q, int64_t N, int64_t k, int32_t* idx, float* val,
+                         void* stream);
+int rsx_fuse_rank(const float* ua, int64_t ldua, const float* Ia, int64_t ldia, int64_t Da, const float* ub,
+                  int64_t ldub, const float* Ib, int64_t ldib, int64_t Db, int64_t Q, int64_t NI,
+                  const int32_t* cand, int64_t C, const float* wa, const float* wb, int A, int mode, float k_rrf,
+                  int cut, const int32_t* ks, int nK, const int64_t* truth_off, const int32_t* truth,
+                  int64_t n_truth, int32_t* hits, int32_t* lists, float* sa, float* sb, int32_t* flag,
+                  void* stream);
+int rsx_first_hit(const int32_t* lists, int64_t ld, int64_t Q, int64_t K, const int64_t* truth_off,
+                  const int32_t* truth, int64_t n_truth, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 12 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 13 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -185,6 +185,10 @@ _SIGS = {
                                 c_f, c_u64, c_f, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "rsx_distill_apply": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_d, c_d, c_d,
                                 c_d, c_i64, c_p]),
+    "rsx_select_topk_rows": (c_i, [c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
+    "rsx_fuse_rank": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64,
+                            c_p, c_p, c_i, c_i, c_f, c_i, c_p, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_first_hit": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -3371,6 +3371,166 @@ def distill_step(user_table, item_table, users, items, w1, b1, w2, b2, logit_sca
 
 
 # ----------------------------------------------------------------------------------------
+# Late fusion of two retrievers (tower_code/mined_inference.py): pool, fuse, hits (csrc/ensemble.hip)
+SELECT_TOPK_MAX = 2048    # rsx_select_topk_rows: largest k
+FUSE_MAX_POOL = 2048      # rsx_fuse_rank: largest candidate pool C
+FUSE_MAX_ALPHAS = 32
+FUSE_MAX_KS = 16
+FUSE_MINMAX, FUSE_RRF = 0, 1
+_FUSE_MODES = {"minmax": FUSE_MINMAX, "rrf": FUSE_RRF}
+
+
+def select_topk_rows(S, k):
+    """(idx [Q, k] int32, val [Q, k]) of the k largest entries of each row of the fp32 score matrix S
+    [Q, N], in the order (value descending, index ascending); -0.0 and +0.0 tie. Exact for
+    1 <= k <= min(N, 2048); the scores must be finite. Rows may be strided (unit column stride)."""
+    fn = "select_topk_rows"
+    _rows2(fn, "S", S)
+    Q, n = S.shape
+    k = int(k)
+    if not 1 <= k <= min(n, SELECT_TOPK_MAX):
+        raise ValueError(f"{fn}: k={k} out of range for N={n} (1 <= k <= min(N, {SELECT_TOPK_MAX}))")
+    N.ensure_device(S)
+    if S.stride(1) != 1 or S.stride(0) < n:
+        S = S.contiguous()
+    idx = torch.empty(Q, k, device=S.device, dtype=torch.int32)
+    val = torch.empty(Q, k, device=S.device, dtype=torch.float32)
+    with timed("select_topk_rows"):
+        rc = N.lib().rsx_select_topk_rows(N.ptr(S), S.stride(0), Q, n, k, N.ptr(idx), N.ptr(val), N.stream())
+    N.check(rc, fn)
+    return idx, val
+
+
+def _rows_vec(fn, name, t, ref=None):
+    """t as fp32 [rows, D] rows read 16 bytes at a time, D in {64, 128} (unit column stride, row stride a
+    multiple of 4 floats, 16-B aligned; anything else is copied)."""
+    D = _rows2(fn, name, t)
+    if D not in (64, 128):
+        raise ValueError(f"{fn}: {name} must have 64 or 128 columns, got {D}")
+    if ref is not None and t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < D or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t
+
+
+def _truth_csr(fn, truth_off, truth, Q, ref):
+    if truth_off.dtype != torch.int64 or truth.dtype != torch.int32:
+        raise TypeError(f"{fn}: truth_off must be int64 and truth int32, got {truth_off.dtype} / {truth.dtype}")
+    if truth_off.device != ref.device or truth.device != ref.device:
+        raise RuntimeError(f"{fn}: the truth is on {truth_off.device} / {truth.device}, expected {ref.device}")
+    if truth_off.dim() != 1 or truth_off.numel() != Q + 1 or truth.dim() != 1:
+        raise ValueError(f"{fn}: truth_off must hold Q + 1 = {Q + 1} offsets (got {tuple(truth_off.shape)}) "
+                         "and truth must be 1-D")
+    return _c(truth_off), _c(truth)
+
+
+class FuseRank:
+    """What fuse_rank returns: hits [Q, A] int32 (bit j = hit@ks[j]), the flag and, on request, lists
+    [Q, A, ks[-1]] int32 (each alpha's fused list without repeats, -1 padded) and the raw scores sa / sb
+    [Q, C] of the pool entries."""
+
+    def __init__(self, hits, flag, lists=None, sa=None, sb=None):
+        self.hits, self.flag, self.lists, self.sa, self.sb = hits, flag, lists, sa, sb
+
+
+def fusion_weights(alphas):
+    """(wa, wb) as Python floats that are exact in fp32: float32(alpha) and float32(1.0 - alpha), the
+    subtraction in double as Python does in `alpha * s_gnn + (1.0 - alpha) * s_seq`
+    (tower_code/mined_inference.py:1162)."""
+    wa = [ctypes.c_float(float(a)).value for a in alphas]
+    wb = [ctypes.c_float(1.0 - float(a)).value for a in alphas]
+    return wa, wb
+
+
+def fuse_rank(ua, Ia, ub, Ib, cand, alphas, ks, truth_off, truth, mode="minmax", k_rrf=200.0, cut=None,
+              return_lists=False, return_scores=False, flag=None):
+    """Late fusion of retrievers a and b over each user's candidate pool, for every alpha, in one launch
+    (include/recsys_amd.h, rsx_fuse_rank): ua [Q, Da], Ia [NI, Da], ub [Q, Db], Ib [NI, Db] (Da, Db in
+    {64, 128}); cand [Q, C] int32 corpus rows, C <= 2048, duplicates kept; alphas: the weights of a
+    (fusion_weights); ks ascending; cut defaults to min(C, ks[-1] + 20); the truth in CSR (truth_off int64
+    [Q + 1], truth int32, each user's items ascending and distinct). mode "minmax" or "rrf".
+    flag (int32 [1], created zeroed when not given) is set by a pool entry outside the corpus, which
+    scores 0. Returns a FuseRank."""
+    fn = "fuse_rank"
+    ua = _rows_vec(fn, "ua", ua)
+    Ia = _rows_vec(fn, "Ia", Ia, ua)
+    ub = _rows_vec(fn, "ub", ub, ua)
+    Ib = _rows_vec(fn, "Ib", Ib, ua)
+    if ua.shape[1] != Ia.shape[1] or ub.shape[1] != Ib.shape[1]:
+        raise ValueError(f"{fn}: widths disagree: ua {tuple(ua.shape)} / Ia {tuple(Ia.shape)}, "
+                         f"ub {tuple(ub.shape)} / Ib {tuple(Ib.shape)}")
+    Q, NI = ua.shape[0], Ia.shape[0]
+    if ub.shape[0] != Q or Ib.shape[0] != NI:
+        raise ValueError(f"{fn}: the two retrievers must share users and corpus: {Q} / {ub.shape[0]} users, "
+                         f"{NI} / {Ib.shape[0]} items")
+    if cand.dtype != torch.int32 or cand.dim() != 2 or cand.shape[0] != Q or cand.device != ua.device:
+        raise ValueError(f"{fn}: cand must be an int32 [Q, C] tensor on the vectors' device")
+    C = cand.shape[1]
+    if not 1 <= C <= FUSE_MAX_POOL:
+        raise ValueError(f"{fn}: the pool holds {C} entries; the kernel takes 1 to {FUSE_MAX_POOL}")
+    if mode not in _FUSE_MODES:
+        raise ValueError(f"{fn}: mode must be one of {sorted(_FUSE_MODES)}")
+    wa, wb = fusion_weights(alphas)
+    A = len(wa)
+    if not 1 <= A <= FUSE_MAX_ALPHAS:
+        raise ValueError(f"{fn}: need 1 to {FUSE_MAX_ALPHAS} alphas (got {A})")
+    ks = [int(x) for x in ks]
+    if not 1 <= len(ks) <= FUSE_MAX_KS or ks[0] < 1 or any(b < a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"{fn}: ks must be 1 to {FUSE_MAX_KS} ascending positive integers (got {ks})")
+    cut = min(C, ks[-1] + 20) if cut is None else int(cut)
+    if not (1 <= cut <= C and ks[-1] <= cut):
+        raise ValueError(f"{fn}: need ks[-1] <= cut <= C (ks[-1]={ks[-1]}, cut={cut}, C={C})")
+    truth_off, truth = _truth_csr(fn, truth_off, truth, Q, ua)
+    own_flag = flag is None
+    if not own_flag and (flag.dtype != torch.int32 or flag.numel() != 1 or flag.device != ua.device):
+        raise ValueError(f"{fn}: flag must be an int32 tensor of one element on the vectors' device")
+    N.ensure_device(ua)
+    dev = ua.device
+    cand = _c(cand)
+    if own_flag:
+        flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    hits = torch.empty(Q, A, device=dev, dtype=torch.int32)
+    lists = torch.empty(Q, A, ks[-1], device=dev, dtype=torch.int32) if return_lists else None
+    sa = torch.empty(Q, C, device=dev, dtype=torch.float32) if return_scores else None
+    sb = torch.empty(Q, C, device=dev, dtype=torch.float32) if return_scores else None
+    wa_c, wb_c = (ctypes.c_float * A)(*wa), (ctypes.c_float * A)(*wb)
+    ks_c = (ctypes.c_int32 * len(ks))(*ks)
+    with timed("fuse_rank"):
+        rc = N.lib().rsx_fuse_rank(N.ptr(ua), ua.stride(0), N.ptr(Ia), Ia.stride(0), ua.shape[1], N.ptr(ub),
+                                   ub.stride(0), N.ptr(Ib), Ib.stride(0), ub.shape[1], Q, NI, N.ptr(cand), C, wa_c,
+                                   wb_c, A, _FUSE_MODES[mode], float(k_rrf), cut, ks_c, len(ks), N.ptr(truth_off),
+                                   N.ptr(truth), truth.numel(), N.ptr(hits), N.ptr(lists), N.ptr(sa), N.ptr(sb),
+                                   N.ptr(flag), N.stream())
+    N.check(rc, fn)
+    return FuseRank(hits, flag, lists, sa, sb)
+
+
+def first_hit(lists, truth_off, truth):
+    """[Q] int32: the smallest j with lists[q, j] in user q's truth (CSR: truth_off int64 [Q + 1], truth
+    int32, each user's items ascending and distinct), or K = lists.shape[1] when there is none.
+    lists [Q, K] is an integer tensor (int32 is read as it is, other integer types are converted)."""
+    fn = "first_hit"
+    if lists.dim() != 2 or lists.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"{fn}: lists must be an int32 or int64 [Q, K] tensor")
+    Q, K = lists.shape
+    if K < 1:
+        raise ValueError(f"{fn}: lists must have at least one column")
+    truth_off, truth = _truth_csr(fn, truth_off, truth, Q, lists)
+    N.ensure_device(lists)
+    if lists.dtype != torch.int32:
+        lists = lists.to(torch.int32)
+    if lists.stride(1) != 1 or lists.stride(0) < K:
+        lists = lists.contiguous()
+    out = torch.empty(Q, device=lists.device, dtype=torch.int32)
+    with timed("first_hit"):
+        rc = N.lib().rsx_first_hit(N.ptr(lists), lists.stride(0), Q, K, N.ptr(truth_off), N.ptr(truth), truth.numel(),
+                                   N.ptr(out), N.stream())
+    N.check(rc, fn)
+    return out
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 
