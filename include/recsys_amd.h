@@ -336,7 +336,9 @@ int rsx_linear_wgrad_x3(const float* dY, int64_t ldy, const float* X, int64_t ld
  * (keep-mask hash(seed, m*N + n)), aux = gelu_erf'(z) (aux may be NULL: inference, e.g. the
  * item tower's BERT intermediate layer, item_tower.py:175); 2 C = acc * keep / (1-p) * aux, its
  * backward (same seed, aux from epi 1). Epilogues 1/2 fuse nn.TransformerEncoderLayer's feed-forward
- * dropout(gelu(linear1(x))) (v1_refine_usertower.py:343-352) into its GEMMs.
+ * dropout(gelu(linear1(x))) (v1_refine_usertower.py:343-352) into its GEMMs. 3 (rsx_gemm_x3 and
+ * rsx_gemm_x3_ws only) C = max(acc + bias, 0), inference only: aux must be NULL and p_drop 0 (the
+ * ReLU feed-forward of HybridUserTower's encoder, tower_code/mined_inference.py:635-638).
  * N % 128 == 0, K % 32 == 0, A/B 16-byte aligned, leading dimensions multiples of 4. */
 int rsx_gemm_x3(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M, int N, int K,
                 int epi, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C, int64_t ldc, void* stream);
@@ -948,6 +950,51 @@ int rsx_fuse_rank(const float* ua, int64_t ldua, const float* Ia, int64_t ldia, 
                   void* stream);
 int rsx_first_hit(const int32_t* lists, int64_t ld, int64_t Q, int64_t K, const int64_t* truth_off,
                   const int32_t* truth, int64_t n_truth, int32_t* out, void* stream);
+
+/* ---- HybridUserTower inference: adapter, sequence input, fusion (csrc/hybrid.hip) --------
+ * The eval forward of tower_code/mined_inference.py's ParallelAdapter (:582-602), the sequence input
+ * of HybridUserTower.forward (:687-695) and SequenceCentricFusion with the two normalisations around
+ * it (:703-710). Exact fp32 products (f32-input MFMA), no float atomics, bit-reproducible; a row's
+ * result does not depend on the rows around it. All float rows 16-B aligned.
+ *
+ * rsx_hybrid_adapter_fwd: R rows; row r takes id = ids[r] (int64, repeats allowed) or, with ids NULL,
+ * id = first_row + r (first_row + R <= min(Nc, Ng)), c = content[id] (Dc = 128 floats, row stride ldc),
+ * g = gnn[id] (Dg = 64, ldg), and
+ *   m = (gelu(LN(wc c + bc; lnc_w, lnc_b, ln_eps)) + c) + gelu(LN(wg g + bg; lng_w, lng_b, ln_eps))
+ * with wc [128, 128], wg [128, 64] dense, erf GELU, biased variance. Outputs [R, 128], each nullable
+ * (at least one given): merged = m; unit = m / max(|m|, eps); seq_in = m * scale + time_tab[min(deltas[r],
+ * 1000)] (the product rounded, then the sum; deltas int64 [R], time_tab [1001, 128] dense). An id outside
+ * [0, min(Nc, Ng)) or a negative delta sets flag[0] = 1 (int32, zeroed by the caller) and reads row 0.
+ *
+ * rsx_hybrid_seq_gather: seq_in[t] = merged[ids[t] - first_row] * scale + time_tab[min(deltas[t], 1000)]
+ * over T tokens from a table merged [Nm, D = 128] (dense) of rsx_hybrid_adapter_fwd: the same bits as its
+ * seq_in. An id in [0, first_row) reads a zero row (the padding id of a table that starts at row 1); a
+ * negative id, an id >= first_row + Nm or a negative delta sets flag[0] = 1.
+ *
+ * rsx_hybrid_fuse_fwd: seq_out [B * L, D = 128] dense, 1 <= L <= 64. The rows fused are rows[0 .. n_rows)
+ * (int64 token rows in [0, B L); outside sets flag[0] = 1 and reads row 0) or, with rows NULL, all B L
+ * rows in order; row i of the outputs belongs to token row s = rows[i], user u = s / L:
+ *   v = x / max(|x|, eps); g = sigmoid(w2 gelu(w1 v + b1) + b2)     w1 [hidden = 64, 128], w2 [2, 64]
+ *   f = (v + g0 u_gnn[u]) + g1 u_meta[u]                             u_gnn, u_meta [B, 128] dense
+ *   out = y / max(|y|, eps), y = LN(f; ln_w, ln_b, ln_eps)
+ * out [n, 128]; v_seq [n, 128] = v (nullable); gate_mean [2] float (nullable) = the means of g0 and g1
+ * over the n rows: per-workgroup double partials in ws (>= rsx_hybrid_fuse_slots(n) * 16 bytes, 8-B
+ * aligned; the slot count depends on n alone) added in slot order by a second launch. */
+int rsx_hybrid_adapter_fwd(const float* content, int64_t ldc, int64_t Nc, int64_t Dc, const float* gnn, int64_t ldg,
+                           int64_t Ng, int64_t Dg, const int64_t* ids, int64_t first_row, int64_t R,
+                           const float* wc, const float* bc, const float* lnc_w, const float* lnc_b,
+                           const float* wg, const float* bg, const float* lng_w, const float* lng_b, float ln_eps,
+                           float eps, const int64_t* deltas, const float* time_tab, float scale, float* merged,
+                           float* unit, float* seq_in, int32_t* flag, void* stream);
+int rsx_hybrid_seq_gather(const float* merged, int64_t Nm, int64_t D, int64_t first_row, const int64_t* ids,
+                          const int64_t* deltas, int64_t T, const float* time_tab, float scale, float* seq_in,
+                          int32_t* flag, void* stream);
+int64_t rsx_hybrid_fuse_slots(int64_t n);
+int rsx_hybrid_fuse_fwd(const float* seq_out, int64_t B, int64_t L, int64_t D, const int64_t* rows, int64_t n_rows,
+                        const float* u_gnn, const float* u_meta, const float* w1, const float* b1, int64_t hidden,
+                        const float* w2, const float* b2, const float* ln_w, const float* ln_b, float ln_eps,
+                        float eps, float* out, float* v_seq, float* gate_mean, void* ws, int64_t ws_bytes,
+                        int32_t* flag, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 13 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 14 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -189,6 +189,12 @@ _SIGS = {
     "rsx_fuse_rank": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64,
                             c_p, c_p, c_i, c_i, c_f, c_i, c_p, c_i, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
     "rsx_first_hit": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p]),
+    "rsx_hybrid_adapter_fwd": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p, c_p,
+                                     c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_hybrid_seq_gather": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_f, c_p, c_p, c_p]),
+    "rsx_hybrid_fuse_slots": (c_i64, [c_i64]),
+    "rsx_hybrid_fuse_fwd": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
+                                  c_f, c_f, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -18,6 +18,7 @@
 //                  aux = gelu_erf'(z), the backward's multiplier (saved instead of z)
 //   EPI_DGELU_DROP C = acc * keep(m, n) / (1 - p) * aux[m][n]   (backward of the above:
 //                  acc = dAct = dY2 . W2)
+//   EPI_RELU       C = max(acc + bias, 0)   (inference only: no aux, no dropout; rsx_gemm_x3's epi 3)
 //   EPI_ADDLN      (weight-stationary, N = 128) the residual add + LayerNorm after the
 //                  attention out-projection: C = s = aux + dropout_p(acc + bias),
 //                  y = LayerNorm(s) * ln_w + ln_b, with the row's mean / rstd saved
@@ -43,6 +44,8 @@ constexpr int kBM = 128, kBN = 128, kBK = RSX_GEMM_BK;
 constexpr int kRow = kBK + 8;  // bf16 per LDS row (80 B at BK 32, 48 B at BK 16: conflict-free b128 reads)
 constexpr int kF4 = kBK / 8;   // float4 loads per thread and operand per stage (two threads per row)
 constexpr int EPI_BIAS = 0, EPI_GELU_DROP = 1, EPI_DGELU_DROP = 2, EPI_ROWADD = 3, EPI_ADDLN = 4;
+constexpr int EPI_RELU = 5;       // internal number; the public epi 3 of rsx_gemm_x3 / rsx_gemm_x3_ws
+constexpr int kPublicRelu = 3;
 #ifndef RSX_GEMM_BLOCKS
 #define RSX_GEMM_BLOCKS (1 << 30)  // workgroup budget of the multi-tile stream: at BK 16 one tile each measured best
 #endif
@@ -160,6 +163,8 @@ __device__ __forceinline__ void epilogue(const GArgs& a, f32x16 (&acc)[2][2], in
           if (a.aux) a.aux[m * a.ldaux + n] = gelu_grad_cdf(v, cdf);
           v *= cdf;  // gelu(v)
           if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
+        } else if (EPI == EPI_RELU) {
+          v = fmaxf(v + bn, 0.0f);
         } else if (a.drop.active()) {
           v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
         }
@@ -338,6 +343,8 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_k(GArgs a) {
     if (a.aux) a.aux[m * a.ldaux + n] = gelu_grad_cdf(v, cdf);
     v *= cdf;  // gelu(v)
     if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
+  } else if (EPI == EPI_RELU) {
+    v = fmaxf(v + bn, 0.0f);
   } else if (a.drop.active()) {
     v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
   }
@@ -558,6 +565,10 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws_k(WsArgs w) {
             v[0] += z[j][g].x; v[1] += z[j][g].y; v[2] += z[j][g].z; v[3] += z[j][g].w;
           }
         }
+        if (EPI == EPI_RELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+        }
         if (EPI == EPI_GELU_DROP) {
           float d[4];
 #pragma unroll
@@ -645,6 +656,8 @@ void launch_ws(const GArgs& g, hipStream_t st) {
     hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_ADDLN>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else if (g.epi == EPI_GELU_DROP)
     hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_GELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
+  else if (g.epi == EPI_RELU)
+    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_RELU>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_DGELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
 }
 
@@ -682,9 +695,14 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
   static_assert(kBK == 16 || kBK == 32, "stage depth 16 or 32");
   RSX_ARG(lda >= K && ldb >= K && ldc >= N && lda % 4 == 0 && ldb % 4 == 0, "bad leading dimensions");
   RSX_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "A/B must be 16-byte aligned");
-  RSX_ARG(epi == EPI_BIAS || epi == EPI_GELU_DROP || epi == EPI_DGELU_DROP, "epi must be 0, 1 or 2");
-  RSX_ARG(epi == EPI_BIAS || (epi == EPI_GELU_DROP && !aux) || (aux && ldaux >= N),
-          "the GELU epilogues need aux [M, >=N] (EPI_GELU_DROP: aux may be null for inference)");
+  if (epi == kPublicRelu) {
+    RSX_ARG(!aux && p_drop == 0.0f, "the ReLU epilogue is inference only: aux must be null and p_drop 0");
+    epi = EPI_RELU;
+  } else {
+    RSX_ARG(epi == EPI_BIAS || epi == EPI_GELU_DROP || epi == EPI_DGELU_DROP, "epi must be 0, 1, 2 or 3");
+    RSX_ARG(epi == EPI_BIAS || (epi == EPI_GELU_DROP && !aux) || (aux && ldaux >= N),
+            "the GELU epilogues need aux [M, >=N] (EPI_GELU_DROP: aux may be null for inference)");
+  }
   RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0, 1)");
   RSX_ARG(M * (int64_t)N < (1LL << 32), "M * N must be < 2^32 (dropout element index)");
   if (M == 0) return 0;
@@ -719,6 +737,7 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
     const unsigned rb = (unsigned)((M * (int64_t)N + 255) / 256);
     if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_BIAS>, dim3(rb), dim3(256), 0, st, g);
     else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_GELU_DROP>, dim3(rb), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU>, dim3(rb), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_DGELU_DROP>, dim3(rb), dim3(256), 0, st, g);
     RSX_LAUNCHED();
     return 0;
@@ -735,9 +754,12 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
     else if (epi == EPI_GELU_DROP && b32)
       hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
     else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU && b32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4>), dim3(grid), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);  // Q = 4 spills here
   } else if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_BIAS>, dim3(grid), dim3(256), 0, st, g);
   else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_GELU_DROP>, dim3(grid), dim3(256), 0, st, g);
+  else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU>, dim3(grid), dim3(256), 0, st, g);
   else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);
   RSX_LAUNCHED();
   return 0;

@@ -1503,6 +1503,7 @@ def add_layer_norm(x, res, weight, bias, eps=1e-5, p_drop=0.0):
 GEMM_PRECISIONS = ("fp32", "bf16x3")
 _gemm_precision = os.environ.get("RSX_GEMM_PRECISION", "bf16x3")
 EPI_BIAS, EPI_GELU_DROP, EPI_DGELU_DROP = 0, 1, 2
+EPI_RELU = 3   # C = max(acc + bias, 0): inference only (no aux, p_drop 0)
 
 
 def set_gemm_precision(p: str) -> str:
@@ -1793,15 +1794,26 @@ class _FFN(torch.autograd.Function):
         return dh, dw1, db1, dw2, db2, None, None
 
 
-def ffn(h, w1, b1, w2, b2, p_drop=0.0, training=True):
-    """linear2(dropout(gelu(linear1(h)))) over a token axis (nn.TransformerEncoderLayer's
-    feed-forward block, activation="gelu"). bf16x3 mode with GEMM-shaped widths: two fused
-    GEMM launches forward, three plus two weight gradients backward; otherwise the unfused ops."""
+def ffn(h, w1, b1, w2, b2, p_drop=0.0, training=True, act="gelu"):
+    """linear2(dropout(act(linear1(h)))) over a token axis (nn.TransformerEncoderLayer's
+    feed-forward block). act="gelu": bf16x3 mode with GEMM-shaped widths: two fused GEMM launches
+    forward, three plus two weight gradients backward; otherwise the unfused ops. act="relu" (the
+    layer's default activation): inference only on the fused path (rsx_gemm_x3's EPI_RELU, gradients
+    off and no dropout); with gradients enabled the unfused PyTorch form."""
+    if act not in ("gelu", "relu"):
+        raise ValueError(f"ffn: act must be 'gelu' or 'relu', got {act!r}")
     p = float(p_drop) if training else 0.0
     shp = h.shape
     h2 = h.reshape(-1, shp[-1])
-    if (h2.is_cuda and h2.shape[0] > 0 and _x3_ok(w1.shape[0], w1.shape[1]) and _x3_ok(w2.shape[0], w2.shape[1])
-            and _x3_ok(w2.shape[1], w2.shape[0]) and _x3_ok(w1.shape[1], w1.shape[0])):
+    shaped = (h2.is_cuda and h2.shape[0] > 0 and _x3_ok(w1.shape[0], w1.shape[1]) and _x3_ok(w2.shape[0], w2.shape[1])
+              and _x3_ok(w2.shape[1], w2.shape[0]) and _x3_ok(w1.shape[1], w1.shape[0]))
+    if act == "relu":
+        if shaped and p == 0.0 and not torch.is_grad_enabled():
+            a = gemm_x3(h2, w1, b1, EPI_RELU, tag="ffn_relu_fwd1")
+            return gemm_x3(a, w2, b2, tag="ffn_fwd2").reshape(*shp[:-1], w2.shape[0])
+        F = torch.nn.functional
+        return F.linear(F.dropout(F.relu(F.linear(h, w1, b1)), p, training), w2, b2)
+    if shaped:
         seed = next_seed() if p > 0 else 0
         f = _FFN.apply(h2, w1, b1, w2, b2, p, seed)
         return f.reshape(*shp[:-1], w2.shape[0])
@@ -3528,6 +3540,173 @@ def first_hit(lists, truth_off, truth):
                                    N.ptr(out), N.stream())
     N.check(rc, fn)
     return out
+
+
+# ----------------------------------------------------------------------------------------
+# HybridUserTower inference (tower_code/mined_inference.py, csrc/hybrid.hip): the dual-table adapter,
+# the sequence input and the sequence-centric fusion
+HYBRID_WIDTHS = (128, 64, 128)   # content row, GNN row, model width of the kernels
+HYBRID_GATE_HIDDEN = 64
+HYBRID_MAX_LEN = 64
+HYBRID_TIME_ROWS = 1001
+_HYBRID_IDS = IdRangeGuard("HybridUserTower ids (item ids, time deltas or token rows)")
+
+
+class AdapterParams:
+    """The eight tensors of a ParallelAdapter and its LayerNorm eps, as the kernels read them."""
+
+    def __init__(self, wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b, ln_eps=1e-5):
+        self.tensors = tuple(_c(t.detach()) for t in (wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b))
+        self.ln_eps = float(ln_eps)
+
+    def check(self, fn, ref):
+        Dc, Dg, D = HYBRID_WIDTHS
+        shapes = ((D, Dc), (D,), (D,), (D,), (D, Dg), (D,), (D,), (D,))
+        for name, t, shp in zip(("wc", "bc", "lnc_w", "lnc_b", "wg", "bg", "lng_w", "lng_b"), self.tensors, shapes):
+            _f32(fn, name, t, ref)
+            if tuple(t.shape) != shp:
+                raise ValueError(f"{fn}: {name} has shape {tuple(t.shape)}, the adapter kernel takes {shp}")
+
+
+def _hybrid_table(fn, name, t, width):
+    D = _rows2(fn, name, t)
+    if D != width:
+        raise ValueError(f"{fn}: {name} must have {width} columns, got {D}")
+    if t.stride(1) != 1 or t.stride(0) % 4 != 0 or t.stride(0) < D or t.data_ptr() % 16 != 0:
+        t = t.contiguous()
+    return t.detach()
+
+
+def _time_table(fn, time_tab, ref):
+    _f32(fn, "time_tab", time_tab, ref)
+    if tuple(time_tab.shape) != (HYBRID_TIME_ROWS, HYBRID_WIDTHS[2]):
+        raise ValueError(f"{fn}: time_tab has shape {tuple(time_tab.shape)}, expected "
+                         f"{(HYBRID_TIME_ROWS, HYBRID_WIDTHS[2])}")
+    return _c(time_tab.detach())
+
+
+def hybrid_adapter(content, gnn, params, ids=None, first_row=0, rows=None, deltas=None, time_tab=None, scale=1.0,
+                   want_merged=True, want_unit=False, eps=1e-12):
+    """ParallelAdapter's eval forward over gathered rows in one launch (rsx_hybrid_adapter_fwd):
+    m = gelu(LN(Wc c + bc)) + c + gelu(LN(Wg g + bg)) with c = content[id] [*, 128], g = gnn[id] [*, 64]
+    and id = ids.flatten()[r] (any shape, repeats allowed) or, without ids, first_row + r for r < rows
+    (default: to the end of the shorter table). Returns (merged, unit, seq_in), each [R, 128] or None:
+    merged = m, unit = m / max(|m|, eps), seq_in = m scale + time_tab[min(deltas, 1000)] when deltas is
+    given. No autograd; deterministic; a row's bits depend on its id (and delta) alone. An id outside
+    the tables raises IndexError asynchronously (IdRangeGuard)."""
+    fn = "hybrid_adapter"
+    Dc, Dg, D = HYBRID_WIDTHS
+    content = _hybrid_table(fn, "content", content, Dc)
+    gnn = _hybrid_table(fn, "gnn", gnn, Dg)
+    _f32(fn, "gnn", gnn, content)
+    params.check(fn, content)
+    n_tab = min(content.shape[0], gnn.shape[0])
+    if ids is not None:
+        ids = _c(_index(fn, "ids", ids, content))
+        R = ids.numel()
+    else:
+        first_row = int(first_row)
+        R = n_tab - first_row if rows is None else int(rows)
+        if first_row < 0 or R < 0 or first_row + R > n_tab:
+            raise ValueError(f"{fn}: rows [{first_row}, {first_row + R}) exceed the tables ({n_tab} rows)")
+    want_seq = deltas is not None
+    if want_seq:
+        if time_tab is None:
+            raise ValueError(f"{fn}: deltas need time_tab")
+        deltas = _c(_index(fn, "deltas", deltas, content, R))
+        time_tab = _time_table(fn, time_tab, content)
+    if not (want_merged or want_unit or want_seq):
+        raise ValueError(f"{fn}: no output requested")
+    N.ensure_device(content)
+    dev = content.device
+    new = lambda on: torch.empty(R, D, device=dev, dtype=torch.float32) if on else None  # noqa: E731
+    merged, unit, seq_in = new(want_merged), new(want_unit), new(want_seq)
+    if R == 0:
+        return merged, unit, seq_in
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("hybrid/adapter"):
+        rc = N.lib().rsx_hybrid_adapter_fwd(
+            N.ptr(content), content.stride(0), content.shape[0], Dc, N.ptr(gnn), gnn.stride(0), gnn.shape[0], Dg,
+            N.ptr(ids), first_row if ids is None else 0, R, *(N.ptr(t) for t in params.tensors), params.ln_eps,
+            float(eps), N.ptr(deltas), N.ptr(time_tab), float(scale), N.ptr(merged), N.ptr(unit), N.ptr(seq_in),
+            N.ptr(flag), N.stream())
+    N.check(rc, fn)
+    _HYBRID_IDS.watch(flag)
+    return merged, unit, seq_in
+
+
+def hybrid_seq_gather(merged, ids, deltas, time_tab, scale=1.0, first_row=0):
+    """seq_in [T, 128] = merged[ids - first_row] scale + time_tab[min(deltas, 1000)] from the merged
+    table of hybrid_adapter(first_row=first_row): the adapter once per item instead of once per token,
+    the same bits as its seq_in. An id below first_row (the padding id) reads a zero row."""
+    fn = "hybrid_seq_gather"
+    D = HYBRID_WIDTHS[2]
+    if _rows2(fn, "merged", merged) != D:
+        raise ValueError(f"{fn}: merged must have {D} columns, got {merged.shape[1]}")
+    merged = _c(merged.detach())
+    ids = _c(_index(fn, "ids", ids, merged))
+    T = ids.numel()
+    deltas = _c(_index(fn, "deltas", deltas, merged, T))
+    time_tab = _time_table(fn, time_tab, merged)
+    N.ensure_device(merged)
+    seq_in = torch.empty(T, D, device=merged.device, dtype=torch.float32)
+    if T == 0:
+        return seq_in
+    flag = torch.zeros(1, device=merged.device, dtype=torch.int32)
+    with timed("hybrid/seq_gather"):
+        rc = N.lib().rsx_hybrid_seq_gather(N.ptr(merged), merged.shape[0], D, int(first_row), N.ptr(ids), N.ptr(deltas),
+                                           T, N.ptr(time_tab), float(scale), N.ptr(seq_in), N.ptr(flag), N.stream())
+    N.check(rc, fn)
+    _HYBRID_IDS.watch(flag)
+    return seq_in
+
+
+def hybrid_fuse(seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, rows=None, ln_eps=1e-5, eps=1e-12,
+                want_v=True, want_gate=True):
+    """SequenceCentricFusion with the normalisations around it, per token row (rsx_hybrid_fuse_fwd):
+    v = normalize(seq_out), g = sigmoid(W2 gelu(W1 v + b1) + b2), out = normalize(LN(v + g0 u_gnn[u] +
+    g1 u_meta[u])). seq_out [B, L, 128] (L <= 64); u_gnn / u_meta [B, 128], the outputs of gnn_proj /
+    meta_proj; rows: int64 token rows b L + l to fuse (None: all, in order). Returns (out [n, 128],
+    v [n, 128] or None, gate_mean [2] device floats (the means of g0, g1 over the n rows) or None).
+    No autograd; bit-reproducible."""
+    fn = "hybrid_fuse"
+    D = HYBRID_WIDTHS[2]
+    _f32(fn, "seq_out", seq_out)
+    if seq_out.dim() != 3 or seq_out.shape[2] != D:
+        raise ValueError(f"{fn}: seq_out must be [B, L, {D}], got shape {tuple(seq_out.shape)}")
+    B, L = seq_out.shape[:2]
+    if not 1 <= L <= HYBRID_MAX_LEN:
+        raise ValueError(f"{fn}: L must be in [1, {HYBRID_MAX_LEN}], got {L}")
+    for name, t, shp in (("u_gnn", u_gnn, (B, D)), ("u_meta", u_meta, (B, D)), ("w1", w1, (HYBRID_GATE_HIDDEN, D)),
+                         ("b1", b1, (HYBRID_GATE_HIDDEN,)), ("w2", w2, (2, HYBRID_GATE_HIDDEN)), ("b2", b2, (2,)),
+                         ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,))):
+        _f32(fn, name, t, seq_out)
+        if tuple(t.shape) != shp:
+            raise ValueError(f"{fn}: {name} has shape {tuple(t.shape)}, expected {shp}")
+    if rows is not None:
+        rows = _c(_index(fn, "rows", rows, seq_out))
+    n = B * L if rows is None else rows.numel()
+    N.ensure_device(seq_out)
+    dev = seq_out.device
+    seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b = (_c(t.detach()) for t in (seq_out, u_gnn, u_meta, w1, b1, w2,
+                                                                                  b2, ln_w, ln_b))
+    out = torch.empty(n, D, device=dev, dtype=torch.float32)
+    v = torch.empty(n, D, device=dev, dtype=torch.float32) if want_v else None
+    gate = torch.zeros(2, device=dev, dtype=torch.float32) if want_gate else None
+    if n == 0:
+        return out, v, gate
+    slots = N.lib().rsx_hybrid_fuse_slots(n)
+    ws = torch.empty(2 * slots, device=dev, dtype=torch.float64) if want_gate else None
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("hybrid/fuse"):
+        rc = N.lib().rsx_hybrid_fuse_fwd(N.ptr(seq_out), B, L, D, N.ptr(rows), n if rows is not None else 0,
+                                         N.ptr(u_gnn), N.ptr(u_meta), N.ptr(w1), N.ptr(b1), HYBRID_GATE_HIDDEN,
+                                         N.ptr(w2), N.ptr(b2), N.ptr(ln_w), N.ptr(ln_b), float(ln_eps), float(eps),
+                                         N.ptr(out), N.ptr(v), N.ptr(gate), N.ptr(ws), 16 * slots if want_gate else 0,
+                                         N.ptr(flag), N.stream())
+    N.check(rc, fn)
+    _HYBRID_IDS.watch(flag)
+    return out, v, gate
 
 
 # ----------------------------------------------------------------------------------------

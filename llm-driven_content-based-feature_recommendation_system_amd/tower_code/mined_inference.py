@@ -1,5 +1,6 @@
-"""Drop-in for the ensemble evaluators of tower_code/mined_inference.py: late fusion of the sequence
-retriever and the GNN retriever over an alpha sweep, on the device.
+"""Drop-in for tower_code/mined_inference.py: HybridUserTower (the sequence model over content and GNN item
+rows with a gated fusion of per-user vectors; defined below, before the evaluators) and the ensemble
+evaluators: late fusion of the sequence retriever and the GNN retriever over an alpha sweep, on the device.
 
 Reference (tower_code/mined_inference.py): evaluate_multi_vector_ensemble :797-993,
 evaluate_weighted_score_ensemble :996-1227 (the live entry point of main, :1669-1678),
@@ -10,8 +11,9 @@ the GNN tables, ran the sequence model over a DataLoader and read the targets fr
 evaluators work at the vector level: they take the user and item vectors of both retrievers (rows of
 one user / one item in the same position in both spaces) and `ground_truth`, a dict from a user row to
 the set of its item rows (0-based into the item matrices), as gnn_model.v1_evaluate_lightgcl.
-evaluate_recall does. Any tower produces the vectors: SASRecUserTower with the distilled LightGCL tables
-(gnn_model.distill_mag_to_cos_l2) today. They return the whole sweep, not only the best alpha:
+evaluate_recall does. Any tower produces the vectors: encode_users / hybrid_item_vectors of
+HybridUserTower as in the reference's main, or SASRecUserTower, with the distilled LightGCL tables
+(gnn_model.distill_mag_to_cos_l2) on the GNN side. They return the whole sweep, not only the best alpha:
 {"best_alpha", "hits": {alpha: {k: users hit}}, "recall": {alpha: {k: hits / users}}, "users"}.
 alpha weighs the GNN retriever, 1 - alpha the sequence retriever.
 
@@ -24,13 +26,261 @@ would raise there). There is no CPU path: CPU tensors raise.
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
+import torch.nn as nn
 import torch.nn.functional as F
+from torch.nn.utils.rnn import pad_sequence
 
 from .. import ops
+from .v1_refine_usertower import encoder_stack
 
 SCORE_CHUNK_BYTES = 512 << 20   # bound of one [users, items] fp32 score matrix
+DROPOUT = 0.3                   # the reference's module constant (:30)
+
+
+# ----------------------------------------------------------------------------------------
+# HybridUserTower (:607-734) with its ParallelAdapter (:582-602) and SequenceCentricFusion (:514-577):
+# the model whose vectors are the sequence side of the evaluators below. In eval mode with gradients
+# off on the device it runs on csrc/hybrid.hip, the bf16x3 encoder stack (ReLU feed-forward) and
+# ops.linear / layer_norm / l2_normalize; in every other case (training, gradients, CPU, other widths,
+# L > 64) the plain PyTorch composition of the same modules runs. See DESIGN.md, section 4.
+def user_tower_collate_fn(batch):
+    """The reference's collate (:180-189): sequences RIGHT-padded with 0 by pad_sequence, seq_mask =
+    (seq_ids != 0), last_target = each sample's last target id (0 without targets)."""
+    stack = lambda k: torch.stack([b[k] for b in batch])  # noqa: E731
+    pad = lambda k: pad_sequence([b[k] for b in batch], batch_first=True, padding_value=0)  # noqa: E731
+    seq_ids, seq_deltas, target_ids = pad("seq_ids"), pad("seq_deltas"), pad("target_ids")
+    last_target = torch.tensor([b["target_ids"][-1] if len(b["target_ids"]) > 0 else 0 for b in batch],
+                               dtype=torch.long)
+    return (stack("user_idx"), stack("user_dense"), stack("user_cat"), seq_ids, seq_deltas, (seq_ids != 0).long(),
+            target_ids, last_target)
+
+
+class SequenceCentricFusion(nn.Module):
+    """v_seq + g_gnn gnn_proj(v_gnn) + g_meta meta_proj(v_meta) under final_ln: the sequence vector keeps
+    weight 1 and gates, by a sigmoid MLP of itself, how much of the two per-user vectors is added
+    (:514-577). The gate's last layer starts at weight 0, bias -5 (sigmoid(-5) ~ 0.007)."""
+
+    def __init__(self, dim=128):
+        super().__init__()
+        self.context_gate = nn.Sequential(nn.Linear(dim, 64), nn.GELU(), nn.Linear(64, 2), nn.Sigmoid())
+        self.gnn_proj = nn.Sequential(nn.Linear(dim, dim), nn.LayerNorm(dim), nn.Dropout(0.1))
+        self.meta_proj = nn.Sequential(nn.Linear(dim, dim), nn.LayerNorm(dim), nn.Dropout(0.1))
+        self.final_ln = nn.LayerNorm(dim)
+        nn.init.zeros_(self.context_gate[-2].weight)
+        nn.init.constant_(self.context_gate[-2].bias, -5.0)
+
+    def forward(self, v_gnn, v_seq, v_meta):
+        gates = self.context_gate(v_seq)
+        g_gnn, g_meta = gates[..., 0:1], gates[..., 1:2]
+        fused = v_seq + (g_gnn * self.gnn_proj(v_gnn)) + (g_meta * self.meta_proj(v_meta))
+        # the means run over every position, padded ones included, as the reference's
+        return self.final_ln(fused), [g_gnn.mean().item(), g_meta.mean().item()]
+
+
+class ParallelAdapter(nn.Module):
+    """(content_proj(c) + c) + gnn_proj(g): two Linear -> LayerNorm -> GELU -> Dropout branches over an
+    item's content row and its GNN row, the content row kept as a residual (:582-602)."""
+
+    def __init__(self, content_dim=128, gnn_dim=64, out_dim=128, dropout=0.2):
+        super().__init__()
+        self.content_proj = nn.Sequential(nn.Linear(content_dim, out_dim), nn.LayerNorm(out_dim), nn.GELU(),
+                                          nn.Dropout(dropout))
+        self.gnn_proj = nn.Sequential(nn.Linear(gnn_dim, out_dim), nn.LayerNorm(out_dim), nn.GELU(),
+                                      nn.Dropout(dropout))
+
+    def forward(self, v_content, v_gnn):
+        return (self.content_proj(v_content) + v_content) + self.gnn_proj(v_gnn)
+
+    def native_params(self):
+        c, g = self.content_proj, self.gnn_proj
+        return ops.AdapterParams(c[0].weight, c[0].bias, c[1].weight, c[1].bias, g[0].weight, g[0].bias, g[1].weight,
+                                 g[1].bias, c[1].eps)
+
+
+class HybridUserTower(nn.Module):
+    """Reference :607-734; construction order, sub-module names and state_dict as there."""
+
+    def __init__(self, num_users, num_items, gnn_user_init, gnn_item_init, item_content_init):
+        super().__init__()
+        self.embed_dim = 128
+        self.logit_scale = nn.Parameter(torch.ones([]) * np.log(1 / 0.07))
+        self.gnn_user_emb = nn.Embedding.from_pretrained(gnn_user_init, freeze=False)
+        self.gnn_item_emb = nn.Embedding.from_pretrained(gnn_item_init, freeze=False)
+        self.item_content_emb = nn.Embedding.from_pretrained(item_content_init, freeze=False)
+        self.gnn_projector = nn.Sequential(
+            nn.Linear(gnn_user_init.shape[1], 256), nn.LayerNorm(256), nn.GELU(), nn.Dropout(DROPOUT),
+            nn.Linear(256, 128), nn.LayerNorm(128))
+        self.seq_adapter = ParallelAdapter(content_dim=128, gnn_dim=64, out_dim=128, dropout=DROPOUT)
+        self.time_emb = nn.Embedding(1001, 128)
+        # no activation=: the layers' feed-forward is ReLU
+        encoder_layer = nn.TransformerEncoderLayer(d_model=128, nhead=2, dim_feedforward=512, dropout=DROPOUT,
+                                                   batch_first=True, norm_first=True)
+        self.seq_encoder = nn.TransformerEncoder(encoder_layer, num_layers=4, enable_nested_tensor=False)
+        self.channel_emb = nn.Embedding(2, 32)
+        self.meta_mlp = nn.Sequential(nn.Linear(35, 128), nn.GELU(), nn.Linear(128, 128), nn.LayerNorm(128))
+        self.fusion_layer = SequenceCentricFusion(dim=128)
+
+    def get_current_temperature(self, clamp_min):
+        """1 / clamp(exp(logit_scale), clamp_min, 100) (:652-664)."""
+        return 1.0 / self.logit_scale.exp().clamp(clamp_min, max=100.0)
+
+    def get_meta_feature_importance(self):
+        """Shares of the mean |weight| of meta_mlp[0] over the column ranges the reference names
+        (:712-734): 0:32, 32:64, 64:96, 96:112 (ranges past the layer's 35 inputs are empty there too)."""
+        w = self.meta_mlp[0].weight.abs().detach().cpu()
+        imp = {"Price": w[:, 0:32].mean().item(), "Count": w[:, 32:64].mean().item(),
+               "Recency": w[:, 64:96].mean().item(), "Channel": w[:, 96:112].mean().item()}
+        total = sum(imp.values()) + 1e-9
+        return {k: v / total for k, v in imp.items()}
+
+    # -- dispatch ---------------------------------------------------------------------------
+    def native_ok(self, seq_ids):
+        """The device path: eval mode, gradients off, device tensors, the reference's widths, L <= 64."""
+        layer = self.seq_encoder.layers[0]
+        return (not self.training and not torch.is_grad_enabled() and seq_ids.is_cuda
+                and self.item_content_emb.weight.is_cuda and seq_ids.dim() == 2
+                and 1 <= seq_ids.shape[1] <= ops.HYBRID_MAX_LEN
+                and self.item_content_emb.weight.shape[1] == 128 and self.gnn_item_emb.weight.shape[1] == 64
+                and self.item_content_emb.weight.dtype == torch.float32
+                and layer.self_attn.num_heads == 2 and layer.linear1.out_features == 512
+                and layer.self_attn.embed_dim == 128)
+
+    # -- the PyTorch composition (training, gradients, CPU) ------------------------------------
+    def _torch_seq_out(self, seq_ids, seq_deltas, seq_mask):
+        L = seq_ids.shape[1]
+        seq_input = self.seq_adapter(self.item_content_emb(seq_ids), self.gnn_item_emb(seq_ids))
+        seq_input = seq_input * math.sqrt(self.embed_dim) + self.time_emb(seq_deltas.clamp(max=1000))
+        causal = torch.triu(torch.full((L, L), float("-inf"), device=seq_ids.device), diagonal=1)
+        pad = seq_mask == 0
+        if bool(pad.all(dim=1).any()):
+            # a user without history: the reference's softmax over no key gives NaN; here such a row
+            # attends to nothing, as on the device path (csrc/mha.hip: a fully masked query gives zeros)
+            return self._torch_encoder_masked(seq_input, pad)
+        # the key mask as floats, which is what the encoder makes of the reference's boolean one
+        key_mask = torch.zeros_like(pad, dtype=causal.dtype).masked_fill(pad, float("-inf"))
+        return self.seq_encoder(seq_input, mask=causal, src_key_padding_mask=key_mask)
+
+    def _torch_encoder_masked(self, x, pad):
+        """The norm_first ReLU stack written out, with softmax rows that see no key set to zero."""
+        B, L, D = x.shape
+        allowed = torch.tril(torch.ones(L, L, dtype=torch.bool, device=x.device))[None] & ~pad[:, None, :]   # [B, q, k]
+        for layer in self.seq_encoder.layers:
+            sa = layer.self_attn
+            H, Dh = sa.num_heads, D // sa.num_heads
+            h = layer.norm1(x)
+            q, k, v = F.linear(h, sa.in_proj_weight, sa.in_proj_bias).view(B, L, 3, H, Dh).permute(2, 0, 3, 1, 4)
+            s = (q @ k.transpose(-1, -2)) / math.sqrt(Dh)
+            has_key = allowed[:, None].any(-1, keepdim=True)
+            s = torch.where(has_key, s.masked_fill(~allowed[:, None], float("-inf")), torch.zeros_like(s))
+            p = F.dropout(torch.softmax(s, dim=-1) * has_key, sa.dropout, self.training)
+            a = (p @ v).permute(0, 2, 1, 3).reshape(B, L, D)
+            x = x + layer.dropout1(sa.out_proj(a))
+            x = x + layer.dropout2(layer.linear2(layer.dropout(F.relu(layer.linear1(layer.norm2(x))))))
+        return x
+
+    def _torch_user_side(self, u_idx, u_dense, u_cat):
+        v_gnn = F.normalize(self.gnn_projector(self.gnn_user_emb(u_idx)), p=2, dim=1)
+        v_gnn = torch.zeros_like(v_gnn)   # reference :672: the GNN user vector is replaced by zeros
+        if self.training:                 # :673-681 (a scaled mask over zeros: still zeros)
+            keep = torch.bernoulli(torch.full((v_gnn.shape[0], 1), 0.6, device=v_gnn.device))
+            v_gnn = (v_gnn * keep) / 0.6
+        v_meta = self.meta_mlp(torch.cat([u_dense, self.channel_emb(u_cat)], dim=1))
+        return v_gnn, F.normalize(v_meta, p=2, dim=1)
+
+    def _torch_forward(self, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat):
+        L = seq_ids.shape[1]
+        v_gnn, v_meta = self._torch_user_side(u_idx, u_dense, u_cat)
+        v_seq = F.normalize(self._torch_seq_out(seq_ids, seq_deltas, seq_mask), p=2, dim=2)
+        output, gates = self.fusion_layer(v_gnn.unsqueeze(1).expand(-1, L, -1), v_seq,
+                                          v_meta.unsqueeze(1).expand(-1, L, -1))
+        return F.normalize(output, p=2, dim=2), v_seq, gates
+
+    # -- the device path ------------------------------------------------------------------------
+    def _native_seq_out(self, seq_ids, seq_deltas, seq_mask, merged=None):
+        B, L = seq_ids.shape
+        scale = math.sqrt(self.embed_dim)
+        if merged is None:
+            _, _, seq_in = ops.hybrid_adapter(self.item_content_emb.weight, self.gnn_item_emb.weight,
+                                              self.seq_adapter.native_params(), ids=seq_ids, deltas=seq_deltas,
+                                              time_tab=self.time_emb.weight, scale=scale, want_merged=False)
+        else:
+            first_row = self.item_content_emb.weight.shape[0] - merged.shape[0]
+            if first_row < 0:
+                raise ValueError(f"merged has {merged.shape[0]} rows, the item table {merged.shape[0] + first_row}")
+            seq_in = ops.hybrid_seq_gather(merged, seq_ids, seq_deltas, self.time_emb.weight, scale=scale,
+                                           first_row=first_row)
+        return encoder_stack(self.seq_encoder.layers, seq_in.view(B, L, self.embed_dim), seq_mask == 0, 0.0, False,
+                             causal=True, act="relu")
+
+    def _native_user_side(self, u_idx, u_dense, u_cat):
+        """(U_gnn, U_meta) [B, 128]: gnn_proj / meta_proj of the fusion applied to the per-user vectors.
+        The GNN vector is zero (:672), so its row is LayerNorm(gnn_proj's bias) for every user."""
+        B = u_idx.shape[0]
+        fl = self.fusion_layer
+        gp, mp = fl.gnn_proj, fl.meta_proj
+        u_gnn = ops.layer_norm(gp[0].bias.detach().view(1, -1), gp[1].weight, gp[1].bias, gp[1].eps).expand(B, -1)
+        m0, m2, mln = self.meta_mlp[0], self.meta_mlp[2], self.meta_mlp[3]
+        x = torch.cat([u_dense.to(torch.float32), self.channel_emb(u_cat)], dim=1)
+        k_pad = (-x.shape[1]) % 4                   # ops.linear reads K in multiples of 4: zero columns
+        h = ops.linear(F.pad(x, (0, k_pad)), F.pad(m0.weight.detach(), (0, k_pad)), m0.bias, ops.ACT_GELU)
+        v_meta = ops.l2_normalize(ops.layer_norm(ops.linear(h, m2.weight, m2.bias), mln.weight, mln.bias, mln.eps))
+        u_meta = ops.layer_norm(ops.linear(v_meta, mp[0].weight, mp[0].bias), mp[1].weight, mp[1].bias, mp[1].eps)
+        return u_gnn.contiguous(), u_meta
+
+    def _native_fuse(self, seq_out, u_gnn, u_meta, rows=None, want_v=True, want_gate=True):
+        fl = self.fusion_layer
+        g0, g2 = fl.context_gate[0], fl.context_gate[2]
+        return ops.hybrid_fuse(seq_out, u_gnn, u_meta, g0.weight, g0.bias, g2.weight, g2.bias, fl.final_ln.weight,
+                               fl.final_ln.bias, rows=rows, ln_eps=fl.final_ln.eps, want_v=want_v, want_gate=want_gate)
+
+    def forward(self, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat):
+        """(output [B, L, 128], v_seq [B, L, 128], [gnn_ratio, meta_ratio]); right-padded sequences."""
+        if not self.native_ok(seq_ids):
+            return self._torch_forward(u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat)
+        B, L = seq_ids.shape
+        seq_out = self._native_seq_out(seq_ids, seq_deltas, seq_mask)
+        u_gnn, u_meta = self._native_user_side(u_idx, u_dense, u_cat)
+        out, v, gate = self._native_fuse(seq_out, u_gnn, u_meta)
+        ratios = gate.tolist()        # Python floats, as .item() in the reference: the forward's one host read
+        ops._HYBRID_IDS.check()       # an id outside the tables raises here (encode_users: at a later call)
+        return out.view(B, L, -1), v.view(B, L, -1), ratios
+
+
+def hybrid_item_vectors(model, first_row=1):
+    """(merged [N, 128], unit [N, 128]) of item rows first_row .. of the model's tables: the adapter
+    over the whole table in one launch. unit = normalize(seq_adapter(content, gnn)) is the item side of
+    the reference's evaluators (:1038-1050, ids from 1); merged feeds encode_users."""
+    content, gnn = model.item_content_emb.weight, model.gnn_item_emb.weight
+    with torch.no_grad():
+        if not model.training and content.is_cuda and content.shape[1] == 128 and gnn.shape[1] == 64:
+            merged, unit, _ = ops.hybrid_adapter(content, gnn, model.seq_adapter.native_params(), first_row=first_row,
+                                                 want_unit=True)
+            return merged, unit
+        n = min(content.shape[0], gnn.shape[0])
+        merged = model.seq_adapter(content[first_row:n], gnn[first_row:n])
+        return merged, F.normalize(merged, p=2, dim=1)
+
+
+def encode_users(model, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat, merged=None):
+    """[B, 128]: the model's unit output at each user's last valid position, (len - 1).clamp(0) with
+    len = seq_mask.sum(1) (:1087-1095). No host read, no gate ratios. On the device path the fusion runs
+    on those B rows only and, with merged = hybrid_item_vectors(model)[0], the sequence input is a
+    gather from it (in eval mode the adapter's result depends on the item id alone)."""
+    B, L = seq_ids.shape
+    last = (seq_mask.sum(dim=1) - 1).clamp(min=0).to(torch.int64)
+    with torch.no_grad():
+        if not model.native_ok(seq_ids):
+            out, _, _ = model._torch_forward(u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat)
+            return out[torch.arange(B, device=out.device), last]
+        seq_out = model._native_seq_out(seq_ids, seq_deltas, seq_mask, merged)
+        u_gnn, u_meta = model._native_user_side(u_idx, u_dense, u_cat)
+        rows = torch.arange(B, device=last.device, dtype=torch.int64) * L + last
+        out, _, _ = model._native_fuse(seq_out, u_gnn, u_meta, rows=rows, want_v=False, want_gate=False)
+        return out
 
 
 def alpha_grid(alpha_step):

@@ -172,8 +172,9 @@ class SASRecDataset(torch.utils.data.Dataset):
 _ADDLN = os.environ.get("RSX_LINEAR_ADDLN", "1") != "0"
 
 
-def encoder_stack(layers, x, key_pad, p, training, causal=True, seg_off=None):
-    """norm_first nn.TransformerEncoderLayer stack (gelu), reference semantics
+def encoder_stack(layers, x, key_pad, p, training, causal=True, seg_off=None, act="gelu"):
+    """norm_first nn.TransformerEncoderLayer stack (act: "gelu", or "relu" for layers built without
+    activation=, as HybridUserTower's; see ops.ffn), reference semantics
     (v1_refine_usertower.py:343-352, item_tower.py:169-182):
       x = x + drop(out_proj(mha(norm1(x)))) ; x = x + drop(linear2(drop(gelu(linear1(norm2(x))))))
     Each residual add is fused with the LayerNorm that follows it (ops.add_layer_norm; after the
@@ -201,7 +202,7 @@ def encoder_stack(layers, x, key_pad, p, training, causal=True, seg_off=None):
             a = ops.linear_tok(a, sa.out_proj.weight, sa.out_proj.bias)
             x, h = ops.add_layer_norm(x, a, layer.norm2.weight, layer.norm2.bias, layer.norm2.eps, p)
         f = ops.ffn(h, layer.linear1.weight, layer.linear1.bias, layer.linear2.weight, layer.linear2.bias, p,
-                    training)
+                    training, act=act)
         if i + 1 < len(layers):
             nxt = layers[i + 1].norm1
             x, h = ops.add_layer_norm(x, f, nxt.weight, nxt.bias, nxt.eps, p)

@@ -1,0 +1,118 @@
+"""Micro-benchmark of HybridUserTower inference (tower_code/mined_inference.py) on seeded synthetic
+tables at the reference's scale (105k items, 4096 users per batch, L = 50): the device path against the
+module's own PyTorch composition (fp32, the same weights, eval mode, gradients off) on the same GPU,
+alternating in one loop after warm-up, each call between HIP events. Three lines:
+
+  * item_table     hybrid_item_vectors (the adapter over the whole item table, one launch) against
+                   normalize(seq_adapter(content, gnn)) in PyTorch;
+  * encode_users   encode_users with a precomputed merged table (gather, encoder stack, fusion of the B
+                   last rows) against the PyTorch forward followed by the pick of the last valid row;
+  * forward        the module's full forward (per-token adapter, fusion of all B L rows, gate ratios read
+                   on the host) against the PyTorch forward.
+Medians with min / max over the timed calls; "native_below_torch" tells whether the native range lies
+wholly below PyTorch's. Writes --out (profiles/hybrid_micro.json)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import recsys_amd  # noqa: E402,F401
+from recsys_amd import ops  # noqa: E402
+from recsys_amd.tower_code import mined_inference as MI  # noqa: E402
+
+
+def timed_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def summary(ms):
+    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "calls": len(ms)}
+
+
+def ab(native, plain, warmup, iters):
+    ours, theirs = [], []
+    with torch.no_grad():
+        for i in range(warmup + iters):
+            t0, t1 = timed_ms(native), timed_ms(plain)
+            if i >= warmup:
+                ours.append(t0)
+                theirs.append(t1)
+    return {"native": summary(ours), "torch": summary(theirs),
+            "speedup_over_torch": statistics.median(theirs) / statistics.median(ours),
+            "native_below_torch": max(ours) < min(theirs)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--items", type=int, default=105_000)
+    ap.add_argument("--users", type=int, default=4096, help="users per batch (and rows of the user table)")
+    ap.add_argument("--len", type=int, default=50)
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join("profiles", "hybrid_micro.json"))
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    g = torch.Generator().manual_seed(0)
+    B, L = a.users, a.len
+    torch.manual_seed(0)
+    model = MI.HybridUserTower(B, a.items, 0.5 * torch.randn(B, 64, generator=g),
+                               0.5 * torch.randn(a.items + 1, 64, generator=g),
+                               0.5 * torch.randn(a.items + 1, 128, generator=g))
+    with torch.no_grad():   # an open gate, so that the fusion's two branches carry weight
+        model.fusion_layer.context_gate[2].weight.normal_(0.0, 0.125, generator=g)
+        model.fusion_layer.context_gate[2].bias.zero_()
+    model = model.to(dev).eval()
+    lengths = torch.randint(1, L + 1, (B,), generator=g)
+    ids = torch.randint(1, a.items + 1, (B, L), generator=g) * (torch.arange(L)[None] < lengths[:, None])
+    deltas = torch.randint(0, 1200, (B, L), generator=g) * (ids != 0)
+    args = [t.to(dev) for t in (torch.arange(B), ids, deltas, (ids != 0).long(), torch.randn(B, 3, generator=g),
+                                torch.randint(0, 2, (B,), generator=g))]
+    last = (args[3].sum(1) - 1).clamp(min=0)
+    rows = torch.arange(B, device=dev)
+    content, gnn = model.item_content_emb.weight, model.gnn_item_emb.weight
+    result = {"items": a.items, "users": B, "len": L, "device": torch.cuda.get_device_name(0)}
+
+    result["item_table"] = ab(lambda: MI.hybrid_item_vectors(model),
+                              lambda: F.normalize(model.seq_adapter(content[1:], gnn[1:]), p=2, dim=1),
+                              a.warmup, a.iters)
+    with torch.no_grad():
+        merged, unit = MI.hybrid_item_vectors(model)
+        result["item_table"]["max_abs_diff_vs_torch"] = float(
+            (unit - F.normalize(model.seq_adapter(content[1:], gnn[1:]), p=2, dim=1)).abs().max())
+    result["item_table"]["bytes"] = a.items * (128 + 64 + 2 * 128) * 4
+    result["item_table"]["gbytes_per_s"] = (result["item_table"]["bytes"]
+                                            / (result["item_table"]["native"]["median_ms"] * 1e-3) / 1e9)
+    print(json.dumps({"item_table": result["item_table"]}), flush=True)
+
+    result["encode_users"] = ab(lambda: MI.encode_users(model, *args, merged=merged),
+                                lambda: model._torch_forward(*args)[0][rows, last], a.warmup, a.iters)
+    with torch.no_grad():
+        result["encode_users"]["max_abs_diff_vs_torch"] = float(
+            (MI.encode_users(model, *args, merged=merged) - model._torch_forward(*args)[0][rows, last]).abs().max())
+    print(json.dumps({"encode_users": result["encode_users"]}), flush=True)
+
+    result["forward"] = ab(lambda: model(*args), lambda: model._torch_forward(*args), a.warmup, a.iters)
+    with torch.no_grad():
+        ops.timing_start()
+        for _ in range(5):
+            model(*args)
+        result["forward"]["native_phase_ms"] = {k: v[1] / 5 for k, v in ops.timing_stop().items()}
+    print(json.dumps({"forward": result["forward"]}), flush=True)
+    ops._HYBRID_IDS.check()
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1, sort_keys=True)
+
+
+if __name__ == "__main__":
+    main()
