@@ -421,17 +421,28 @@ int rsx_step_index_fill(const uint8_t* pm, const int64_t* tgt, const int64_t* co
  * scores = U I^T (fp32 MFMA, never materialised), per query the k best items sorted by
  * (score desc, index asc). Replaces `scores = matmul(user, items.T); topk(k)` at
  * tower_code/v1_usertower_train.py:672-675 and temp_model/ranker_skelet.py:193-196.
- * U [Q, ldu], I [NI, ldi], D = 128, 1 <= k <= 512. ws: rsx_topk_workspace_bytes(Q, NI, k).
- * out_idx = -1 where fewer than k items exist. */
+ * U [Q, ldu], I [NI, ldi], D = 128, 1 <= k <= rsx_topk_max_k() = 2048. ws: rsx_topk_workspace_bytes(Q, NI, k).
+ * k <= 512: every corpus; out_idx = -1 where fewer than k items exist. 512 < k <= 2048: k <= NI, and
+ * only where rsx_topk_path returns 2 (NI >= 131,072 for k <= 1024, NI >= 262,144 beyond); elsewhere
+ * the call is an argument error (select from a materialised score matrix: rsx_select_topk_rows). */
 int64_t rsx_topk_workspace_bytes(int64_t Q, int64_t NI, int64_t k);
 int rsx_retrieve_topk(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t Q, int64_t NI, int64_t k,
                       void* ws, float* out_scores, int64_t* out_idx, void* stream);
 /* Which exact path a (Q, NI, k) call takes: 0 list kernels, 1 fp32 candidate/threshold path,
- * 2 bf16 single scan + exact fp32 rescoring (large corpora). Every call writes a workspace
+ * 2 bf16 single scan + exact fp32 rescoring (large corpora), 3 (k > 512 only) not served natively.
+ * Every call writes a workspace
  * header: int32 ws[0] = queries path 2 sent to the exact kernels, ws[1] = path id, ws[2] = path
  * 1's whole-batch fallback flag. Path 2 runs the queries in chunks of at most 4096 (workspace
- * bounded in Q). */
+ * bounded in Q). Its exact kernels for listed queries are the list kernels for k <= 512 and, for
+ * k > 512, fp32 score rows in a scratch of at most 256 MB (whatever Q is) with a radix select per row. */
 int rsx_topk_path(int64_t Q, int64_t NI, int64_t k);
+/* Path 2's capacities: the largest k; entries per lane stream of the collect pass; collected entries
+ * per query; entries of the rescored margin set for a given k. A query that exceeds one of them
+ * runs on the exact kernels. */
+int64_t rsx_topk_max_k(void);
+int64_t rsx_topk_stream_capacity(void);
+int64_t rsx_topk_entry_capacity(void);
+int64_t rsx_topk_margin_capacity(int64_t k);
 /* Path 2 with a caller-cached corpus image (a static corpus, e.g. the serving item matrix of
  * controller.py:62-124 or evaluate_model's normalised item table, :672): rsx_topk_prepare_corpus
  * writes max ||w||, max ||w - bf16(w)|| and the bf16 image of I into `corpus` (rsx_topk_corpus_bytes(NI) bytes) once;

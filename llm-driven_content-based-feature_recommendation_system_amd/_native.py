@@ -128,6 +128,10 @@ _SIGS = {
     "rsx_topk_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "rsx_retrieve_topk": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
     "rsx_topk_path": (c_i, [c_i64, c_i64, c_i64]),
+    "rsx_topk_max_k": (c_i64, []),
+    "rsx_topk_stream_capacity": (c_i64, []),
+    "rsx_topk_entry_capacity": (c_i64, []),
+    "rsx_topk_margin_capacity": (c_i64, [c_i64]),
     "rsx_ids_check": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p]),
     "rsx_step_index_workspace_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "rsx_step_index_count": (c_i, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p]),

@@ -439,7 +439,8 @@ __global__ __launch_bounds__(256) void topk_final_k(const float* bs, const int* 
 //     entry with a >= a_k - 2 delta (the only ones that can reach the exact k-th) is rescored in
 //     fp32 and sorted by (e desc, index asc); the first k are written. A stream buffer overflow or
 //     more than kSelMax entries sends the query to the exact list-based kernels above (a device
-//     list of query ids; their grid exits past its count: no host sync).
+//     list of query ids; their grid exits past its count: no host sync). For 512 < k <= 2048, beyond
+//     those kernels' KMAX, the listed queries go to topk_fb_scores_k / topk_fb_select_k below.
 using rsx::bf16x8, rsx::u32x4;
 constexpr int kImgStride = 272;   // bytes per staged item row: 256 + 16 (conflict-free ds_read_b128)
 constexpr int kStreamCap = 32;    // P3 entries per lane stream
@@ -932,7 +933,15 @@ __global__ __launch_bounds__(256) void topk_bf16_thresh_k(const float* __restric
 // margin set {a >= a_k - 2 delta}, rescore it exactly in fp32, sort it by (e desc, idx asc) and
 // write the first k. (The margin set's order before the final sort does not matter: (e, idx)
 // pairs are distinct, so the output is deterministic.)
+// Two instantiations: MARGIN = kMarginMax (k <= 512: static LDS, three workgroups per CU) and MARGIN =
+// kMarginMaxLarge (512 < k <= 2048: the margin set must hold k plus the 2 delta band, so ss / ms / mi
+// come to 64 KB and live in dynamic LDS, kSelectLargeLds bytes raised by hipFuncSetAttribute; two
+// workgroups per CU). Everything else is shared: the stream and entry capacities are sized by the
+// expected load, which thr_rank keeps near k + band for k > 512 (see bf_plan).
 constexpr int kMarginMax = 2048;
+constexpr int kMarginMaxLarge = 4096;
+constexpr size_t kSelectLargeLds = (size_t)kSelMax * 4 + (size_t)kMarginMaxLarge * 8;
+template <int MARGIN>
 __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restrict__ be,
                                                           const int* __restrict__ bn, int nstreams,
                                                           const float* __restrict__ U, int64_t ldu,
@@ -942,9 +951,21 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
                                                           int* qmap, int* qtotal) {
   // LDS: the appended scores only (their item ids are read back from global for the margin set),
   // so three workgroups fit per CU
-  __shared__ __attribute__((aligned(16))) float ss[kSelMax];
-  __shared__ __attribute__((aligned(16))) float ms[kMarginMax];
-  __shared__ __attribute__((aligned(16))) int mi[kMarginMax];
+  float *ss, *ms;
+  int* mi;
+  if constexpr (MARGIN == kMarginMax) {
+    __shared__ __attribute__((aligned(16))) float ss_s[kSelMax];
+    __shared__ __attribute__((aligned(16))) float ms_s[kMarginMax];
+    __shared__ __attribute__((aligned(16))) int mi_s[kMarginMax];
+    ss = ss_s; ms = ms_s; mi = mi_s;
+  } else {
+    // the statics below (3,136 B, a multiple of 16) precede this region; with n >= k > 512 the only
+    // LDS accesses wider than 32 bits, the rank sort's, never run in this instantiation
+    extern __shared__ __attribute__((aligned(16))) unsigned char sel_lds[];
+    ss = reinterpret_cast<float*>(sel_lds);
+    ms = ss + kSelMax;
+    mi = reinterpret_cast<int*>(ms + MARGIN);
+  }
   __shared__ int off[513];
   __shared__ int hist[256], sel[2];
   __shared__ unsigned red[8];
@@ -1032,13 +1053,13 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
     for (int e = 0; e < cn; ++e) {
       if (ss[o + e] >= thr) {
         const int slot = atomicAdd(&nsel_s, 1);
-        if (slot < kMarginMax) mi[slot] = st * kStreamCap + e;
+        if (slot < MARGIN) mi[slot] = st * kStreamCap + e;
       }
     }
   }
   __syncthreads();
   const int n = nsel_s;
-  if (n > kMarginMax) {  // block-uniform: the exact kernels take this query
+  if (n > MARGIN) {  // block-uniform: the exact kernels take this query
     if (tid == 0) {
       qmap[atomicAdd(qcount, 1)] = (int)q;
       atomicAdd(qtotal, 1);
@@ -1046,15 +1067,15 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
     return;
   }
   {
-    int ids[kMarginMax / 256];
+    int ids[MARGIN / 256];
 #pragma unroll
-    for (int u = 0; u < kMarginMax / 256; ++u) {
+    for (int u = 0; u < MARGIN / 256; ++u) {
       const int t = tid + 256 * u;
       ids[u] = t < n ? __float_as_int(be[q * nstreams * kStreamCap + mi[t]].y) : 0;
     }
     __syncthreads();  // every slot read before any is overwritten
 #pragma unroll
-    for (int u = 0; u < kMarginMax / 256; ++u) {
+    for (int u = 0; u < MARGIN / 256; ++u) {
       const int t = tid + 256 * u;
       if (t < n) mi[t] = ids[u];
     }
@@ -1131,6 +1152,181 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
   }
 }
 
+// ---- exact fallback of the bf16 path for 512 < k <= 2048 (the list kernels above stop at KMAX = 512) ----
+// Serves only the queries P4 listed (qmap / qcount), kFbRows-bounded batches of them at a time, with
+// no host read: every launch reads the device count and exits past it.
+// topk_fb_scores_k: the fp32 score rows of listed queries [row0, row0 + nrows) into the scratch S
+//     [nrows][lds]; every item row is read once per group of kFbGroup queries, each dot product in the
+//     order of P4's rescoring (32 lanes x float4, xor-shuffle reduction).
+// topk_fb_select_k: one workgroup per row. The 64-bit keys score_key(e) << 32 | ~j are distinct and
+//     order as (e desc, j asc; -0.0 ties +0.0), so the k-th largest key (8-bit radix select from the
+//     highest bit in which the keys differ, as block_kth_largest) is a threshold with exactly k keys at
+//     or above it: no tie handling. They are gathered, sorted in LDS and written with their scores.
+constexpr int kFbGroup = 8;                      // listed queries per workgroup of topk_fb_scores_k
+constexpr int64_t kFbScratchBytes = 256ll << 20;  // bound of the score scratch (or one row, if larger)
+constexpr int kLargeKMax = 2048;
+
+__global__ __launch_bounds__(256) void topk_fb_scores_k(const int* __restrict__ qmap, const int* __restrict__ qcount,
+                                                        int row0, int nrows, const float* __restrict__ U, int64_t ldu,
+                                                        const float* __restrict__ I, int64_t ldi, int64_t NI,
+                                                        float* __restrict__ S, int64_t lds) {
+  const int cnt = *qcount;
+  const int g0 = blockIdx.y * kFbGroup;  // first row of this group within the batch
+  if (row0 + g0 >= cnt) return;          // whole workgroup: no listed query here
+  const int lane = threadIdx.x & 63, c = lane & 31;
+  const int hw = threadIdx.x >> 5;       // half-wave 0..7: one item each per step
+  float4 u4[kFbGroup];
+  bool ok[kFbGroup];
+#pragma unroll
+  for (int r = 0; r < kFbGroup; ++r) {
+    ok[r] = g0 + r < nrows && row0 + g0 + r < cnt;
+    u4[r] = ok[r] ? reinterpret_cast<const float4*>(U + (int64_t)qmap[row0 + g0 + r] * ldu)[c]
+                  : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  for (int64_t j0 = (int64_t)blockIdx.x * 32; j0 < NI; j0 += (int64_t)gridDim.x * 32) {
+    float4 w4[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int64_t j = j0 + 8 * v + hw;
+      w4[v] = j < NI ? reinterpret_cast<const float4*>(I + j * ldi)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int64_t j = j0 + 8 * v + hw;
+#pragma unroll
+      for (int r = 0; r < kFbGroup; ++r) {
+        float e = u4[r].x * w4[v].x + u4[r].y * w4[v].y + u4[r].z * w4[v].z + u4[r].w * w4[v].w;
+        for (int o = 16; o > 0; o >>= 1) e += __shfl_xor(e, o, 64);
+        if (ok[r] && c == 0 && j < NI) S[(int64_t)(g0 + r) * lds + j] = e;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(1024) void topk_fb_select_k(const int* __restrict__ qmap, const int* __restrict__ qcount,
+                                                         int row0, const float* __restrict__ S, int64_t lds,
+                                                         int64_t NI, int K, float* out_s, int64_t* out_i) {
+  typedef unsigned long long u64;
+  __shared__ u64 keys[kLargeKMax];
+  __shared__ int hist[256], sel[2], nsel_s;
+  __shared__ unsigned red[32];
+  const int ql = row0 + (int)blockIdx.x;
+  if (ql >= *qcount) return;
+  const int64_t q = qmap[ql];
+  const float* row = S + (int64_t)blockIdx.x * lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  auto key = [&](int64_t j) { return ((u64)rsx::score_key(row[j]) << 32) | (u64)(~(unsigned)j); };
+  // the highest differing bit: of the score keys, or (all scores equal) of the item ids
+  unsigned kmin = 0xffffffffu, kmax = 0u;
+  for (int64_t j = tid; j < NI; j += 1024) {
+    const unsigned k = rsx::score_key(row[j]);
+    kmin = min(kmin, k);
+    kmax = max(kmax, k);
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o, 64));
+    kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
+  }
+  if (lane == 0) {
+    red[wave] = kmin;
+    red[16 + wave] = kmax;
+  }
+  if (tid == 0) nsel_s = 0;
+  __syncthreads();
+  for (int w = 0; w < 16; ++w) {
+    kmin = min(kmin, red[w]);
+    kmax = max(kmax, red[16 + w]);
+  }
+  int hb;  // in the 64-bit key
+  u64 prefix;
+  if (kmin != kmax) {
+    hb = 32 + (31 - __clz((int)(kmin ^ kmax)));
+    prefix = (u64)kmin << 32;
+  } else {
+    hb = NI > 1 ? 31 - __clz((int)(unsigned)(NI - 1)) : 0;  // ~j differs only below this bit's top
+    prefix = ((u64)kmin << 32) | 0xffffffffull;
+  }
+  u64 mask = hb == 63 ? 0ull : ~((2ull << hb) - 1ull);
+  prefix &= mask;
+  int krem = K;
+  for (int top = hb; top >= 0; top -= 8) {
+    const int lo = top >= 7 ? top - 7 : 0;
+    const u64 dm = (2ull << (top - lo)) - 1ull;
+    for (int t = tid; t < 256; t += 1024) hist[t] = 0;
+    __syncthreads();
+    for (int64_t j = tid; j < NI; j += 1024) {
+      const u64 k = key(j);
+      if ((k & mask) == prefix) atomicAdd(&hist[(int)((k >> lo) & dm)], 1);
+    }
+    __syncthreads();
+    if (tid < 64) {  // lane l owns digits 255-4l .. 252-4l (descending), as block_kth_largest
+      int c4[4], sum = 0;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        c4[u] = hist[255 - 4 * tid - u];
+        sum += c4[u];
+      }
+      int incl = sum;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(incl, o, 64);
+        if (tid >= o) incl += y;
+      }
+      const int excl = incl - sum;
+      if (excl < krem && krem <= incl) {
+        int acc = excl;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          if (acc + c4[u] >= krem) {
+            sel[0] = 255 - 4 * tid - u;
+            sel[1] = krem - acc;
+            break;
+          }
+          acc += c4[u];
+        }
+      }
+    }
+    __syncthreads();
+    prefix |= (u64)sel[0] << lo;
+    mask |= dm << lo;
+    krem = sel[1];
+    __syncthreads();  // sel / hist are rewritten by the next pass
+  }
+  // prefix is the k-th largest key: exactly K keys reach it (K <= NI, host-checked)
+  for (int64_t j = tid; j < NI; j += 1024) {
+    const u64 k = key(j);
+    if (k >= prefix) {
+      const int slot = atomicAdd(&nsel_s, 1);
+      if (slot < kLargeKMax) keys[slot] = k;
+    }
+  }
+  int P2 = 2;
+  while (P2 < K) P2 <<= 1;
+  __syncthreads();
+  for (int t = K + tid; t < P2; t += 1024) keys[t] = 0ull;  // below every real key
+  __syncthreads();
+  for (int size = 2; size <= P2; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (tid < P2 / 2) {
+        const int lo = 2 * tid - (tid & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = ((lo & size) == 0);
+        const u64 a0 = keys[lo], a1 = keys[hi];
+        if (desc ? a1 > a0 : a0 > a1) {
+          keys[lo] = a1;
+          keys[hi] = a0;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int t = tid; t < K; t += 1024) {
+    const unsigned id = ~(unsigned)keys[t];
+    out_s[q * K + t] = row[id];
+    out_i[q * K + t] = (int64_t)id;
+  }
+}
+
 constexpr int kFastCap = 2048;
 
 struct FastPlan {
@@ -1172,7 +1368,12 @@ BfPlan bf_plan(int64_t Q, int64_t NI, int64_t k) {
   while (S < 16 && k * (int64_t)S * 2 <= 8 * (int64_t)ns) S *= 2;
   p.sample = S;
   // the sample's candidates must hold k items: 2 nsplit T >= 2 k
-  p.use = NI > 16384 && k <= 512 && 2 * ns * p.T >= 2 * k;
+  // 512 < k <= 2048 takes the same plan: nsplit >= k / 8 then asks for NI >= 131,072 up to k = 1024 and
+  // NI >= 262,144 beyond. There S <= 2 and thr_rank gives r = k (no P4 check), so about S k items lie
+  // above c_k and the collect pass appends those plus the 2 delta band: ~2500 entries per query at
+  // k = 2048 / 1M items, ~5 per stream against kStreamCap = 32 (a Poisson tail below 1e-13 per
+  // stream) and well inside kSelMax. The capacity k outgrows is the margin set's (kMarginMaxLarge).
+  p.use = NI > 16384 && k <= kLargeKMax && 2 * ns * p.T >= 2 * k;
   return p;
 }
 
@@ -1214,7 +1415,17 @@ int choose_nsplit(int64_t Q, int64_t NI, int kmax) {
 }  // namespace
 
 namespace {
+// 512 < k <= 2048: the score scratch of topk_fb_scores_k / topk_fb_select_k, fb_rows(Q, NI) rows of
+// fb_ld(NI) floats: at most kFbScratchBytes = 256 MB whatever Q is (one row where a row alone is
+// larger, NI > 64M), half the 512-MB score chunk of the materialised evaluators.
+int64_t fb_ld(int64_t NI) { return (NI + 63) / 64 * 64; }
+int64_t fb_rows(int64_t Q, int64_t NI) {
+  int64_t f = kFbScratchBytes / (fb_ld(NI) * 4);
+  if (f < 1) f = 1;
+  return f < Q ? f : Q;
+}
 int64_t old_ws_bytes(int64_t Q, int64_t NI, int64_t k) {
+  if (k > 512) return fb_rows(Q, NI) * fb_ld(NI) * 4;
   const int kmax = k <= 128 ? 128 : 512;
   const int ns = choose_nsplit(Q, NI, kmax);
   return Q * ns * 2 * (int64_t)kmax * 8;
@@ -1247,7 +1458,9 @@ FastLayout fast_layout(int64_t Q, int64_t NI, int64_t k, const FastPlan& p) {
 // The bf16 path's corpus image (rsx_topk_prepare_corpus: a 256-byte header holding the bits of
 // max ||w|| and max ||w - bf16(w)||,
 // then the [NI][128] bf16 image) either lives in the caller's cached buffer or is built into the
-// workspace per call. Queries run in chunks of at most kQChunk (workspace bounded in Q).
+// workspace per call. Queries run in chunks of at most kQChunk (workspace bounded in Q). The exact
+// fallback of a chunk reuses its candidate / stream-buffer region: the list kernels' lists for
+// k <= 512, for k > 512 a score scratch of at most kFbScratchBytes = 256 MB independent of Q (fb_rows).
 constexpr int64_t kHeader = 256;
 constexpr int64_t kQChunk = 4096;
 int64_t corpus_bytes(int64_t NI) { return kHeader + align256(NI * kD * 2); }
@@ -1267,7 +1480,8 @@ BfLayout bf_layout(int64_t Qc, int64_t NI, int64_t k, const BfPlan& p, bool own_
   L.buf_n = L.buf_e + align256(nstream * kStreamCap * 8);
   const int64_t end = L.buf_n + align256(nstream * 4);
   // the exact kernels for the chunk's listed queries run after its P4: they reuse the
-  // candidate / stream-buffer region (never the corpus image, which later chunks still read)
+  // candidate / stream-buffer region (never the corpus image, which later chunks still read).
+  // k <= 512: the list kernels' [Qc][nsplit][2][KMAX] lists; k > 512: the score scratch (fb_rows)
   L.fallback = L.cand_s;
   const int64_t fb_end = L.fallback + old_ws_bytes(Qc, NI, k);
   L.total = (end > fb_end ? end : fb_end) + 256;
@@ -1312,9 +1526,32 @@ void launch_fast_scans(FastArgs f, int blocks, int mode, hipStream_t st) {
 }  // namespace
 
 namespace {
+constexpr int kPathNone = 3;  // 512 < k <= 2048 on a corpus too small for the bf16 plan: not served here
 int topk_path(int64_t Q, int64_t NI, int64_t k) {
   if (bf_plan(Q < kQChunk ? Q : kQChunk, NI, k).use) return 2;
+  if (k > 512) return kPathNone;
   return fast_plan(Q, NI, k).use ? 1 : 0;
+}
+
+// the exact fallback for 512 < k <= 2048: the chunk's listed queries, fb_rows at a time; launches past
+// the device count exit at once
+int launch_fb_large(const float* U, int64_t ldu, const float* I, int64_t ldi, int64_t Q, int64_t NI, int64_t k,
+                    char* ws, float* out_scores, int64_t* out_idx, hipStream_t st, const int* qmap,
+                    const int* qcount) {
+  float* S = reinterpret_cast<float*>(ws);
+  const int64_t F = fb_rows(Q, NI), ld = fb_ld(NI);
+  int64_t gx = (NI + 31) / 32;
+  if (gx > 1024) gx = 1024;
+  for (int64_t row0 = 0; row0 < Q; row0 += F) {
+    const int64_t nr = Q - row0 < F ? Q - row0 : F;
+    hipLaunchKernelGGL(topk_fb_scores_k, dim3((unsigned)gx, (unsigned)((nr + kFbGroup - 1) / kFbGroup)), dim3(256), 0,
+                       st, qmap, qcount, (int)row0, (int)nr, U, ldu, I, ldi, NI, S, ld);
+    RSX_LAUNCHED();
+    hipLaunchKernelGGL(topk_fb_select_k, dim3((unsigned)nr), dim3(1024), 0, st, qmap, qcount, (int)row0, S, ld, NI,
+                       (int)k, out_scores, out_idx);
+    RSX_LAUNCHED();
+  }
+  return 0;
 }
 
 void launch_prep(const float* I, int64_t ldi, int64_t NI, char* corpus, hipStream_t st) {
@@ -1385,7 +1622,21 @@ int run_bf16_chunk(const BfPlan& bp, const BfLayout& L, const float* U, int64_t 
   if (bp.G == 2) hipLaunchKernelGGL(topk_bf16_collect_k<2>, grid, dim3(256), 0, st, b);
   else hipLaunchKernelGGL(topk_bf16_collect_k<1>, grid, dim3(256), 0, st, b);
   RSX_LAUNCHED();
-  hipLaunchKernelGGL(topk_bf16_select_k, dim3((unsigned)Q), dim3(256), 0, st, b.buf_e, b.buf_n,
+  if (k > 512) {
+    static const hipError_t raised =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(topk_bf16_select_k<kMarginMaxLarge>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSelectLargeLds);
+    if (raised != hipSuccess) {
+      rsx::set_error("retrieve_topk: cannot raise the LDS limit: %s", hipGetErrorString(raised));
+      return (int)raised;
+    }
+    hipLaunchKernelGGL(topk_bf16_select_k<kMarginMaxLarge>, dim3((unsigned)Q), dim3(256), kSelectLargeLds, st,
+                       b.buf_e, b.buf_n, bp.nsplit * 2, U, ldu, I, ldi, (int)k, wmax, thr, r < k ? 1 : 0, out_scores,
+                       out_idx, qcount, qmap, qtotal);
+    RSX_LAUNCHED();
+    return launch_fb_large(U, ldu, I, ldi, Q, NI, k, w + L.fallback, out_scores, out_idx, st, qmap, qcount);
+  }
+  hipLaunchKernelGGL(topk_bf16_select_k<kMarginMax>, dim3((unsigned)Q), dim3(256), 0, st, b.buf_e, b.buf_n,
                      bp.nsplit * 2, U, ldu, I, ldi, (int)k, wmax, thr, r < k ? 1 : 0, out_scores, out_idx, qcount,
                      qmap, qtotal);
   RSX_LAUNCHED();
@@ -1400,18 +1651,23 @@ int64_t ws_bytes(int64_t Q, int64_t NI, int64_t k, bool own_corpus) {
     return bf_layout(Qc, NI, k, bf_plan(Qc, NI, k), own_corpus).total;
   }
   if (path == 1) return fast_layout(Q, NI, k, fast_plan(Q, NI, k)).total;
+  if (path == kPathNone) return 2 * kHeader;  // the header only: rsx_retrieve_topk refuses the call
   return kHeader + old_ws_bytes(Q, NI, k) + 256;
 }
 
 int retrieve(const float* U, int64_t ldu, const float* I, int64_t ldi, const void* corpus_in, int64_t Q, int64_t NI,
              int64_t k, void* ws, float* out_scores, int64_t* out_idx, void* stream) {
   RSX_ARG(U && I && ws && out_scores && out_idx, "null tensor");
-  RSX_ARG(k >= 1 && k <= 512, "k must be in [1,512]");
+  RSX_ARG(k >= 1 && k <= kLargeKMax, "k must be in [1,2048]");
+  RSX_ARG(k <= 512 || k <= NI, "k above 512 must not exceed the item count");
   RSX_ARG(ldu >= kD && ldi >= kD && ldu % 4 == 0 && ldi % 4 == 0, "D must be 128 (row strides >= 128)");
   RSX_ARG(NI < 0x7fffffff, "item count must fit int32");
   hipStream_t st = (hipStream_t)stream;
   char* w = reinterpret_cast<char*>(ws);
   const int path = topk_path(Q, NI, k);
+  RSX_ARG(path != kPathNone,
+          "k in (512, 2048] needs a corpus the bf16 scan's plan serves: at least 131,072 items for k <= 1024 and "
+          "262,144 beyond (rsx_topk_path returns 3); select from a materialised score matrix instead");
   (void)hipMemsetAsync(w, 0, 16, st);
   (void)hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w + 4), path, 1, st);
   if (Q == 0) return 0;
@@ -1476,6 +1732,12 @@ int retrieve(const float* U, int64_t ldu, const float* I, int64_t ldi, const voi
 }  // namespace
 
 RSX_API int rsx_topk_path(int64_t Q, int64_t NI, int64_t k) { return topk_path(Q, NI, k); }
+
+// capacities of the bf16 path, for callers that size inputs against them (tests of the fallback)
+RSX_API int64_t rsx_topk_max_k(void) { return kLargeKMax; }
+RSX_API int64_t rsx_topk_stream_capacity(void) { return kStreamCap; }
+RSX_API int64_t rsx_topk_entry_capacity(void) { return kSelMax; }
+RSX_API int64_t rsx_topk_margin_capacity(int64_t k) { return k <= 512 ? kMarginMax : kMarginMaxLarge; }
 
 RSX_API int64_t rsx_topk_workspace_bytes(int64_t Q, int64_t NI, int64_t k) { return ws_bytes(Q, NI, k, true); }
 

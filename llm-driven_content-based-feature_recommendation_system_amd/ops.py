@@ -2906,19 +2906,57 @@ def clear_retrieval_cache(device=None) -> None:
         _TOPK_CORPUS.pop(torch.device(device), None)
 
 
+RETRIEVE_TOPK_MAX = 2048  # rsx_topk_max_k(): largest k of retrieve_topk
+_TOPK_NOT_NATIVE = 3      # rsx_topk_path: 512 < k <= 2048 on a corpus the bf16 plan does not serve
+
+
+def _retrieve_topk_materialised(q, it, k):
+    """retrieve_topk's composition where the fused scan does not apply: fp32 score chunks of at most
+    the evaluators' SCORE_CHUNK_BYTES by torch.matmul, each selected by select_topk_rows."""
+    from .tower_code.mined_inference import SCORE_CHUNK_BYTES
+    Q, NI = q.shape[0], it.shape[0]
+    sc = torch.empty(Q, k, device=q.device, dtype=torch.float32)
+    ix = torch.empty(Q, k, device=q.device, dtype=torch.int64)
+    w = it[:, :q.shape[1]].to(torch.float32)
+    step = max(1, SCORE_CHUNK_BYTES // (4 * NI))
+    for s in range(0, Q, step):
+        idx, val = select_topk_rows(torch.matmul(q[s:s + step], w.T), k)
+        sc[s:s + step], ix[s:s + step] = val, idx
+    return sc, ix
+
+
 def retrieve_topk(queries, items, k, diag=None):
-    """(scores [Q, k] desc, indices [Q, k] int64) of queries @ items.T without materialising
-    the score matrix. Ties resolve to the lower item index. D = 128.
-    Large corpora take the bf16 single scan + exact fp32 rescoring (path "bf16"), whose corpus
-    image is cached across calls (_topk_corpus). diag: optional dict; receives "path" ("list" /
-    "fast" / "bf16"), "fallback" (bool) and "fallback_queries" (int): how many queries the
-    path's exactness check sent to the exact list-based kernels (the "fast" path re-runs the
-    whole batch; one host sync, for tests / diagnostics)."""
+    """(scores [Q, k] desc, indices [Q, k] int64) of queries @ items.T. Ties resolve to the lower
+    item index. D = 128. Exact for 1 <= k <= min(NI, RETRIEVE_TOPK_MAX = 2048); a k outside that
+    range raises ValueError before any device work (k <= 512 may exceed NI: the missing places hold
+    index -1). Three behaviours:
+      * k <= 512: the score matrix is never formed. Large corpora take the bf16 single scan + exact
+        fp32 rescoring (path "bf16"), whose corpus image is cached across calls (_topk_corpus);
+        small ones the fp32 paths ("list" / "fast").
+      * 512 < k <= 2048 where the bf16 scan's plan applies (rsx_topk_path == 2: NI >= 131,072 for
+        k <= 1024, NI >= 262,144 beyond): the same scan with a larger margin set; a query that fails
+        its exactness check is served from fp32 score rows in a bounded scratch.
+      * 512 < k <= 2048 on smaller corpora: fp32 score chunks by torch.matmul (at most
+        SCORE_CHUNK_BYTES each) selected by select_topk_rows (path "materialised").
+    diag: optional dict; receives "path" ("list" / "fast" / "bf16" / "materialised"), "fallback"
+    (bool) and "fallback_queries" (int): how many queries the path's exactness check sent to the
+    exact kernels (the "fast" path re-runs the whole batch; one host sync, for tests /
+    diagnostics)."""
+    k = int(k)
+    NI = items.shape[0]
+    if not 1 <= k <= RETRIEVE_TOPK_MAX or (k > 512 and k > NI):
+        raise ValueError(f"retrieve_topk: k={k} out of range for {NI} items "
+                         f"(1 <= k <= min(items, {RETRIEVE_TOPK_MAX}); k <= 512 may exceed the item count)")
     N.ensure_device(queries)
     q = _c(queries.to(torch.float32))
     it = items if (items.stride(-1) == 1 and items.stride(0) % 4 == 0) else items.contiguous()
-    Q, NI = q.shape[0], it.shape[0]
+    Q = q.shape[0]
     path = N.lib().rsx_topk_path(Q, NI, k)
+    if path == _TOPK_NOT_NATIVE:
+        sc, ix = _retrieve_topk_materialised(q, it, k)
+        if diag is not None:
+            diag["path"], diag["fallback"], diag["fallback_queries"] = "materialised", False, 0
+        return sc, ix
     corpus = _topk_corpus(it) if path == 2 and Q > 0 else None
     nws = (N.lib().rsx_topk_workspace_bytes_corpus(Q, NI, k) if corpus is not None
            else N.lib().rsx_topk_workspace_bytes(Q, NI, k))

@@ -17,8 +17,10 @@ HybridUserTower as in the reference's main, or SASRecUserTower, with the distill
 {"best_alpha", "hits": {alpha: {k: users hit}}, "recall": {alpha: {k: hits / users}}, "users"}.
 alpha weighs the GNN retriever, 1 - alpha the sequence retriever.
 
-Compute: per chunk of users the two score matrices come from fp32 torch.matmul, each pool from
-ops.select_topk_rows, and the fusion, the alpha sweep and the hit test of the chunk from one
+Compute: on corpora of at least FUSED_POOL_MIN_ITEMS items each retriever's pools come from
+ops.retrieve_topk (the fused bf16 scan with exact rescoring: no score matrix, chunks of batch_size
+users); on smaller ones, per chunk of users the two score matrices come from fp32 torch.matmul and each
+pool from ops.select_topk_rows. The fusion, the alpha sweep and the hit test of the chunk from one
 ops.fuse_rank launch (csrc/ensemble.hip); the ratio merge takes two ops.retrieve_topk lists and two
 ops.first_hit. Hit counts accumulate on the device and are read once per evaluation. One clamp is ours:
 the number of fused entries kept, max_k + 20 in the reference, is min(pool entries, max_k + 20) (torch.topk
@@ -38,6 +40,11 @@ from .. import ops
 from .v1_refine_usertower import encoder_stack
 
 SCORE_CHUNK_BYTES = 512 << 20   # bound of one [users, items] fp32 score matrix
+# Corpus size from which _evaluate_fused takes its pools from ops.retrieve_topk (the fused bf16 scan
+# for pools above 512) and not from a materialised score matrix: the smallest measured size from which
+# the fused form's range lies wholly below the materialised form's (profiles/ensemble_pool_switch.json,
+# DESIGN.md section 4), and never below the smallest corpus the scan's plan serves at these pools.
+FUSED_POOL_MIN_ITEMS = 131_072
 DROPOUT = 0.3                   # the reference's module constant (:30)
 
 
@@ -397,12 +404,25 @@ def _evaluate_fused(fn, mode, seq_user_vecs, seq_item_vecs, gnn_user_vecs, gnn_i
         users_d = torch.tensor(users, dtype=torch.long, device=dev)
         counts = torch.zeros(len(alphas), len(ks), device=dev, dtype=torch.int64)
         flag = torch.zeros(1, device=dev, dtype=torch.int32)
-        step = _chunk_rows(batch_size, n_items)
+        fused = n_items >= FUSED_POOL_MIN_ITEMS and len(users) > 0
+        if fused:
+            # no score matrix bounds the chunk; one retriever's pools for every chunk first, then the
+            # other's, so that the two corpora do not evict each other's cached bf16 image per chunk
+            step = max(1, int(batch_size))
+            pools_g, pools_s = (
+                torch.cat([ops.retrieve_topk(_pad128(uv[users_d[s:s + step]]), iv, pool_k)[1].to(torch.int32)
+                           for s in range(0, len(users), step)])
+                for uv, iv in ((gu, _pad128(gi)), (su, _pad128(si))))
+        else:
+            step = _chunk_rows(batch_size, n_items)
         for s in range(0, len(users), step):
             rows = users_d[s:s + step]
             ug, us = gu[rows], su[rows]
-            pool_g, _ = ops.select_topk_rows(torch.matmul(ug, gi.T), pool_k)   # :1103-1104
-            pool_s, _ = ops.select_topk_rows(torch.matmul(us, si.T), pool_k)   # :1107-1108
+            if fused:
+                pool_g, pool_s = pools_g[s:s + step], pools_s[s:s + step]
+            else:
+                pool_g, _ = ops.select_topk_rows(torch.matmul(ug, gi.T), pool_k)   # :1103-1104
+                pool_s, _ = ops.select_topk_rows(torch.matmul(us, si.T), pool_k)   # :1107-1108
             cand = torch.cat([pool_g, pool_s], dim=1)                          # :1115
             out = ops.fuse_rank(ug, gi, us, si, cand, alphas, ks, off_d[s:s + rows.numel() + 1], truth_d, mode=mode,
                                 k_rrf=k_rrf, cut=cut, flag=flag)

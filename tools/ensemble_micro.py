@@ -3,14 +3,18 @@ of users: seeded unit vectors, 64-wide GNN space, 128-wide sequence space.
 
   * pool: both retrievers' pools of 1000, as the evaluators form them (per chunk of users bounded to
     512 MB of scores: fp32 torch.matmul, then ops.select_topk_rows), beside the same chunks with
-    torch.topk; and the selection alone on one resident chunk of scores beside torch.topk on it;
+    torch.topk, and the pools from ops.retrieve_topk ("fused": the bf16 scan with exact rescoring where
+    its plan serves the corpus, one corpus image built per retriever and call; "fused_path" tells which
+    route the op took); and the selection alone on one resident chunk of scores beside torch.topk on it;
   * fuse: ops.fuse_rank over the joined pool of 2000 with 11 alphas, min-max and RRF, beside a
     plain-PyTorch restatement of the same batch kept on the device (gather, both score sets,
     normalisation or double-argsort ranks, per alpha the weighted sum, torch.topk(max_k + 20), first
     occurrences by a stable sort, hit@k against a padded truth). The reference's own form adds a
     device-to-host copy per alpha and Python loops over the users; that part is not timed;
-  * k = 512: torch.matmul + ops.select_topk_rows beside ops.retrieve_topk (the scan fused with the dot
-    products, which stops at k = 512), 128-wide.
+  * k = 512, 1000, 2048: torch.matmul + ops.select_topk_rows beside ops.retrieve_topk (the scan fused with
+    the dot products where its plan serves the corpus), 128-wide, with the fused path's fallback count.
+--stages pool runs the pool stage alone (the evaluators' switch between the two forms,
+profiles/ensemble_pool_switch.json).
 Every side runs on the same GPU in the same process, alternating after warm-up, each call between HIP
 events; medians with min / max. Writes --out (profiles/ensemble_micro.json)."""
 import argparse
@@ -109,10 +113,20 @@ def run(n_items, a, dev, g):
 
     sel_ours = lambda S, k: ops.select_topk_rows(S, k)[0]
     sel_torch = lambda S, k: torch.topk(S, k=k, dim=1)[1].to(torch.int32)
+    gu128, gi128 = MI._pad128(gu), MI._pad128(gi).contiguous()
+    fused = lambda u, items: ops.retrieve_topk(u, items, POOL)[1].to(torch.int32)
     res["pool_both_retrievers"] = alternate({
         "native": lambda: (pools(gu, gi, POOL, step, sel_ours), pools(su, si, POOL, step, sel_ours)),
         "torch": lambda: (pools(gu, gi, POOL, step, sel_torch), pools(su, si, POOL, step, sel_torch)),
+        "fused": lambda: (fused(gu128, gi128), fused(su, si)),
     }, a.warmup, iters)
+    diag = {}
+    ops.retrieve_topk(su, si, POOL, diag=diag)
+    res["pool_both_retrievers"]["fused_path"] = diag["path"]
+    res["pool_both_retrievers"]["fused_fallback_queries_seq"] = diag["fallback_queries"]
+    if a.stages == "pool":
+        ops.clear_retrieval_cache()
+        return res
     S = torch.matmul(su[:step], si.T)
     res["select_alone_one_chunk"] = dict(alternate({
         "native": lambda: ops.select_topk_rows(S, POOL), "torch": lambda: torch.topk(S, k=POOL, dim=1)}, a.warmup, iters),
@@ -143,14 +157,18 @@ def run(n_items, a, dev, g):
         res[f"fuse_{mode}"]["users_whose_hits_differ_from_torch"] = int((ours != plain()).any(dim=-1).any(dim=-1).sum())
         res[f"fuse_{mode}"]["hit_rate_at_k_alpha_0.5"] = ours[:, 5].float().mean(dim=0).tolist()
 
-    res["k512"] = alternate({
-        "matmul_select_topk_rows": lambda: pools(su, si, 512, step, sel_ours),
-        "retrieve_topk": lambda: ops.retrieve_topk(su, si, 512)[1],
-    }, a.warmup, iters)
-    # the two form the fp32 dot products in different orders, so near-equal scores may swap places
-    differ = (pools(su, si, 512, step, sel_ours).long() != ops.retrieve_topk(su, si, 512)[1])
-    res["k512"]["places_that_differ"] = int(differ.sum())
-    res["k512"]["places"] = differ.numel()
+    for k in (512, 1000, 2048):
+        res[f"k{k}"] = alternate({
+            "matmul_select_topk_rows": lambda: pools(su, si, k, step, sel_ours),
+            "retrieve_topk": lambda: ops.retrieve_topk(su, si, k)[1],
+        }, a.warmup, iters)
+        # the two form the fp32 dot products in different orders, so near-equal scores may swap places
+        diag = {}
+        differ = (pools(su, si, k, step, sel_ours).long() != ops.retrieve_topk(su, si, k, diag=diag)[1])
+        res[f"k{k}"]["places_that_differ"] = int(differ.sum())
+        res[f"k{k}"]["places"] = differ.numel()
+        res[f"k{k}"]["retrieve_topk_path"] = diag["path"]
+        res[f"k{k}"]["fallback_queries"] = diag["fallback_queries"]
     ops.clear_retrieval_cache()
     return res
 
@@ -161,6 +179,7 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--stages", choices=["all", "pool"], default="all")
     ap.add_argument("--out", default=os.path.join("profiles", "ensemble_micro.json"))
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
