@@ -199,6 +199,7 @@ struct GArgs {
   int64_t span;          // streamed rows per split
   float* part;           // fwd: [4][nsplit][N]
   const float* lse;      // bwd
+  const float* row_loss; // bwd, f16 column pass: lse_i - s_ii of the forward's merge (fp32 label logit)
   const float* gout;     // bwd: gradient of the row-loss sum
   float* dout;           // bwd: [nsplit][owner][128]
   const __bf16* ahi;     // bf16x3: hi/lo images of A [N][128] and B [M][128]

@@ -1391,6 +1391,7 @@ RSX_API int rsx_nce_grouped_bwd(const float* A, const float* B, const float* bia
   GArgs g = grouped_args(A, B, bias, colcnt, row_col, row_beg, row_end, exc_cols, N, D, lda, ldb, tau);
   g.col_beg = col_beg; g.col_end = col_end; g.exc_s = exc_s; g.exc_e = exc_e; g.exc_n = exc_n;
   g.lse = ws + L.lse;
+  g.row_loss = ws + L.row_loss;
   g.gout = gout;
   g.dout = ws + L.dpart;
   g.ahi = im.ahi; g.alo = im.alo; g.bhi = im.bhi; g.blo = im.blo;

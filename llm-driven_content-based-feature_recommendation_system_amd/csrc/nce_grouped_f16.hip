@@ -10,8 +10,9 @@ namespace {
 // fp16 form of the fused forward and the column pass (precision RSX_NCE_F16).
 // Logits: every operand is split into fp16 hi + lo of x * 2^8 (unit-vector components scaled into
 // fp16's normal range; lo carries the next 11 bits), S = hi*hi' + hi*lo' + lo*hi' on
-// v_mfma_f32_32x32x16_f16 with fp32 accumulation: |dot error| ~2^-22 relative per term, tighter
-// than bf16x3 (2^-16) at the same MFMA count; the 2^16 product scale is folded into 1/tau.
+// v_mfma_f32_32x32x16_f16 (the GP = 1 column pass: v_mfma_f32_16x16x32_f16) with fp32 accumulation:
+// |dot error| ~2^-22 relative per term, tighter than bf16x3 (2^-16) at the same MFMA count; the 2^16
+// product scale is folded into 1/tau.
 // Gradient products (the softmax weights G against the streamed rows): G rounded to fp16 once and
 // multiplied by the rows' fp16 hi image (GP = 1: one MFMA per k-step instead of three) or by hi and
 // lo (GP = 2: only G's rounding, 2^-11 relative per weight). This is the reference's own GPU
@@ -19,7 +20,7 @@ namespace {
 // accumulation; the gradient scales (the 2^8 row scale, the column pass's per-owner factor and
 // its 2^14 weight scale) are applied to the fp32 accumulators after the sweep.
 // The images keep the bf16x3 layout and LDS tiles (16-bit containers: bf16x8 vectors carry fp16
-// bits and are bit-cast at the MFMA).
+// bits and are bit-cast at the MFMA); the 16x16x32 column pass has an LDS image of its own.
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr float kHUnscale = 1.0f / 256.0f;
 constexpr float kHS2 = 1.0f / 65536.0f;   // S product scale 2^-16
@@ -71,29 +72,6 @@ __device__ __forceinline__ f32x16 dots_h3(const X3Tile& t, int c, int h, const b
     __builtin_amdgcn_sched_barrier(0);
     ah = nh;
     al = nl;
-  }
-  return acc;
-}
-
-// S tile from two fp16 products, hi*hi' + hi*lo' (streamed hi against the owner's hi and lo): the
-// streamed rows' lo image is never read. |dot error| = |<lo, owner>| ~ 2^-11 |x| per component with
-// random signs, ~2e-5 on unit vectors (the column pass's weights only; the logits of the loss keep
-// three products in the forward)
-__device__ __forceinline__ f32x16 dots_h2(const X3Tile& t, int c, int h, const bf16x8 (&uh)[8],
-                                          const bf16x8 (&ul)[8]) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-  const int base = img_off(c, 64 * h);
-  bf16x8 ah = *reinterpret_cast<const bf16x8*>(&t.hi[base]);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    bf16x8 nh = ah;
-    if (s < 7) nh = *reinterpret_cast<const bf16x8*>(&t.hi[base + 8 * (s + 1)]);
-    acc = mfma_h(ah, ul[s], acc);
-    acc = mfma_h(ah, uh[s], acc);
-    __builtin_amdgcn_sched_barrier(0);
-    ah = nh;
   }
   return acc;
 }
@@ -377,14 +355,10 @@ __device__ __forceinline__ void grad_half_gh(f32x16 (&gacc)[4], const bf16x8& g,
 // the common product, when its G fragments are dead: folded into the common product, the exception
 // bookkeeping needs ~60 more VGPRs than the 256 a two-wave-per-SIMD kernel has (and with the owner
 // fragments moved to LDS instead the pass is LDS-bound).
-// SPN = products of the S tile: 3 (dots_h3) or 2 (dots_h2, GP = 1 only: with one gradient product on the
-// hi image as well, the streamed rows' lo image is neither staged nor read). GP = 1 runs with two: the
-// column weights' logits to ~2e-5 on unit vectors (the pass outputs gradients only, 1e-3 of scale); at
-// batch 8192 the pass takes 3.33 instead of 4.03 ms with grad_b's deviation from fp32 unchanged
-// (4.897e-4 vs 4.899e-4 of scale, tools/nce_micro.py --compare).
-template <int GP, int SPN = 3>
+// This 32x32x16 form serves RSX_NCE_F16_GP = 2 (three S products, gradient products on the rows' hi and
+// lo images); the shipped GP = 1 pass is nce_grouped_bwd_cols_h16_k below.
+template <int GP>
 __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
-  static_assert(SPN == 3 || (SPN == 2 && GP == 1), "two S products only with one gradient product");
   __shared__ __attribute__((aligned(16))) X3Tile sT[2];
   __shared__ __attribute__((aligned(16))) float sM0[2][kTile];  // lse_i * log2e (+inf past the split)
   __shared__ __attribute__((aligned(16))) int sM2[2][kTile];    // d(i) (-2 past the split)
@@ -434,8 +408,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
   int stg2 = 0;
   auto gload = [&](int64_t s0) {
     const int64_t sidx = s0 + (tid >> 3);
-    if constexpr (SPN == 2) stg.load_hi(a.ahi, sidx, sidx < s_end, tid);
-    else stg.load(a.ahi, a.alo, sidx, sidx < s_end, tid);
+    stg.load(a.ahi, a.alo, sidx, sidx < s_end, tid);
     if (tid < kTile) {
       const int64_t ss = s0 + tid;
       const bool ok = ss < s_end;
@@ -444,8 +417,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
     }
   };
   auto lstore = [&](int buf) {
-    if constexpr (SPN == 2) stg.store_hi(sT[buf], tid);
-    else stg.store(sT[buf], tid);
+    stg.store(sT[buf], tid);
     if (tid < kTile) {
       sM0[buf][tid] = stg0 * kLog2e;
       sM2[buf][tid] = stg2;
@@ -477,7 +449,7 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
       const bool has_next = t + 1 < ntile;
       const bool exc = exc_flag(s0);
       if (has_next) gload(s0 + kTile);
-      f32x16 acc = SPN == 2 ? dots_h2(sT[cur], c, h, uh, ul) : dots_h3(sT[cur], c, h, uh, ul);
+      f32x16 acc = dots_h3(sT[cur], c, h, uh, ul);
       // G' rows of k-step 0, then k-step 0's product with k-step 1's rows under its MFMAs
       u32x4 g0;
 #pragma unroll
@@ -547,6 +519,313 @@ __global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h_k(GArgs a) {
                     gs * (kHUnscale / kHGSv));
 }
 
+// =====================================================================================
+// The GP = 1 column pass (the shipped one) on v_mfma_f32_16x16x32_f16: nce_grouped_bwd_cols_h_k's
+// pass in 16x16 accumulator blocks, with two S products, hi*hi' + hi*lo' (streamed hi against the
+// owner's hi and lo): with one gradient product on the hi image as well, the streamed rows' lo image is
+// neither staged nor read. |dot error| = |<lo, owner>| ~ 2^-11 |x| per component with random signs, ~2e-5
+// on unit vectors (the pass outputs gradients only, 1e-3 of scale; the logits of the loss keep three
+// products in the forward); grad_b's deviation from fp32 is that of three products (4.897e-4 vs
+// 4.899e-4 of scale, tools/nce_micro.py --compare). A wave owns 32 columns and streams 32-row tiles;
+// a lane (i = lane & 15, g = lane >> 4) serves owner columns i and 16 + i, and everything per owner
+// (exponent offset, count, exception cursor) is held twice.
+// Exception pairs (the owner's same-user rows and label rows) do not take a second product here: on
+// the rare tiles that hold some, their exact weight 2^14 (w p1 - lab), formed in fp32 from the same S,
+// replaces the common weight in the G' fragment before the one gradient product, so it is rounded to
+// fp16 once at its own magnitude; a label pair's p - 1 comes from the forward's row loss lse_i - s_ii. (Common weight plus a correction product, as in the 32x32 form,
+// rounds two values of magnitude 2^14 whose sum on a label pair is 2^14 (p - 1): an absolute floor of
+// ~3e-4 per label row, 1e-2 of a near-converged batch's column gradient.)
+//   S block (sh, b): streamed rows 16sh .. 16sh+15 x owner columns 16b .. 16b+15, 4 k-steps of 32
+//             dims, 2 products each. Operands: lane (i, g) holds dims 32ks + 8g + j of streamed row
+//             16sh + i (A) and of owner column 16b + i (B); accumulator register r is streamed row
+//             16sh + 4g + r, owner column 16b + i.
+//   gradient: K = the tile's 32 streamed rows, one k-step: for owner half b the A fragment is the
+//             lane's own G' of blocks (0, b) and (1, b), i.e. k element j = streamed row
+//             16(j>>2) + 4g + (j&3), and the B fragment of dims 16nb .. 16nb+15 is read transposed
+//             in the same k order (two 4-row blocks 16 rows apart). gacc[b][nb] register r is owner
+//             column 16b + 4g + r, dim 16nb + i.
+// The S of streamed half 0 is complete after half of the tile's S MFMAs, and its G' work is issued
+// under the S MFMAs of half 1.
+// LDS image of the hi tile (the lo image is not staged): plain 288-B rows, no skew; conflict-free
+// for the 16-row fragment reads (ds_read_b128: row i, 16-B chunk 4ks + g), the transposed reads
+// and the staging stores (tools/lds_banks.py, "16x16x32 column pass").
+constexpr int kImg16Row = 144;  // fp16 elements per image row
+__device__ __forceinline__ int img16_off(int row, int col) { return row * kImg16Row + col; }
+struct H16Tile {
+  __bf16 hi[kTile * kImg16Row];
+};
+
+__device__ __forceinline__ f32x4 mfma_h16(const bf16x8& a, const bf16x8& b, const f32x4& c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0,
+                                                0);
+}
+
+// transposed fragment of dims 16nb .. 16nb+15: rows 4g .. 4g+3 and 16 + 4g .. 16 + 4g+3 from the
+// lane's base offset img16_off(4g + q, 4p) (lane = 16g + 4q + p)
+__device__ __forceinline__ bf16x8 img16_read_tr(const __bf16* img, int base, int nb) {
+  const int o0 = base + img16_off(0, 16 * nb), o1 = base + img16_off(16, 16 * nb);
+  const rsx::bf16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((rsx::lds_bf16x4*)(&img[o0]));
+  const rsx::bf16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((rsx::lds_bf16x4*)(&img[o1]));
+  return __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// owner columns row0 + 16b + i (b = 0, 1): fragment [b][ks] = dims 32ks + 8g .. 32ks + 8g+7
+__device__ __forceinline__ void load_owner_h16(bf16x8 (&uh)[2][4], bf16x8 (&ul)[2][4], const float* base,
+                                               const int64_t (&row)[2], int64_t ld, const bool (&ok)[2], int g) {
+  float4 v[16];  // all loads issued from clamped rows, then zeroed past the rows (load_owner_h)
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    const float* src = base + (ok[b] ? row[b] : 0) * ld + 8 * g;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      v[8 * b + 2 * ks] = *reinterpret_cast<const float4*>(src + 32 * ks);
+      v[8 * b + 2 * ks + 1] = *reinterpret_cast<const float4*>(src + 32 * ks + 4);
+    }
+  }
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+      split8_h(ok[b] ? v[8 * b + 2 * ks] : z, ok[b] ? v[8 * b + 2 * ks + 1] : z, uh[b][ks], ul[b][ks]);
+}
+
+// G' pair of one lane: 2^14 min(c_o p1, 1) of two logits, packed as fp16 (grad_half_gh's arithmetic)
+__device__ __forceinline__ uint32_t gprime_pair(float s0, float s1, float q0, float q1, float o_m2s, float it2) {
+  const float a = fminf(__builtin_amdgcn_exp2f(fmaf(s0, it2, -(q0 + o_m2s))), kHGSv);
+  const float b = fminf(__builtin_amdgcn_exp2f(fmaf(s1, it2, -(q1 + o_m2s))), kHGSv);
+  return pack_h(a, b);
+}
+
+// S blocks (sh, 0) and (sh, 1) from two fp16 products, hi*lo' then hi*hi' per k-step.
+// WORK: the G' pairs of the previous half's blocks prev[0], prev[1] (its row offsets pm), one pair
+// under each k-step's four MFMAs: og[2b + t] = rows 2t, 2t+1 of block b, pair 2b + t at step 2b + t
+template <bool WORK>
+__device__ __forceinline__ void dots_h16(f32x4 (&acc)[2], const H16Tile& t, int fbase, int sh,
+                                         const bf16x8 (&uh)[2][4], const bf16x8 (&ul)[2][4], const f32x4 (&prev)[2],
+                                         const f32x4& pm, const float (&o_m2s)[2], float it2, uint32_t (&og)[4]) {
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[b][r] = 0.0f;
+  const int base = fbase + img16_off(16 * sh, 0);
+  bf16x8 a = *reinterpret_cast<const bf16x8*>(&t.hi[base]);
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    bf16x8 n = a;
+    if (ks < 3) n = *reinterpret_cast<const bf16x8*>(&t.hi[base + 32 * (ks + 1)]);
+    acc[0] = mfma_h16(a, ul[0][ks], acc[0]);
+    acc[1] = mfma_h16(a, ul[1][ks], acc[1]);
+    acc[0] = mfma_h16(a, uh[0][ks], acc[0]);
+    acc[1] = mfma_h16(a, uh[1][ks], acc[1]);
+    if (WORK) {
+      const int b = ks >> 1, r = 2 * (ks & 1);
+      og[ks] = gprime_pair(prev[b][r], prev[b][r + 1], pm[r], pm[r + 1], o_m2s[b], it2);
+      asm volatile("" : "+v"(og[ks]));  // pins the work to this step (no sinking)
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // next step's fragment read
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    a = n;
+  }
+}
+
+// gacc[b][nb] += G'_b^T X over the tile's 32 rows (one k-step), nb = 0..7
+__device__ __forceinline__ void grad_h16(f32x4 (&gacc)[2][8], const bf16x8 (&g)[2], const H16Tile& t, int tbase) {
+  bf16x8 x = img16_read_tr(t.hi, tbase, 0);
+#pragma unroll
+  for (int nb = 0; nb < 8; ++nb) {
+    bf16x8 n = x;
+    if (nb < 7) n = img16_read_tr(t.hi, tbase, nb + 1);
+    gacc[0][nb] = mfma_h16(g[0], x, gacc[0][nb]);
+    gacc[1][nb] = mfma_h16(g[1], x, gacc[1][nb]);
+    __builtin_amdgcn_sched_barrier(0);
+    x = n;
+  }
+}
+
+__global__ __launch_bounds__(256, 2) void nce_grouped_bwd_cols_h16_k(GArgs a) {
+  __shared__ __attribute__((aligned(16))) H16Tile sT[2];
+  __shared__ __attribute__((aligned(16))) float sM0[2][kTile];  // lse_i * log2e (+inf past the split)
+  __shared__ __attribute__((aligned(16))) int sM2[2][kTile];    // d(i) (-2 past the split)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, i = lane & 15;
+  int split, ob;
+  const int64_t n_own = a.M, n_str = a.N;
+  if (a.split_major) {
+    const int b = blockIdx.x, xcd = b & 7, q = b >> 3;
+    const int nob = (int)((n_own + kOwnRows - 1) / kOwnRows);
+    split = xcd + 8 * (q / nob);
+    ob = q % nob;
+  } else {
+    remap_block(a.nsplit, split, ob);
+  }
+  const float gs = a.gout[0] * a.inv_tau;
+  const float it2 = a.inv_tau * kLog2e * kHS2;
+  const int64_t own_base = (int64_t)ob * kOwnRows + wave * 32;
+  const int64_t o[2] = {own_base + i, own_base + 16 + i};
+  const bool own_ok[2] = {o[0] < n_own, o[1] < n_own};
+  bf16x8 uh[2][4], ul[2][4];
+  load_owner_h16(uh, ul, a.B, o, a.ldb, own_ok, g);
+  const int64_t s_begin = (int64_t)split * a.span;
+  int64_t s_end = s_begin + a.span;
+  if (s_end > n_str) s_end = n_str;
+  constexpr int kNone = 0x7fffffff;
+  // exponent offset of G' = 2^14 c_o 2^(x): bias_o log2e - log2 c_o - 14 (no owner: +inf -> G' = 0)
+  float o_m2s[2] = {INFINITY, INFINITY}, o_cnt[2] = {0.0f, 0.0f};
+  int p[2] = {0, 0}, e[2] = {0, 0}, q[2], e_first[2] = {0, 0}, s_next[2] = {kNone, kNone};
+#pragma unroll
+  for (int b = 0; b < 2; ++b) {
+    if (own_ok[b]) {
+      o_cnt[b] = a.colcnt[o[b]];
+      o_m2s[b] = (a.bias ? a.bias[o[b]] * kLog2e : 0.0f) - __log2f(o_cnt[b]) - kHGS;
+      p[b] = a.col_beg[o[b]];
+      e[b] = a.col_end[o[b]];
+      p[b] = lower_bound_i(a.exc_e, p[b], e[b], s_begin + 1);  // first user range ending after s_begin
+    }
+    q[b] = p[b];
+    if (own_ok[b] && q[b] < e[b]) s_next[b] = a.exc_s[q[b]];
+  }
+
+  f32x4 gacc[2][8];
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int nb = 0; nb < 8; ++nb)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gacc[b][nb][r] = 0.0f;
+
+  X3Stage stg;
+  float stg0 = 0.0f;
+  int stg2 = 0;
+  auto gload = [&](int64_t s0) {
+    const int64_t sidx = s0 + (tid >> 3);
+    stg.load_hi(a.ahi, sidx, sidx < s_end, tid);
+    if (tid < kTile) {
+      const int64_t ss = s0 + tid;
+      const bool ok = ss < s_end;
+      stg0 = ok ? a.lse[ss] : INFINITY;
+      stg2 = ok ? a.row_col[ss] : -2;
+    }
+  };
+  auto lstore = [&](int buf) {
+    const int row = tid >> 3, ch = tid & 7;
+    *reinterpret_cast<u32x4*>(&sT[buf].hi[img16_off(row, 8 * ch)]) = stg.v[0];
+    *reinterpret_cast<u32x4*>(&sT[buf].hi[img16_off(row, 64 + 8 * ch)]) = stg.v[1];
+    if (tid < kTile) {
+      sM0[buf][tid] = stg0 * kLog2e;
+      sM2[buf][tid] = stg2;
+    }
+  };
+  // user row ranges [p, q) of owner column b intersecting tile s0 (before the prefetch: may load)
+  auto exc_flag = [&](int b, int64_t s0) -> bool {
+    while (p[b] < q[b] && (int64_t)e_first[b] <= s0) {
+      ++p[b];
+      if (p[b] < q[b]) e_first[b] = a.exc_e[p[b]];
+    }
+    while ((int64_t)s_next[b] < s0 + kTile) {
+      if (p[b] == q[b]) e_first[b] = a.exc_e[q[b]];
+      ++q[b];
+      s_next[b] = (q[b] < e[b]) ? a.exc_s[q[b]] : kNone;
+    }
+    return q[b] != p[b];
+  };
+
+  if (s_begin < s_end) {
+    const int ntile = (int)((s_end - s_begin + kTile - 1) / kTile);
+    gload(s_begin);
+    lstore(0);
+    __syncthreads();
+    int cur = 0;
+    const int fbase = img16_off(i, 8 * g);
+    const int tbase = img16_off(4 * g + (i >> 2), 4 * (i & 3));
+    for (int t = 0; t < ntile; ++t) {
+      const int64_t s0 = s_begin + (int64_t)t * kTile;
+      const bool has_next = t + 1 < ntile;
+      const bool exc[2] = {exc_flag(0, s0), exc_flag(1, s0)};
+      if (has_next) gload(s0 + kTile);
+      // lse offsets of the lane's streamed rows 4g .. 4g+3 and 16 + 4g .. 16 + 4g+3
+      const f32x4 m0 = *reinterpret_cast<const f32x4*>(&sM0[cur][4 * g]);
+      const f32x4 m1 = *reinterpret_cast<const f32x4*>(&sM0[cur][16 + 4 * g]);
+      f32x4 S0[2], S1[2];
+      uint32_t g0[4], g1[4];
+      dots_h16<false>(S0, sT[cur], fbase, 0, uh, ul, S0, m0, o_m2s, it2, g0);
+      dots_h16<true>(S1, sT[cur], fbase, 1, uh, ul, S0, m0, o_m2s, it2, g0);
+#pragma unroll
+      for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+          g1[2 * b + tt] = gprime_pair(S1[b][2 * tt], S1[b][2 * tt + 1], m1[2 * tt], m1[2 * tt + 1], o_m2s[b], it2);
+      // A fragments of the gradient product: element j of gf[b] = G' of streamed row 16(j>>2) + 4g + (j&3)
+      const u32x4 f0 = {g0[0], g0[1], g1[0], g1[1]}, f1 = {g0[2], g0[3], g1[2], g1[3]};
+      f16x8 gf[2] = {__builtin_bit_cast(f16x8, f0), __builtin_bit_cast(f16x8, f1)};
+      if (__any(exc[0] || exc[1])) {
+        // the owners' exception rows take their exact weight 2^14 (w p1 - lab) in place of the common one:
+        // w = c_o - n (the user's own rows of target o) or 1 (label), from the same S, rounded to fp16 once
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+          float n[8];  // multiplicity n of the user range holding streamed row 16(k>>2) + 4g + (k&3) (0: none)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) n[k] = 0.0f;
+          if (exc[b]) {
+            for (int k = p[b]; k < q[b]; ++k) {  // each range's bounds loaded once
+              const int ks = (int)(a.exc_s[k] - s0), ke = (int)(a.exc_e[k] - s0);
+              const float nk = (float)a.exc_n[k];
+#pragma unroll
+              for (int r = 0; r < 8; ++r) {
+                const int tr = 16 * (r >> 2) + 4 * g + (r & 3);
+                n[r] += (tr >= ks && tr < ke) ? nk : 0.0f;
+              }
+            }
+          }
+#pragma unroll
+          for (int r = 0; r < 8; ++r) {
+            const int tr = 16 * (r >> 2) + 4 * g + (r & 3);
+            const float s = (r < 4) ? S0[b][r & 3] : S1[b][r & 3];
+            const bool lab = exc[b] && sM2[cur][tr] == (int)o[b];
+            if (exc[b] && (n[r] > 0.0f || lab)) {
+              const float ex = __builtin_amdgcn_exp2f(fmaf(s, it2, -(sM0[cur][tr] + o_m2s[b])));  // 2^14 c_o p1
+              const float rc = __builtin_amdgcn_rcpf(o_cnt[b]);
+              const float w = lab ? 1.0f : fmaxf(o_cnt[b] - n[r], 0.0f);
+              // (c_o - n) p1 <= 1: lse_i holds the column's other c_o - n instances; no instance left: 0
+              // label pair: p - 1 = expm1(-(lse_i - s_ii)) from the forward's fp32 label logit (this pass's
+              // two-product S leaves ~2e-4 on the logit, which is all of p - 1's error once p is near 1)
+              const float ge = lab ? kHGSv * expm1f(-a.row_loss[s0 + tr])
+                                   : ((w > 0.0f) ? fminf((w * rc) * ex, kHGSv) : 0.0f);
+              gf[b][r] = (_Float16)ge;
+            }
+          }
+        }
+      }
+      {
+        const bf16x8 ga[2] = {__builtin_bit_cast(bf16x8, gf[0]), __builtin_bit_cast(bf16x8, gf[1])};
+        grad_h16(gacc, ga, sT[cur], tbase);
+      }
+      if (has_next) lstore(cur ^ 1);
+      __builtin_amdgcn_s_waitcnt(kVmcnt0);
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+  // scale: gout / tau, the 2^-8 row scale and the 2^-14 weight scale
+  const float scale = gs * (kHUnscale / kHGSv);
+  float* dst = a.dout + (int64_t)split * n_own * kD;
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int64_t orow = own_base + 16 * b + 4 * g + r;
+      if (orow < n_own) {
+#pragma unroll
+        for (int nb = 0; nb < 8; ++nb) dst[orow * kD + 16 * nb + i] = gacc[b][nb][r] * scale;
+      }
+    }
+}
+
 // RSX_NCE_F16_GP = 1 | 2: MFMAs per gradient-product k-step in the fp16 kernels (default 1)
 int f16_gp() {
   static const int v = [] {
@@ -565,5 +844,5 @@ void rsx::nce::launch_grouped_fwdg_h(const GArgs& g, int blocks, hipStream_t st)
 
 void rsx::nce::launch_grouped_bwd_cols_h(const GArgs& g, int blocks, hipStream_t st) {
   if (f16_gp() == 2) hipLaunchKernelGGL(nce_grouped_bwd_cols_h_k<2>, dim3(blocks), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL((nce_grouped_bwd_cols_h_k<1, 2>), dim3(blocks), dim3(256), 0, st, g);
+  else hipLaunchKernelGGL(nce_grouped_bwd_cols_h16_k, dim3(blocks), dim3(256), 0, st, g);
 }

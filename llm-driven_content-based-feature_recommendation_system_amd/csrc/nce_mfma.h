@@ -94,11 +94,6 @@ struct X3Stage {
       v[0] = v[1] = u32x4{0u, 0u, 0u, 0u};
     }
   }
-  __device__ __forceinline__ void store_hi(X3Tile& t, int tid) const {
-    const int row = tid >> 3, ch = tid & 7;
-    *reinterpret_cast<u32x4*>(&t.hi[img_off(row, 8 * ch)]) = v[0];
-    *reinterpret_cast<u32x4*>(&t.hi[img_off(row, 64 + 8 * ch)]) = v[1];
-  }
 };
 
 

@@ -105,3 +105,28 @@ for S in range(256, 400, 16):
         best.append((wr+wt+ww/2, wr,wt,ww,size,S,u,v,a))
 best.sort()
 for b in best[:15]: print(b)
+
+print("---- 16x16x32 column pass (csrc/nce_grouped_f16.hip, nce_grouped_bwd_cols_h16_k)")
+# lane (i = L & 15, g = L >> 4). Fragment reads: row 16sh + i, 16-B chunk 4ks + g (ds_read_b128);
+# transposed reads: rows r0 + 4g + q, columns 16nb + 4p, lane = 16g + 4q + p, r0 = 0 / 16; staging
+# stores as above. Ideal: b128 4, tr 2, write 8.
+def eval_layout16(off):
+    wr = 0
+    for sh in range(2):
+        for ks in range(4):
+            wr = max(wr, cost([off(16 * sh + (L & 15), (4 * ks + (L >> 4)) * 8) for L in range(64)], B128_GROUPS, 4))
+    wt = 0
+    for r0 in (0, 16):
+        for nb in range(8):
+            addrs = [off(r0 + 4 * (L >> 4) + ((L >> 2) & 3), 16 * nb + 4 * (L & 3)) for L in range(64)]
+            wt = max(wt, cost(addrs, HALVES, 2))
+    W_GROUPS = [list(range(8 * k, 8 * k + 8)) for k in range(8)]
+    ww = 0
+    for wave in range(4):
+        for k in range(2):
+            addrs = [off((64 * wave + L) >> 3, 64 * k + 8 * ((64 * wave + L) & 7)) for L in range(64)]
+            ww = max(ww, cost(addrs, W_GROUPS, 4, mod=32))
+    return wr, wt, ww
+print("bf16x3 image 320*row + 16*(row>>3):", eval_layout16(lambda r, c: r * 320 + 16 * (r >> 3) + 2 * c))
+for S in range(256, 336, 16):
+    print("plain rows of", S, "B:", eval_layout16(lambda r, c, S=S: r * S + 2 * c), "(in use: 288)" if S == 288 else "")
