@@ -25,6 +25,7 @@
 // No step walks a tie group: one group over all R rows costs what distinct scores cost. The sums
 // are integers (any order gives the same bits); the only floating-point sum is the Logloss, whose
 // order is fixed.
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include "rsx_x3.h"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -32,7 +33,7 @@
 
 namespace {
 
-using rsx::score_key;
+using rsx::at, rsx::block_scan_excl, rsx::score_key, rsx::Sum;
 
 constexpr int kThreads = 256, kPer = 8, kTile = kThreads * kPer;
 constexpr int kLossSlots = 1024;  // workgroups of the key pass (each one Logloss partial)
@@ -53,43 +54,12 @@ hipError_t sort_pairs(void* tmp, size_t& bytes, const unsigned* kin, unsigned* k
   return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, kin, kout, vin, vout, (size_t)R, 0u, 32u, st);
 }
 
-struct Sum {
-  __device__ __forceinline__ int operator()(int a, int b) const { return a + b; }
-};
 struct Max {
   __device__ __forceinline__ int operator()(int a, int b) const { return a > b ? a : b; }
 };
 struct Min {
   __device__ __forceinline__ int operator()(int a, int b) const { return a < b ? a : b; }
 };
-
-// Exclusive scan of one value per thread over the workgroup (REV: from the last thread down);
-// total = the reduction of all NT values. sm holds NT / 64 ints.
-template <int NT, bool REV, class Op>
-__device__ __forceinline__ int block_scan_excl(int x, Op op, int ident, int* sm, int& total) {
-  constexpr int NW = NT / 64;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = REV ? __shfl_down(incl, d, 64) : __shfl_up(incl, d, 64);
-    if (REV ? lane + d < 64 : lane >= d) incl = op(incl, y);
-  }
-  if (lane == (REV ? 0 : 63)) sm[w] = incl;
-  __syncthreads();
-  int pre = ident;
-  total = ident;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    const int v = sm[k];
-    total = op(total, v);
-    if (REV ? k > w : k < w) pre = op(pre, v);
-  }
-  int e = REV ? __shfl_down(incl, 1, 64) : __shfl_up(incl, 1, 64);
-  if (lane == (REV ? 63 : 0)) e = ident;
-  __syncthreads();  // sm is free for the next scan
-  return op(pre, e);
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void be_key_k(const float* __restrict__ logit, const float* __restrict__ y,
@@ -328,8 +298,6 @@ __global__ __launch_bounds__(1024) void be_carry_k(TileArrays ta, int64_t tiles,
   }
 }
 
-int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
-
 struct BeLayout {
   int64_t keys, keys_o, lab, lab_o, neg, head, tail, negoff, carry_h, carry_t, lpart, temp, temp_bytes, total, tiles;
 };
@@ -342,24 +310,19 @@ size_t sort_temp_bytes(int64_t R) {
 
 BeLayout be_layout(int64_t R) {
   BeLayout l;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t r = o;
-    o += a256(bytes);
-    return r;
-  };
+  rsx::Bump bump{0, 256};
   l.tiles = (R + kTile - 1) / kTile;
-  l.keys = take(R * 4);
-  l.keys_o = take(R * 4);
-  l.lab = take(R);
-  l.lab_o = take(R);
-  l.neg = take(l.tiles * 4);
-  l.head = take(l.tiles * 4);
-  l.tail = take(l.tiles * 4);
-  l.negoff = take(l.tiles * 4);
-  l.carry_h = take(l.tiles * 4);
-  l.carry_t = take(l.tiles * 4);
-  l.lpart = take(kLossSlots * 8);
+  l.keys = bump.take(R * 4);
+  l.keys_o = bump.take(R * 4);
+  l.lab = bump.take(R);
+  l.lab_o = bump.take(R);
+  l.neg = bump.take(l.tiles * 4);
+  l.head = bump.take(l.tiles * 4);
+  l.tail = bump.take(l.tiles * 4);
+  l.negoff = bump.take(l.tiles * 4);
+  l.carry_h = bump.take(l.tiles * 4);
+  l.carry_t = bump.take(l.tiles * 4);
+  l.lpart = bump.take(kLossSlots * 8);
   // the library's sort picks its plan by size (one block, merge sort, radix passes), and a plan
   // for fewer rows could ask for more storage: take the largest request over R and the powers of
   // two below it, so that the total does not shrink where the plan changes (a guard, checked over
@@ -367,14 +330,9 @@ BeLayout be_layout(int64_t R) {
   size_t tb = sort_temp_bytes(R);
   for (int64_t p = 1; p < R; p <<= 1) tb = std::max(tb, sort_temp_bytes(p));
   l.temp_bytes = (int64_t)tb;
-  l.temp = take(l.temp_bytes);
-  l.total = o;
+  l.temp = bump.take(l.temp_bytes);
+  l.total = bump.off;
   return l;
-}
-
-template <typename P>
-P* at(void* ws, int64_t off) {
-  return reinterpret_cast<P*>(reinterpret_cast<char*>(ws) + off);
 }
 
 }  // namespace

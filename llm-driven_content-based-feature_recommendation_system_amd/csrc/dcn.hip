@@ -314,7 +314,7 @@ int64_t bwd_resident_blocks(BwdFn fn, int nc, int L) {
   return c;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using rsx::aligned16;
 
 }  // namespace
 

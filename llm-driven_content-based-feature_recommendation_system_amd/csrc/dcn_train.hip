@@ -16,7 +16,7 @@
 
 namespace {
 constexpr int kHeadCols = 128;
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using rsx::aligned16;
 }  // namespace
 
 extern "C" int64_t rsx_deepfm_train_head_workspace_bytes(int64_t R);

@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256) void sparse_adam_k(SparseArgs a) {
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+using rsx::aligned16;
 inline unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace

@@ -383,7 +383,7 @@ __global__ __launch_bounds__(kApplyThreads) void distill_apply_k(ApplyArgs a) {
   a.v[e] = v;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using rsx::aligned16;
 
 template <typename K>
 int raise_lds(K kernel, const char* fn) {

@@ -26,6 +26,7 @@
 //
 // The fp32 expressions of the fusion are written to be reproduced bit for bit on the host: contraction
 // is off in this file, and only the dot products, whose summation order is free, use explicit FMAs.
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include "rsx_x3.h"
 #include "recsys_amd.h"
@@ -36,6 +37,7 @@
 namespace {
 
 using rsx::score_key;
+using rsx::bitonic_sort_desc, rsx::block_scan_excl, rsx::digit_search_desc, rsx::pow2_at_least;
 typedef unsigned long long u64;
 
 constexpr int kMaxK = 2048;      // rsx_select_topk_rows: largest k
@@ -52,33 +54,6 @@ constexpr int kNone = 0x7fffffff;
 __device__ __forceinline__ u64 pair_of(unsigned key, int pos) { return (u64)key << 32 | (u64)(0xffffffffu - (unsigned)pos); }
 __device__ __forceinline__ int pair_pos(u64 p) { return (int)(0xffffffffu - (unsigned)(p & 0xffffffffull)); }
 __device__ __forceinline__ unsigned pair_key(u64 p) { return (unsigned)(p >> 32); }
-
-// Bitonic sort of a[0, P) in LDS, descending; P a power of two. Every thread of the workgroup calls
-// it; a is complete (and visible) on return.
-template <int NT>
-__device__ __forceinline__ void sort_desc(u64* a, int P) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (P >> 1); t += NT) {
-        const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const u64 x = a[lo], y = a[hi];
-        if ((x < y) == desc) {
-          a[lo] = y;
-          a[hi] = x;
-        }
-      }
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ int pow2_at_least(int n) {
-  int p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
 
 // Is id among the ascending, distinct t[lo, hi)?
 __device__ __forceinline__ bool in_truth(const int32_t* __restrict__ t, int64_t lo, int64_t hi, int id) {
@@ -150,30 +125,18 @@ __global__ __launch_bounds__(kSelThreads) void select_topk_k(const float* __rest
       }
     }
     __syncthreads();
-    if (w == 0) {  // lane l owns the bytes 255 - 4l ... 252 - 4l; a scan over the lanes counts the bytes above
-      unsigned c[4], s = 0u;
+    if (w == 0) {  // the prefix holds >= need keys, so one lane finds the byte
+      int byte;
+      unsigned above;
+      const auto count = [&](int b) {
+        unsigned c = 0u;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int b = 255 - 4 * lane - j;
-        c[j] = 0u;
-#pragma unroll
-        for (int q = 0; q < kSelWaves; ++q) c[j] += hist[q][b];
-        s += c[j];
-      }
-      unsigned incl = s;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const unsigned y = (unsigned)__shfl_up((int)incl, d, 64);
-        if (lane >= d) incl += y;
-      }
-      unsigned above = incl - s;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (above < need && need <= above + c[j]) {  // true for exactly one byte: the prefix holds >= need keys
-          sPrefix = prefix | ((unsigned)(255 - 4 * lane - j) << shift);
-          sNeed = need - above;
-        }
-        above += c[j];
+        for (int q = 0; q < kSelWaves; ++q) c += hist[q][b];
+        return c;
+      };
+      if (digit_search_desc(count, need, lane, byte, above)) {
+        sPrefix = prefix | ((unsigned)byte << shift);
+        sNeed = need - above;
       }
     }
     __syncthreads();
@@ -227,7 +190,7 @@ __global__ __launch_bounds__(kSelThreads) void select_topk_k(const float* __rest
       run += __popcll(m);
     }
   }
-  sort_desc<kSelThreads>(buf, P);
+  bitonic_sort_desc<kSelThreads>(buf, P);
   int32_t* __restrict__ oi = idx + (int64_t)blockIdx.x * k;
   float* __restrict__ ov = val + (int64_t)blockIdx.x * k;
   for (int j = tid; j < k; j += kSelThreads) {
@@ -259,30 +222,6 @@ struct FuseArgs {
   float *sa, *sb;
   int32_t* flag;
 };
-
-// Exclusive scan of one int per thread over the workgroup; total = the sum. sm holds NT / 64 ints.
-template <int NT>
-__device__ __forceinline__ int block_scan_excl(int x, int* sm, int& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += y;
-  }
-  if (lane == 63) sm[w] = incl;
-  __syncthreads();
-  int pre = 0;
-  total = 0;
-#pragma unroll
-  for (int q = 0; q < NT / 64; ++q) {
-    const int v = sm[q];
-    total += v;
-    if (q < w) pre += v;
-  }
-  __syncthreads();  // sm is free again
-  return pre + incl - x;
-}
 
 // min and max of v[0, C) over the workgroup (C >= 1); sm holds 2 NT / 64 floats.
 template <int NT>
@@ -322,7 +261,7 @@ __device__ __forceinline__ void normalise(float* v, int C, int P, int mode, floa
     for (int c = threadIdx.x; c < C; c += NT) v[c] = __fdiv_rn(v[c] - mn, den);
   } else {
     for (int c = threadIdx.x; c < P; c += NT) sortbuf[c] = c < C ? pair_of(score_key(v[c]), c) : 0ull;
-    sort_desc<NT>(sortbuf, P);
+    bitonic_sort_desc<NT>(sortbuf, P);
     for (int r = threadIdx.x; r < C; r += NT) v[pair_pos(sortbuf[r])] = __fdiv_rn(1.0f, (k_rrf + (float)r) + 1.0f);
   }
   __syncthreads();
@@ -411,7 +350,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rank_k(FuseArgs g, FuseCons
     int64_t tlo, thi;
     truth_range(g.truth_off, q, g.n_truth, tlo, thi);
     for (int c = tid; c < P; c += NT) sortbuf[c] = c < C ? pair_of((unsigned)cid[c], c) : 0ull;
-    sort_desc<NT>(sortbuf, P);
+    bitonic_sort_desc<NT>(sortbuf, P);
     for (int s = tid; s < C; s += NT) {
       const u64 e = sortbuf[s];
       const unsigned id = pair_key(e);
@@ -432,7 +371,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rank_k(FuseArgs g, FuseCons
       first[c] = kNone;
     }
     if (tid == 0) sHit = kNone;
-    sort_desc<NT>(sortbuf, P);
+    bitonic_sort_desc<NT>(sortbuf, P);
     // 6.-8. the first `cut` entries; an entry is kept when it is its id's first in the order
     int pos[kFusePer];
 #pragma unroll
@@ -453,7 +392,7 @@ __global__ __launch_bounds__(kFuseThreads) void fuse_rank_k(FuseArgs g, FuseCons
       }
     }
     int total;
-    int rank = block_scan_excl<NT>(cnt, smi, total);
+    int rank = block_scan_excl<NT>(cnt, rsx::Sum(), 0, smi, total);
     // 9. the rank of the first kept entry that is in the truth decides every hit@k
     int32_t* __restrict__ lst = g.lists ? g.lists + (q * k.A + a) * (int64_t)kmax : nullptr;
 #pragma unroll
@@ -497,9 +436,7 @@ __global__ __launch_bounds__(kHitThreads) void first_hit_k(const int32_t* __rest
 }
 
 size_t fuse_lds_bytes(int C) {
-  int P = 1;
-  while (P < C) P <<= 1;
-  return (size_t)P * (8 + 4 + 4 + 4 + 4 + 2);
+  return (size_t)pow2_at_least(C) * (8 + 4 + 4 + 4 + 4 + 2);
 }
 
 }  // namespace

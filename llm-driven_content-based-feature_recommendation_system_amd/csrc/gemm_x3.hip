@@ -35,7 +35,7 @@
 
 namespace {
 
-using rsx::bf16x8, rsx::f32x16, rsx::tile_row, rsx::u32x4;
+using rsx::bf16x8, rsx::f32x16, rsx::split8, rsx::tile_row, rsx::u32x4;
 
 #ifndef RSX_GEMM_BK
 #define RSX_GEMM_BK 16  // measured (tools/gemm_micro.py): 16 beats 32 by 10-15 % (48 KB LDS: 3 workgroups/CU)
@@ -111,15 +111,6 @@ struct GArgs {
   int transb;  // weight-stationary path only: B given as Bt [K, ldb] (B[n][k] = Bt[k * ldb + n])
   rsx::Dropout drop;
 };
-
-// 8 fp32 -> 8 hi + 8 lo bf16 (one 16-B chunk each)
-__device__ __forceinline__ void split8(const float4& x, const float4& y, u32x4& hi, u32x4& lo) {
-  const float f[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
-  bf16x8 h, l;
-  rsx::split_x3(f, h, l);
-  hi = __builtin_bit_cast(u32x4, h);
-  lo = __builtin_bit_cast(u32x4, l);
-}
 
 template <int EPI>
 __device__ __forceinline__ void epilogue(const GArgs& a, f32x16 (&acc)[2][2], int64_t m0, int n0, int wm, int wn,

@@ -29,8 +29,9 @@
 //               first group had gathered before the tile; finishes the recorded groups
 //   ge_group_k  NDCG_g and AUC_g of the G groups, block b its contiguous slice, a fixed-order sum
 //   ge_sum_k    the blocks' partial sums in block order -> the summary
-// The double sums have a fixed order (the scans' trees depend on the sizes only) and the integer sums
-// are exact: the outputs are the same bits every run. No float atomics.
+// The double sums have a fixed order (the trees of rsx_block.h's block_scan_excl depend on the sizes
+// only) and the integer sums are exact: the outputs are the same bits every run. No float atomics.
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include "rsx_x3.h"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -38,7 +39,7 @@
 
 namespace {
 
-using rsx::score_key;
+using rsx::at, rsx::block_scan_excl, rsx::score_key;
 
 constexpr int kThreads = 256, kPer = 8, kTile = kThreads * kPer;
 constexpr int kGroupBlocks = 256;  // most workgroups of ge_group_k (each one partial of the summary)
@@ -62,47 +63,6 @@ using SortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::
 hipError_t sort_pairs(void* tmp, size_t& bytes, const u64* kin, u64* kout, const uint8_t* vin, uint8_t* vout, int64_t R,
                       unsigned end_bit, hipStream_t st) {
   return rocprim::radix_sort_pairs<SortConfig>(tmp, bytes, kin, kout, vin, vout, (size_t)R, 0u, end_bit, st);
-}
-
-// ---- workgroup scans over any 4-byte-multiple type ------------------------------------------------
-template <class T>
-__device__ __forceinline__ T shfl_up_t(const T& v, int d) {
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  int w[sizeof(T) / 4];
-  memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (int k = 0; k < (int)(sizeof(T) / 4); ++k) w[k] = __shfl_up(w[k], d, 64);
-  T r;
-  memcpy(&r, w, sizeof(T));
-  return r;
-}
-
-// Exclusive scan of one value per thread, op(earlier, later) (it need not commute); total = all NT
-// values combined. sm holds NT / 64 values.
-template <int NT, class T, class Op>
-__device__ __forceinline__ T block_scan_excl(T x, Op op, T ident, T* sm, T& total) {
-  constexpr int NW = NT / 64;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T incl = x;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T y = shfl_up_t(incl, d);
-    if (lane >= d) incl = op(y, incl);
-  }
-  if (lane == 63) sm[w] = incl;
-  __syncthreads();
-  T pre = ident;
-  total = ident;
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    const T v = sm[k];
-    total = op(total, v);
-    if (k < w) pre = op(pre, v);
-  }
-  T e = shfl_up_t(incl, 1);
-  if (lane == 0) e = ident;
-  __syncthreads();  // sm is free for the next scan
-  return op(pre, e);
 }
 
 struct Cnt {  // negatives, group heads
@@ -441,8 +401,6 @@ __global__ void ge_sum_k(const double* __restrict__ part, int nblocks, i64* __re
   reinterpret_cast<double*>(summary)[4] = b;
 }
 
-int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
-
 struct GeLayout {
   int64_t keys, keys_o, lab, lab_o, neg, heads, ghead, thead, negoff, headoff, carry_g, carry_t, agg_head, agg_v, agg_d,
       rec_ord, rec_v, rec_d, part, temp, temp_bytes, total, tiles;
@@ -456,45 +414,35 @@ size_t sort_temp_bytes(int64_t R) {
 
 GeLayout ge_layout(int64_t R) {
   GeLayout l;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t r = o;
-    o += a256(bytes);
-    return r;
-  };
+  rsx::Bump bump{0, 256};
   l.tiles = (R + kTile - 1) / kTile;
-  l.keys = take(R * 8);
-  l.keys_o = take(R * 8);
-  l.lab = take(R);
-  l.lab_o = take(R);
-  l.neg = take(l.tiles * 4);
-  l.heads = take(l.tiles * 4);
-  l.ghead = take(l.tiles * 8);
-  l.thead = take(l.tiles * 8);
-  l.negoff = take(l.tiles * 4);
-  l.headoff = take(l.tiles * 4);
-  l.carry_g = take(l.tiles * 8);
-  l.carry_t = take(l.tiles * 8);
-  l.agg_head = take(l.tiles * 4);
-  l.agg_v = take(l.tiles * 8);
-  l.agg_d = take(l.tiles * 8);
-  l.rec_ord = take(l.tiles * 4);
-  l.rec_v = take(l.tiles * 8);
-  l.rec_d = take(l.tiles * 8);
-  l.part = take(kGroupBlocks * 4 * 8);
+  l.keys = bump.take(R * 8);
+  l.keys_o = bump.take(R * 8);
+  l.lab = bump.take(R);
+  l.lab_o = bump.take(R);
+  l.neg = bump.take(l.tiles * 4);
+  l.heads = bump.take(l.tiles * 4);
+  l.ghead = bump.take(l.tiles * 8);
+  l.thead = bump.take(l.tiles * 8);
+  l.negoff = bump.take(l.tiles * 4);
+  l.headoff = bump.take(l.tiles * 4);
+  l.carry_g = bump.take(l.tiles * 8);
+  l.carry_t = bump.take(l.tiles * 8);
+  l.agg_head = bump.take(l.tiles * 4);
+  l.agg_v = bump.take(l.tiles * 8);
+  l.agg_d = bump.take(l.tiles * 8);
+  l.rec_ord = bump.take(l.tiles * 4);
+  l.rec_v = bump.take(l.tiles * 8);
+  l.rec_d = bump.take(l.tiles * 8);
+  l.part = bump.take(kGroupBlocks * 4 * 8);
   // as binary_eval.hip: the sort's plan depends on the size, so take its largest request over R and
   // the powers of two below it (the total must not shrink where the plan changes)
   size_t tb = sort_temp_bytes(R);
   for (int64_t p = 1; p < R; p <<= 1) tb = std::max(tb, sort_temp_bytes(p));
   l.temp_bytes = (int64_t)tb;
-  l.temp = take(l.temp_bytes);
-  l.total = o;
+  l.temp = bump.take(l.temp_bytes);
+  l.total = bump.off;
   return l;
-}
-
-template <typename P>
-P* at(void* ws, int64_t off) {
-  return reinterpret_cast<P*>(reinterpret_cast<char*>(ws) + off);
 }
 
 }  // namespace

@@ -15,12 +15,14 @@
 //     threshold value go to the lowest column index) and a bitonic sort of the k winners.
 // Output order: mining value descending, then column index ascending (torch.topk leaves tie
 // order unspecified; ties need equal fp32 quotients, which random cosines do not produce).
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include "rsx_x3.h"
 
 namespace {
 
 using rsx::f32x16, rsx::ordered_key, rsx::tile_row;
+using rsx::bitonic_sort_desc, rsx::pow2_at_least;
 
 constexpr int kThreads = 256;
 constexpr int kRowsPerBlock = 128;
@@ -125,7 +127,10 @@ __global__ __launch_bounds__(256) void hnm_products_k(const float* __restrict__ 
   }
 }
 
-// Block-wide exclusive prefix of per-thread counts (256 threads); returns the block total.
+// Block-wide exclusive prefix of per-thread counts (256 threads); returns the block total. This scan
+// and find_bin below stay hnm_select_k's own: on rsx_block.h's block_scan_excl and digit_search_desc,
+// either one, hnm_mine measured about 0.7 % slower at N = 16,384 at the same occupancy (DESIGN.md,
+// section 4; profiles/block_prims_ab.json).
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_wt, uint32_t& excl) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   uint32_t inc = x;
@@ -143,33 +148,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_wt, 
   excl = base + inc - x;
   __syncthreads();
   return tot;
-}
-
-// wave 0: bins 255..0 scanned from the top; the bin where the running count reaches rem.
-// Writes s_out[0] = bin, s_out[1] = count strictly above that bin.
-__device__ __forceinline__ void find_bin(const uint32_t* s_hist, uint32_t rem, uint32_t* s_out) {
-  const int lane = threadIdx.x & 63;
-  uint32_t h[4], loc = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { h[q] = s_hist[255 - 4 * lane - q]; loc += h[q]; }
-  uint32_t inc = loc;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += t;
-  }
-  const unsigned long long hit = __ballot(inc >= rem);
-  const int first = __ffsll((long long)hit) - 1;  // rem <= total guarantees a hit
-  if (lane == first) {
-    uint32_t cum = inc - loc;
-    int bin = 255 - 4 * lane;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (cum + h[q] >= rem) { bin = 255 - 4 * lane - q; break; }
-      cum += h[q];
-    }
-    s_out[0] = (uint32_t)bin;
-    s_out[1] = cum;
-  }
 }
 
 // Per row: the k largest (mining value desc, column asc) of the row's masked cosines.
@@ -199,6 +177,31 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
   const int tid = threadIdx.x, lane = tid & 63;
   const int64_t row0 = (int64_t)blockIdx.x * R;
   const uint32_t kNegInf = ordered_key(-INFINITY);
+  // wave 0: bins 255..0 of s_hist scanned from the top; the bin where the running count reaches rem.
+  // Writes s_out[0] = bin, s_out[1] = count strictly above that bin.
+  auto find_bin = [&](uint32_t rem, uint32_t* s_out) {
+    uint32_t h[4], loc = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { h[q] = s_hist[255 - 4 * lane - q]; loc += h[q]; }
+    uint32_t inc = loc;
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    const unsigned long long hit = __ballot(inc >= rem);
+    const int first = __ffsll((long long)hit) - 1;  // rem <= total guarantees a hit
+    if (lane == first) {
+      uint32_t cum = inc - loc;
+      int bin = 255 - 4 * lane;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cum + h[q] >= rem) { bin = 255 - 4 * lane - q; break; }
+        cum += h[q];
+      }
+      s_out[0] = (uint32_t)bin;
+      s_out[1] = cum;
+    }
+  };
 
   for (int e = tid; e < R * D; e += kThreads) {
     const int r = e / D, c = e % D;
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
           if (x != -INFINITY) atomicAdd(&s_hist[min(255, (int)((x - lo) * scale))], 1u);
         }
         __syncthreads();
-        if ((tid >> 6) == 0) find_bin(s_hist, (uint32_t)k, s_sel);
+        if ((tid >> 6) == 0) find_bin((uint32_t)k, s_sel);
         __syncthreads();
         const int b = (int)s_sel[0];
         const uint32_t n_take = s_sel[1] + s_hist[b];  // everything above b plus bin b
@@ -283,8 +286,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
                   ((unsigned long long)ordered_key(x) << 32) | (uint32_t)(0xFFFFFFFFu - (uint32_t)j);
           }
           __syncthreads();
-          nsort = 1;
-          while (nsort < (int)n_take) nsort <<= 1;
+          nsort = pow2_at_least((int)n_take);
           for (int t = (int)n_take + tid; t < nsort; t += kThreads) s_sort[t] = 0ull;
           done = true;
         }
@@ -305,7 +307,7 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
           if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
-        if ((tid >> 6) == 0) find_bin(s_hist, rem, s_sel + 2);
+        if ((tid >> 6) == 0) find_bin(rem, s_sel + 2);
         __syncthreads();
         if (tid == 0) {
           s_sel[0] = prefix | (s_sel[2] << shift);
@@ -332,24 +334,10 @@ __global__ __launch_bounds__(kThreads) void hnm_select_k(const float* __restrict
         gt_base += t_gt;
         eq_base += t_eq;
       }
-      nsort = 1;
-      while (nsort < k) nsort <<= 1;
+      nsort = pow2_at_least(k);
       for (int t = k + tid; t < nsort; t += kThreads) s_sort[t] = 0ull;
     }
-    __syncthreads();
-    // bitonic sort of nsort codes, descending
-    for (int size = 2; size <= nsort; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < nsort / 2; t += kThreads) {
-          const int lo = 2 * t - (t & (stride - 1));
-          const int hi = lo + stride;
-          const bool desc = (lo & size) == 0;
-          const unsigned long long a = s_sort[lo], b = s_sort[hi];
-          if ((a < b) == desc) { s_sort[lo] = b; s_sort[hi] = a; }
-        }
-        __syncthreads();
-      }
-    }
+    bitonic_sort_desc<kThreads>(s_sort, nsort);  // its first barrier orders the writes above
     // outputs; the raw cosine is recomputed (also for ignored columns picked when fewer than
     // k are available: the reference's torch.gather(cos_sim, 1, top_k_indices), :690, 753, 818)
     for (int t = tid; t < k; t += kThreads) {
@@ -414,9 +402,8 @@ RSX_API int rsx_hnm_mine(const float* u_norm, const float* i_norm, const int64_t
   RSX_ARG(temperature > 0.0f, "temperature must be positive");
   RSX_ARG((int64_t)ws_bytes >= rsx_hnm_workspace_bytes(N), "workspace smaller than rsx_hnm_workspace_bytes(N)");
   RSX_ARG(((uintptr_t)ws & 15) == 0, "workspace must be 16-byte aligned");
-  int kpad = 1;
-  while (kpad < k) kpad <<= 1;
-  RSX_ARG(kpad <= 4096, "k must be <= 4096");
+  RSX_ARG(k <= 4096, "k must be <= 4096");
+  const int kpad = pow2_at_least((int)k);
   // sort buffer: the k winners, or (fast path) everything from the k-th value's bin upward
   const int buf = kpad * 2 > 1024 ? kpad * 2 : 1024;
   int R = 8;

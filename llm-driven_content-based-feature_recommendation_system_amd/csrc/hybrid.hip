@@ -434,7 +434,7 @@ __global__ void hybrid_gate_mean_k(const double* __restrict__ part, int slots, i
   }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using rsx::aligned16;
 
 template <typename K>
 int raise_lds(K kernel, size_t bytes, const char* fn) {

@@ -208,7 +208,7 @@ int64_t proj_slots(int64_t n) {
   return tiles < 1 ? 1 : (tiles > kProjMaxSlots ? kProjMaxSlots : tiles);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using rsx::aligned16;
 
 }  // namespace
 

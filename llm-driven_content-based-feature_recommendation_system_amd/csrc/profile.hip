@@ -23,8 +23,6 @@ namespace {
 
 constexpr int kD = 128, kKp = 128, kMaxTab = 16;
 
-int64_t al(int64_t floats) { return (floats + 63) / 64 * 64; }  // 256-B granules
-
 struct Cfg {
   int64_t U, src;  // output rows; input rows (row r reads input row r % src: both dropout views)
   int ntab, C, P, K, ncols;  // ncols = table columns (the projection's start column)
@@ -39,12 +37,11 @@ struct ArenaLayout {
 // them (out-of-range ids replaced by 0), [ntab][src] int64, what the backward scatters by
 ArenaLayout arena_layout(int64_t U) {
   ArenaLayout s{};
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += al(n); return r; };
-  s.flag = take(1); s.sid = take(2 * kMaxTab * U);
-  s.X = take(U * kKp); s.Wp = take(kD * kKp); s.H = take(U * kD); s.mean = take(U); s.rstd = take(U);
-  s.ug = take(kMaxTab + 1);
-  s.total = o;
+  rsx::Bump bump{0, 64};  // floats: 256-B granules
+  s.flag = bump.take(1); s.sid = bump.take(2 * kMaxTab * U);
+  s.X = bump.take(U * kKp); s.Wp = bump.take(kD * kKp); s.H = bump.take(U * kD); s.mean = bump.take(U); s.rstd = bump.take(U);
+  s.ug = bump.take(kMaxTab + 1);
+  s.total = bump.off;
   return s;
 }
 
@@ -57,15 +54,14 @@ struct WsLayout {
 };
 WsLayout ws_layout(int64_t U) {
   WsLayout s{};
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += al(n); return r; };
-  s.dY = take(U * kD); s.dH = take(U * kD); s.dX = take(U * kKp); s.dWp = take(kD * kKp); s.dgu = take(kMaxTab + 1);
+  rsx::Bump bump{0, 64};  // floats: 256-B granules
+  s.dY = bump.take(U * kD); s.dH = bump.take(U * kD); s.dX = bump.take(U * kKp); s.dWp = bump.take(kD * kKp); s.dgu = bump.take(kMaxTab + 1);
   s.n_wsw = rsx_linear_wgrad_workspace_floats(U, kD, kKp);
   s.n_wsl = rsx_ln_bwd_workspace_floats(U, kD);
   s.n_wse = ((U + 63) / 64) * (4096 + kMaxTab) + 1;  // >= rsx_static_embed_bwd_workspace_floats for any tables
-  s.wsw = take(s.n_wsw); s.wsl = take(s.n_wsl); s.wse = take(s.n_wse);
-  s.cpart = take(((U + kRowsPerBlk - 1) / kRowsPerBlk) * kNout);
-  s.total = o;
+  s.wsw = bump.take(s.n_wsw); s.wsl = bump.take(s.n_wsl); s.wse = bump.take(s.n_wse);
+  s.cpart = bump.take(((U + kRowsPerBlk - 1) / kRowsPerBlk) * kNout);
+  s.total = bump.off;
   return s;
 }
 

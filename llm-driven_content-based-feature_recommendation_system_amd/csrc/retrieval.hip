@@ -14,6 +14,7 @@
 // Pass 2 (topk_merge_k): per query, the 2 * nsplit lists are bitonic-sorted in LDS by
 // (score desc, index asc) and the first k are written. Ties therefore resolve to the lower
 // item index (documented tie-break; torch.topk leaves tie order unspecified).
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include "rsx_x3.h"
 #include <math.h>
@@ -21,6 +22,7 @@
 namespace {
 
 using rsx::f32x16, rsx::ordered_key, rsx::ordered_key_inv, rsx::tile_row;
+using rsx::bitonic_sort_desc, rsx::digit_search_desc, rsx::pow2_at_least, rsx::wave_scan_incl;
 constexpr int kD = 128;
 constexpr int kTile = 32;
 constexpr int kOwnRows = 128;
@@ -166,6 +168,28 @@ __global__ __launch_bounds__(256, 2) void topk_scan_k(ScanArgs a) {
   }
 }
 
+// Bitonic sort of the first P (a power of two) (score, idx) pairs in LDS by (score desc, idx asc). The
+// callers' barrier comes before it; the pairs are complete (and visible) on return.
+__device__ __forceinline__ void bitonic_desc(float* ss, int* si, int P) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = ((lo & size) == 0);  // descending runs first => overall descending
+        const float a0 = ss[lo], a1 = ss[hi];
+        const int b0 = si[lo], b1 = si[hi];
+        const bool swap = desc ? better(a1, b1, a0, b0) : better(a0, b0, a1, b1);
+        if (swap) {
+          ss[lo] = a1; ss[hi] = a0;
+          si[lo] = b1; si[hi] = b0;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // One workgroup per query: bitonic sort of NC = 2*nsplit*KMAX candidates, descending.
 template <int NC>
 __global__ __launch_bounds__(256) void topk_merge_k(const float* cs, const int* ci, int64_t Q, int ncand, int K,
@@ -189,23 +213,7 @@ __global__ __launch_bounds__(256) void topk_merge_k(const float* cs, const int* 
     }
   }
   __syncthreads();
-  for (int size = 2; size <= NC; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < NC / 2; t += blockDim.x) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = ((lo & size) == 0);  // descending runs first => overall descending
-        const float a0 = ss[lo], a1 = ss[hi];
-        const int b0 = si[lo], b1 = si[hi];
-        const bool swap = desc ? better(a1, b1, a0, b0) : better(a0, b0, a1, b1);
-        if (swap) {
-          ss[lo] = a1; ss[hi] = a0;
-          si[lo] = b1; si[hi] = b0;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_desc(ss, si, NC);
   for (int t = threadIdx.x; t < K; t += blockDim.x) {
     out_s[q * K + t] = ss[t];
     out_i[q * K + t] = (si[t] == 0x7fffffff) ? -1 : (int64_t)si[t];
@@ -348,28 +356,6 @@ __global__ __launch_bounds__(256, 2) void topk_fast_scan_k(FastArgs a) {
   }
 }
 
-// bitonic sort of NC (score, idx) pairs in LDS by (score desc, idx asc)
-template <int NC>
-__device__ __forceinline__ void bitonic_desc(float* ss, int* si) {
-  for (int size = 2; size <= NC; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < NC / 2; t += blockDim.x) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const float a0 = ss[lo], a1 = ss[hi];
-        const int b0 = si[lo], b1 = si[hi];
-        const bool swap = desc ? better(a1, b1, a0, b0) : better(a0, b0, a1, b1);
-        if (swap) {
-          ss[lo] = a1; ss[hi] = a0;
-          si[lo] = b1; si[hi] = b0;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // K2: t_q = k-th best candidate (or -inf if fewer valid candidates than k); count[q] = 0
 template <int NC>
 __global__ __launch_bounds__(256) void topk_thresh_k(const float* cs, const int* ci, int ncand, int K, float* thresh,
@@ -383,7 +369,7 @@ __global__ __launch_bounds__(256) void topk_thresh_k(const float* cs, const int*
     si[t] = ok ? ci[q * ncand + t] : 0x7fffffff;
   }
   __syncthreads();
-  bitonic_desc<NC>(ss, si);
+  bitonic_desc(ss, si, NC);
   if (threadIdx.x == 0) {
     const bool valid = si[K - 1] != 0x7fffffff;
     thresh[q] = valid ? ss[K - 1] : -INFINITY;
@@ -409,7 +395,7 @@ __global__ __launch_bounds__(256) void topk_final_k(const float* bs, const int* 
     si[t] = ok ? bi[q * cap + t] : 0x7fffffff;
   }
   __syncthreads();
-  bitonic_desc<NC>(ss, si);
+  bitonic_desc(ss, si, NC);
   for (int t = threadIdx.x; t < K; t += blockDim.x) {
     out_s[q * K + t] = ss[t];
     out_i[q * K + t] = (si[t] == 0x7fffffff) ? -1 : (int64_t)si[t];
@@ -783,27 +769,6 @@ __global__ __launch_bounds__(256, 2) void topk_bf16_collect_k(BfArgs a) {
     if (q0 + 32 * g < a.Q) a.buf_n[sbase[g]] = cnt[g];
 }
 
-// bitonic sort of the first P (power of two) entries, (score desc, idx asc)
-__device__ __forceinline__ void bitonic_desc_n(float* ss, int* si, int P) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = threadIdx.x; t < P / 2; t += blockDim.x) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const float a0 = ss[lo], a1 = ss[hi];
-        const int b0 = si[lo], b1 = si[hi];
-        const bool swap = desc ? better(a1, b1, a0, b0) : better(a0, b0, a1, b1);
-        if (swap) {
-          ss[lo] = a1; ss[hi] = a0;
-          si[lo] = b1; si[hi] = b0;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // delta_q (see the bf16 path's header): ||u|| and ||u - bf16(u)|| by fixed-order wave reductions
 // (every wave computes them), hdr = the corpus header of topk_bf16_prep_k
 __device__ __forceinline__ float query_delta(const float* U, int64_t ldu, int64_t q, const unsigned* hdr) {
@@ -860,32 +825,12 @@ __device__ float block_kth_largest(const float* v, int n, int K, int* hist, int*
       if ((k & mask) == prefix) atomicAdd(&hist[(k >> lo) & dm], 1);
     }
     __syncthreads();
-    if (threadIdx.x < 64) {  // lane l owns digits 255-4l .. 252-4l (descending)
-      const int l = threadIdx.x;
-      int c[4], sum = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        c[j] = hist[255 - 4 * l - j];
-        sum += c[j];
-      }
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (l >= o) incl += y;
-      }
-      const int excl = incl - sum;
-      if (excl < krem && krem <= incl) {
-        int acc = excl;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (acc + c[j] >= krem) {
-            sel[0] = 255 - 4 * l - j;
-            sel[1] = krem - acc;
-            break;
-          }
-          acc += c[j];
-        }
+    if (threadIdx.x < 64) {
+      int digit;
+      unsigned above;
+      if (digit_search_desc([&](int b) { return (unsigned)hist[b]; }, (unsigned)krem, lane, digit, above)) {
+        sel[0] = digit;
+        sel[1] = krem - (int)above;
       }
     }
     __syncthreads();
@@ -986,12 +931,7 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
       c8[u] = n < kStreamCap ? n : kStreamCap;
       sum += c8[u];
     }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(incl, o, 64);
-      if (lane >= o) incl += y;
-    }
+    const int incl = wave_scan_incl(sum);
     int run = incl - sum;
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
@@ -1136,14 +1076,13 @@ __global__ __launch_bounds__(256) void topk_bf16_select_k(const float2* __restri
       }
     }
   } else {
-    int P2 = 1;
-    while (P2 < n) P2 <<= 1;
+    const int P2 = pow2_at_least(n);
     for (int t = n + tid; t < P2; t += 256) {
       ms[t] = -INFINITY;
       mi[t] = 0x7fffffff;
     }
     __syncthreads();
-    bitonic_desc_n(ms, mi, P2);
+    bitonic_desc(ms, mi, P2);
     for (int t = tid; t < K; t += 256) {
       const bool ok = t < n;
       out_s[q * K + t] = ok ? ms[t] : -INFINITY;
@@ -1259,31 +1198,12 @@ __global__ __launch_bounds__(1024) void topk_fb_select_k(const int* __restrict__
       if ((k & mask) == prefix) atomicAdd(&hist[(int)((k >> lo) & dm)], 1);
     }
     __syncthreads();
-    if (tid < 64) {  // lane l owns digits 255-4l .. 252-4l (descending), as block_kth_largest
-      int c4[4], sum = 0;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        c4[u] = hist[255 - 4 * tid - u];
-        sum += c4[u];
-      }
-      int incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(incl, o, 64);
-        if (tid >= o) incl += y;
-      }
-      const int excl = incl - sum;
-      if (excl < krem && krem <= incl) {
-        int acc = excl;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if (acc + c4[u] >= krem) {
-            sel[0] = 255 - 4 * tid - u;
-            sel[1] = krem - acc;
-            break;
-          }
-          acc += c4[u];
-        }
+    if (tid < 64) {
+      int digit;
+      unsigned above;
+      if (digit_search_desc([&](int b) { return (unsigned)hist[b]; }, (unsigned)krem, lane, digit, above)) {
+        sel[0] = digit;
+        sel[1] = krem - (int)above;
       }
     }
     __syncthreads();
@@ -1300,26 +1220,11 @@ __global__ __launch_bounds__(1024) void topk_fb_select_k(const int* __restrict__
       if (slot < kLargeKMax) keys[slot] = k;
     }
   }
-  int P2 = 2;
-  while (P2 < K) P2 <<= 1;
-  __syncthreads();
+  // no barrier between the gather and the padding: the keys are distinct and K <= NI (host-checked), so
+  // exactly K of them reach prefix and the gather fills slots [0, K), the padding [K, P2)
+  const int P2 = pow2_at_least(K);
   for (int t = K + tid; t < P2; t += 1024) keys[t] = 0ull;  // below every real key
-  __syncthreads();
-  for (int size = 2; size <= P2; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (tid < P2 / 2) {
-        const int lo = 2 * tid - (tid & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = ((lo & size) == 0);
-        const u64 a0 = keys[lo], a1 = keys[hi];
-        if (desc ? a1 > a0 : a0 > a1) {
-          keys[lo] = a1;
-          keys[hi] = a0;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort_desc<1024>(keys, P2);
   for (int t = tid; t < K; t += 1024) {
     const unsigned id = ~(unsigned)keys[t];
     out_s[q * K + t] = row[id];

@@ -95,6 +95,25 @@ inline int cu_count() {
   return n;
 }
 
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// Workspace layouts: take(n) returns the running offset and advances it by n rounded up to the
+// granule (256 for byte layouts, 64 for float layouts: 256-B granules both); off ends as the total.
+struct Bump {
+  int64_t off, granule;
+  int64_t take(int64_t n) {
+    const int64_t r = off;
+    off += (n + granule - 1) / granule * granule;
+    return r;
+  }
+};
+
+// Typed pointer to byte offset off of a workspace.
+template <typename P>
+P* at(void* ws, int64_t off) {
+  return reinterpret_cast<P*>(reinterpret_cast<char*>(ws) + off);
+}
+
 // The Logloss head of the rerankers' training steps (csrc/deepfm_train.hip: head_k + head_sum_k),
 // arguments as rsx_deepfm_train_head after its checks; relu_mask: dh2 = g wo [h2 > 0], else g wo.
 int train_head_launch(const float* h2, const float* wo, const float* lin, const float* bias, const float* y,

@@ -37,6 +37,14 @@ __device__ __forceinline__ void split_x3(const float (&f)[N], V& hi, V& lo) {
     lo[k] = x3_lo(f[k], hk);
   }
 }
+// split_x3 of 8 fp32 as the staging stores take it: 8 hi + 8 lo bf16, one 16-B chunk each
+__device__ __forceinline__ void split8(const float4& x, const float4& y, u32x4& hi, u32x4& lo) {
+  const float f[8] = {x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w};
+  bf16x8 h, l;
+  split_x3(f, h, l);
+  hi = __builtin_bit_cast(u32x4, h);
+  lo = __builtin_bit_cast(u32x4, l);
+}
 
 // Token-major [rows][128] bf16 LDS image: 320-B rows plus a 16-B skew per 8-row group, i.e. byte
 // offset 320*row + 16*(row>>3) + 2*col. Conflict-free for the row reads (ds_read_b128, lane (c,h)

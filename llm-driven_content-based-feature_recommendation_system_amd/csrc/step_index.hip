@@ -24,11 +24,14 @@
 //   radix sort of the view-1 tokens by item id and of the (user, target) pairs by column,
 //   si_itemseg_k (the two-view segmented-sum plan), si_cols_k, si_pairs_k, si_pv_k (pretrained
 //   rows of the distinct items; si_tokens_k writes each token's slot among them).
+#include "rsx_block.h"
 #include "rsx_common.h"
 #include <hipcub/hipcub.hpp>
 #include <limits.h>
 
 namespace {
+
+using rsx::at, rsx::block_scan_excl;
 
 constexpr int kSegChunk = 64;  // ops._SEG_CHUNK
 
@@ -199,7 +202,7 @@ struct ScanJobs {
 __global__ __launch_bounds__(1024) void si_scan_k(ScanJobs js) {
   const ScanJob J = js.j[blockIdx.x];
   __shared__ int wsum[16];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   int carry = 0;
   for (int base = 0; base < J.n; base += 4096) {
     const int i0 = base + tid * 4;
@@ -209,32 +212,14 @@ __global__ __launch_bounds__(1024) void si_scan_k(ScanJobs js) {
       v[k] = i0 + k < J.n ? scan_xform(J.in[i0 + k], J.mode) : 0;
       s += v[k];
     }
-    int x = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    if (w == 0) {
-      int t = lane < 16 ? wsum[lane] : 0;
-#pragma unroll
-      for (int d = 1; d < 16; d <<= 1) {
-        const int y = __shfl_up(t, d, 64);
-        if (lane >= d) t += y;
-      }
-      if (lane < 16) wsum[lane] = t;
-    }
-    __syncthreads();
-    int e = carry + (w > 0 ? wsum[w - 1] : 0) + x - s;
+    int tot;
+    int e = carry + block_scan_excl<1024>(s, rsx::Sum(), 0, wsum, tot);  // wsum is free again on return
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (i0 + k < J.n) J.out[i0 + k] = e;
       e += v[k];
     }
-    carry += wsum[15];
-    __syncthreads();  // wsum is rewritten by the next tile
+    carry += tot;
   }
 }
 
@@ -429,8 +414,6 @@ __global__ __launch_bounds__(256) void si_pv_k(const float* lookup, int64_t ld, 
     reinterpret_cast<float4*>(pv + u * 128)[lane] = reinterpret_cast<const float4*>(lookup + uniq_items[u] * ld)[lane];
 }
 
-int64_t a256(int64_t x) { return (x + 255) / 256 * 256; }
-
 struct SiLayout {
   int64_t err, Tb, Nb, Eb, offT, offN, offE, srt, hist_t, hist_u, hist_i, colidx, itemidx, itemoff, chunkoff,
       pairoff, ikeys, ivals, ikeys_o, ivals_o, pkeys, pvals, pkeys_o, pvals_o, pair_b, pair_n, temp, temp_bytes,
@@ -453,48 +436,38 @@ size_t temp_bytes(int64_t B, int64_t L, int64_t n_items) {
 
 SiLayout si_layout(int64_t B, int64_t L, int64_t n_items) {
   SiLayout l;
-  int64_t o = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t r = o;
-    o += a256(bytes);
-    return r;
-  };
+  rsx::Bump bump{0, 256};
   const int64_t BL = B * L, ni = n_items + 1;
-  l.err = take(4);
-  l.Tb = take((B + 1) * 4);
-  l.Nb = take((B + 1) * 4);
-  l.Eb = take((B + 1) * 4);
-  l.offT = take((B + 1) * 4);
-  l.offN = take((B + 1) * 4);
-  l.offE = take((B + 1) * 4);
-  l.srt = take(BL * 4);
-  l.hist_t = take(ni * 4);
-  l.hist_u = take(ni * 4);
-  l.hist_i = take(ni * 4);
-  l.colidx = take(ni * 4);
-  l.itemidx = take(ni * 4);
-  l.itemoff = take(ni * 4);
-  l.chunkoff = take(ni * 4);
-  l.pairoff = take(ni * 4);
-  l.ikeys = take(BL * 4);
-  l.ivals = take(BL * 4);
-  l.ikeys_o = take(BL * 4);
-  l.ivals_o = take(BL * 4);
-  l.pkeys = take(BL * 4);
-  l.pvals = take(BL * 4);
-  l.pkeys_o = take(BL * 4);
-  l.pvals_o = take(BL * 4);
-  l.pair_b = take(BL * 4);
-  l.pair_n = take(BL * 4);
+  l.err = bump.take(4);
+  l.Tb = bump.take((B + 1) * 4);
+  l.Nb = bump.take((B + 1) * 4);
+  l.Eb = bump.take((B + 1) * 4);
+  l.offT = bump.take((B + 1) * 4);
+  l.offN = bump.take((B + 1) * 4);
+  l.offE = bump.take((B + 1) * 4);
+  l.srt = bump.take(BL * 4);
+  l.hist_t = bump.take(ni * 4);
+  l.hist_u = bump.take(ni * 4);
+  l.hist_i = bump.take(ni * 4);
+  l.colidx = bump.take(ni * 4);
+  l.itemidx = bump.take(ni * 4);
+  l.itemoff = bump.take(ni * 4);
+  l.chunkoff = bump.take(ni * 4);
+  l.pairoff = bump.take(ni * 4);
+  l.ikeys = bump.take(BL * 4);
+  l.ivals = bump.take(BL * 4);
+  l.ikeys_o = bump.take(BL * 4);
+  l.ivals_o = bump.take(BL * 4);
+  l.pkeys = bump.take(BL * 4);
+  l.pvals = bump.take(BL * 4);
+  l.pkeys_o = bump.take(BL * 4);
+  l.pvals_o = bump.take(BL * 4);
+  l.pair_b = bump.take(BL * 4);
+  l.pair_n = bump.take(BL * 4);
   l.temp_bytes = (int64_t)temp_bytes(B, L, n_items);
-  l.temp = take(l.temp_bytes);
-  l.total = o;
+  l.temp = bump.take(l.temp_bytes);
+  l.total = bump.off;
   return l;
-}
-
-template <typename P>
-P* at(void* ws, int64_t off) {
-  return reinterpret_cast<P*>(reinterpret_cast<char*>(ws) + off);
 }
 
 unsigned grid_for(int64_t n) {

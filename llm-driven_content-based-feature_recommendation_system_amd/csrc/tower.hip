@@ -27,8 +27,6 @@ namespace {
 constexpr int64_t kD = 128, kQKV = 384, kF = 256, kHeads = 4, kDh = 32, kMaxLayers = 8;
 constexpr int kEpiBias = 0, kEpiGeluDrop = 1, kEpiDgeluDrop = 2, kActGelu = 2;
 
-int64_t al(int64_t floats) { return (floats + 63) / 64 * 64; }  // 256-B granules
-
 struct LayerAct {
   int64_t qkv, a, lse, xs, hs, m2, r2, gg, act, f, xn, hn, mn, rn;
 };
@@ -41,24 +39,23 @@ struct Layout {  // float offsets into the arena
 // pv_rows: rows of item_proj's output (T, or the distinct items' Uq when the tokens read it by slot)
 Layout layout(int64_t T, int64_t U, int nl, int64_t pv_rows) {
   Layout s{};
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += al(n); return r; };
-  s.base = take(pv_rows * kD); s.x0 = take(T * kD); s.m0 = take(T); s.r0 = take(T);
-  s.h0 = take(T * kD); s.mh0 = take(T); s.rh0 = take(T);
+  rsx::Bump bump{0, 64};  // floats: 256-B granules
+  s.base = bump.take(pv_rows * kD); s.x0 = bump.take(T * kD); s.m0 = bump.take(T); s.r0 = bump.take(T);
+  s.h0 = bump.take(T * kD); s.mh0 = bump.take(T); s.rh0 = bump.take(T);
   for (int i = 0; i < nl; ++i) {
     LayerAct& a = s.l[i];
-    a.qkv = take(T * kQKV); a.a = take(T * kD); a.lse = take(T * kHeads);
-    a.xs = take(T * kD); a.hs = take(T * kD); a.m2 = take(T); a.r2 = take(T);
-    a.gg = take(T * kF); a.act = take(T * kF); a.f = take(T * kD);
-    a.xn = take(T * kD); a.hn = take(T * kD); a.mn = take(T); a.rn = take(T);
+    a.qkv = bump.take(T * kQKV); a.a = bump.take(T * kD); a.lse = bump.take(T * kHeads);
+    a.xs = bump.take(T * kD); a.hs = bump.take(T * kD); a.m2 = bump.take(T); a.r2 = bump.take(T);
+    a.gg = bump.take(T * kF); a.act = bump.take(T * kF); a.f = bump.take(T * kD);
+    a.xn = bump.take(T * kD); a.hn = bump.take(T * kD); a.mn = bump.take(T); a.rn = bump.take(T);
   }
-  s.prof = take(U * kD); s.hp = take(T * kD); s.g = take(T * kD); s.mo = take(T); s.ro = take(T);
-  s.o = take(T * kD); s.nrm = take(T);
+  s.prof = bump.take(U * kD); s.hp = bump.take(T * kD); s.g = bump.take(T * kD); s.mo = bump.take(T); s.ro = bump.take(T);
+  s.o = bump.take(T * kD); s.nrm = bump.take(T);
   // the tail (rows the losses read, see rsx_tower_fwd): gathered attention output and layer input,
   // and the row maps (int64, two floats each)
-  s.aR = take(T * kD); s.xR = take(T * kD); s.tidx = take(2 * T); s.tinv = take(2 * T); s.tuser = take(2 * T);
-  s.tseg = take(2 * (U + 1)); s.lseq = take(kHeads * U);
-  s.total = o;
+  s.aR = bump.take(T * kD); s.xR = bump.take(T * kD); s.tidx = bump.take(2 * T); s.tinv = bump.take(2 * T); s.tuser = bump.take(2 * T);
+  s.tseg = bump.take(2 * (U + 1)); s.lseq = bump.take(kHeads * U);
+  s.total = bump.off;
   return s;
 }
 
@@ -70,14 +67,13 @@ struct BwdLayout {  // float offsets into the workspace
 
 BwdLayout bwd_layout(int64_t T, int64_t U, int64_t L, int64_t C) {
   BwdLayout s{};
-  int64_t o = 0;
-  auto take = [&](int64_t n) { const int64_t r = o; o += al(n); return r; };
-  s.dO = take(T * kD); s.dG = take(T * kD); s.dHp = take(T * kD); s.dX = take(T * kD); s.dXs = take(T * kD);
-  s.dH = take(T * kD); s.dHs = take(T * kD); s.dF = take(T * kD); s.dPre = take(T * kF); s.dRes = take(T * kD);
-  s.dA = take(T * kD); s.dQKV = take(T * kQKV); s.dProf = take(U * kD); s.dBase = take(T * kD);
-  s.part = take((C > 0 ? C : 1) * kD);
-  s.dBaseU = take((C > 0 ? C : 1) * kD);  // per-distinct-item sums of dBase: Uq <= C rows
-  s.dAR = take((T + 1) * kD); s.dXR = take((T + 1) * kD);  // tail rows + one zero row (the expand's source)
+  rsx::Bump bump{0, 64};  // floats: 256-B granules
+  s.dO = bump.take(T * kD); s.dG = bump.take(T * kD); s.dHp = bump.take(T * kD); s.dX = bump.take(T * kD); s.dXs = bump.take(T * kD);
+  s.dH = bump.take(T * kD); s.dHs = bump.take(T * kD); s.dF = bump.take(T * kD); s.dPre = bump.take(T * kF); s.dRes = bump.take(T * kD);
+  s.dA = bump.take(T * kD); s.dQKV = bump.take(T * kQKV); s.dProf = bump.take(U * kD); s.dBase = bump.take(T * kD);
+  s.part = bump.take((C > 0 ? C : 1) * kD);
+  s.dBaseU = bump.take((C > 0 ? C : 1) * kD);  // per-distinct-item sums of dBase: Uq <= C rows
+  s.dAR = bump.take((T + 1) * kD); s.dXR = bump.take((T + 1) * kD);  // tail rows + one zero row (the expand's source)
   int64_t w = 0;
   const int64_t nk[5][3] = {{T, kD, kD}, {T, kQKV, kD}, {T, kD, kF}, {T, kF, kD}, {U, kD, kD}};
   for (auto& q : nk) {
@@ -87,8 +83,8 @@ BwdLayout bwd_layout(int64_t T, int64_t U, int64_t L, int64_t C) {
   s.n_wsw = w;
   s.n_wsl = rsx_ln_bwd_workspace_floats(T, kD);
   s.n_wse = rsx_seq_embed_bwd_workspace_floats(T, L, kD);
-  s.wsw = take(s.n_wsw); s.wsl = take(s.n_wsl); s.wse = take(s.n_wse);
-  s.total = o;
+  s.wsw = bump.take(s.n_wsw); s.wsl = bump.take(s.n_wsl); s.wse = bump.take(s.n_wse);
+  s.total = bump.off;
   return s;
 }
 

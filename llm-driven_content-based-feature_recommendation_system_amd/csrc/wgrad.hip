@@ -22,7 +22,7 @@
 
 namespace {
 
-using rsx::bf16x8, rsx::f32x16, rsx::img_off, rsx::kImgRow, rsx::tile_row, rsx::u32x4;
+using rsx::bf16x8, rsx::f32x16, rsx::img_off, rsx::kImgRow, rsx::split8, rsx::tile_row, rsx::u32x4;
 constexpr int kTile = 128;   // output tile (n and k)
 constexpr int kStage = 32;   // tokens per LDS stage
 
@@ -150,14 +150,6 @@ struct X3Img {
   __bf16 hi[kElems];
   __bf16 lo[kElems];
 };
-
-__device__ __forceinline__ void split8(const float4& a, const float4& b, u32x4& hi, u32x4& lo) {
-  const float f[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  bf16x8 h, l;
-  rsx::split_x3(f, h, l);
-  hi = __builtin_bit_cast(u32x4, h);
-  lo = __builtin_bit_cast(u32x4, l);
-}
 
 // STAGE = tokens per LDS stage: 32 (80 KB LDS, two workgroups per CU) or 16 (40 KB, three).
 template <int STAGE>
