@@ -115,6 +115,10 @@ int rsx_mha_qkv_fwd_x3(const float* x, const float* w, const float* bias, const 
  *   6 (MASK_K1|K2)    + also k2 (user) keys               (live inbatch_corrected_logq_loss :826-861)
  *   9 (EXCL_DIAG|POS) SupCon term of duorec_loss_refined (:595-625): diagonal excluded,
  *                     positives k1_i == k1_j != 0, loss_i = LSE_i - mean positive logit
+ *   18 (MASK_K1|DIAG_NOBIAS) flags 2 with the label logit left uncorrected: S_ii = <A_i,B_i>/tau, the
+ *                     bias on the other columns only (efficient_corrected_logq_loss with lambda > 0,
+ *                     tower_code/mined_inference.py:751-789: its "positive recovery"). 16 alone or with
+ *                     any other bit is refused.
  * Keys are int32. D = 128 (row strides lda/ldb >= 128, multiple of 4, 16-B aligned).
  * ws: rsx_nce_workspace_floats(N, M, nsplit_fwd, nsplit_bwd) floats, shared by fwd and bwd.
  * out2 (device, 2 floats) = {sum of row losses over valid rows, number of valid rows};
@@ -351,6 +355,15 @@ int64_t rsx_gemm_x3_split_floats(int64_t M, int N, int K);
 int rsx_gemm_x3_ws(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M, int N,
                    int K, int epi, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C, int64_t ldc,
                    float* ws, int64_t ws_floats, void* stream);
+/* The ReLU feed-forward's first GEMM with gradients (nn.TransformerEncoderLayer's default activation:
+ * dropout(relu(linear1(x))) of HybridUserTower's encoder, tower_code/mined_inference.py:635-638, in
+ * training): z = A . B^T + bias, C = dropout_p(max(z, 0)) with keep-mask hash(seed, m*N + n) as epi 1,
+ * aux[m][n] = z > 0 ? 1 : 0 (required; 16-byte aligned, ldaux >= N and a multiple of 4, as C and ldc).
+ * Its backward is epi 2 of rsx_gemm_x3 / rsx_gemm_x3_tn with the same aux, p_drop and seed. Shapes,
+ * ws and ws_floats as rsx_gemm_x3_ws. */
+int rsx_gemm_x3_relu_train(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M,
+                           int N, int K, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C,
+                           int64_t ldc, float* ws, int64_t ws_floats, void* stream);
 /* C = epi(A . Bt + bias) with Bt [K, N] as stored (row stride ldbt >= N): the input gradient
  * dX = dY . W of the same token linears straight from W [out, in] (K = out, N = in; autograd's
  * dX GEMM of nn.Linear, v1_refine_usertower.py:447-510), no transposed copy of W; epi / aux /
@@ -1006,6 +1019,52 @@ int rsx_hybrid_fuse_fwd(const float* seq_out, int64_t B, int64_t L, int64_t D, c
                         const float* w2, const float* b2, const float* ln_w, const float* ln_b, float ln_eps,
                         float eps, float* out, float* v_seq, float* gate_mean, void* ws, int64_t ws_bytes,
                         int32_t* flag, void* stream);
+
+/* ---- HybridUserTower with gradients: the adapter's and the fusion's training forward and backward ----
+ * rsx_hybrid_adapter_train_fwd: rsx_hybrid_adapter_fwd over ids [R] (required) with the two Dropout(p_drop)
+ * after the GELUs (tower_code/mined_inference.py:582-602 in training): m = (drop_c(gelu(LN(Wc c + bc))) + c) +
+ * drop_g(gelu(LN(Wg g + bg))), keep = hash(seed, r * 128 + col) >= p_drop 2^32 (seed_c, seed_g). Writes
+ * merged and / or seq_in (nullable, one required) and, for the backward, the gathered rows xc [R, 128],
+ * xg [R, 64] and the pre-LayerNorm products zc, zg [R, 128] (1,792 bytes per row).
+ * rsx_hybrid_adapter_bwd: from dy [R, 128] = d seq_in (gscale = the forward's scale) or d merged (gscale = 1):
+ * dzc, dzg [R, 128] = the gradients of the two products (dWc = dzc^T xc, dbc = column sums of dzc; so Wg, bg);
+ * dc [R, 128] = gscale dy + dzc Wc, dg [R, 64] = dzg Wg (exact fp32 MFMA), the gradients of the gathered rows;
+ * dln [4][128] = d lnc_w, d lnc_b, d lng_w, d lng_b, per-workgroup partials in ws
+ * (rsx_hybrid_adapter_bwd_workspace_floats(R) floats) added in workgroup order. The gradient of the time
+ * rows is dy itself. No atomics: identical inputs give identical bits.
+ * rsx_hybrid_fuse_train_fwd: rsx_hybrid_fuse_fwd over all B L rows with each token's own Dropout(p_drop)
+ * masks over its copies of the two projected rows (the reference applies gnn_proj / meta_proj to the expanded
+ * [B, L, 128] tensors, :514-577): f = v + g0 drop_a(u_gnn[u]) + g1 drop_b(u_meta[u]), keep index token_row *
+ * 128 + col (seed_a, seed_b). The gate means are those of the gates, before dropout.
+ * rsx_hybrid_fuse_bwd: from dout [B L, 128] and dv (gradient of v_seq, nullable), recomputing the forward
+ * from its inputs: dx [B L, 128] = d seq_out; dpre [B L, 64] = the gradient of the gate's pre-activations
+ * (dW1 = dpre^T v_seq, db1 = its column sums); du_gnn, du_meta [B, 128] = each user's L token rows added in
+ * position order; dsmall [386] = d ln_w [128] | d ln_b [128] | d W2 [2][64] | d b2 [2]. A row at the eps
+ * floor of either normalise is divided by eps (a constant): an all-zero seq_out row with zero upstream
+ * gradients gives exact zeros. ws: rsx_hybrid_fuse_bwd_workspace_floats(B, L) floats, 16-byte aligned. */
+int rsx_hybrid_adapter_train_fwd(const float* content, int64_t ldc, int64_t Nc, int64_t Dc, const float* gnn,
+                                 int64_t ldg, int64_t Ng, int64_t Dg, const int64_t* ids, int64_t R, const float* wc,
+                                 const float* bc, const float* lnc_w, const float* lnc_b, const float* wg,
+                                 const float* bg, const float* lng_w, const float* lng_b, float ln_eps,
+                                 const int64_t* deltas, const float* time_tab, float scale, float p_drop,
+                                 uint64_t seed_c, uint64_t seed_g, float* merged, float* seq_in, float* xc, float* xg,
+                                 float* zc, float* zg, int32_t* flag, void* stream);
+int64_t rsx_hybrid_adapter_bwd_workspace_floats(int64_t R);
+int rsx_hybrid_adapter_bwd(const float* dy, float gscale, int64_t R, const float* zc, const float* zg, const float* wc,
+                           const float* wg, const float* lnc_w, const float* lnc_b, const float* lng_w,
+                           const float* lng_b, float ln_eps, float p_drop, uint64_t seed_c, uint64_t seed_g, float* dzc,
+                           float* dzg, float* dc, float* dg, float* dln, float* ws, int64_t ws_floats, void* stream);
+int rsx_hybrid_fuse_train_fwd(const float* seq_out, int64_t B, int64_t L, const float* u_gnn, const float* u_meta,
+                              const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_w,
+                              const float* ln_b, float ln_eps, float eps, float p_drop, uint64_t seed_a,
+                              uint64_t seed_b, float* out, float* v_seq, float* gate_mean, void* ws, int64_t ws_bytes,
+                              int32_t* flag, void* stream);
+int64_t rsx_hybrid_fuse_bwd_workspace_floats(int64_t B, int64_t L);
+int rsx_hybrid_fuse_bwd(const float* seq_out, int64_t B, int64_t L, const float* u_gnn, const float* u_meta,
+                        const float* w1, const float* b1, const float* w2, const float* b2, const float* ln_w,
+                        const float* ln_b, float ln_eps, float eps, float p_drop, uint64_t seed_a, uint64_t seed_b,
+                        const float* dout, const float* dv, float* dx, float* dpre, float* du_gnn, float* du_meta,
+                        float* dsmall, float* ws, int64_t ws_floats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 14 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 15 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -106,6 +106,8 @@ _SIGS = {
     "rsx_gemm_x3_split_floats": (c_i64, [c_i64, c_i, c_i]),
     "rsx_gemm_x3_ws": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64, c_p,
                              c_i64, c_p]),
+    "rsx_gemm_x3_relu_train": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64,
+                                     c_p, c_i64, c_p]),
     "rsx_gemm_x3_tn": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64,
                              c_p]),
     "rsx_loss_combine": (c_i, [c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_f, c_p, c_p, c_p]),
@@ -199,6 +201,17 @@ _SIGS = {
     "rsx_hybrid_fuse_slots": (c_i64, [c_i64]),
     "rsx_hybrid_fuse_fwd": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p,
                                   c_f, c_f, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
+    "rsx_hybrid_adapter_train_fwd": (c_i, [c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_p,
+                                           c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_f, c_f, c_u64, c_u64, c_p,
+                                           c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_hybrid_adapter_bwd_workspace_floats": (c_i64, [c_i64]),
+    "rsx_hybrid_adapter_bwd": (c_i, [c_p, c_f, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_u64, c_u64,
+                                     c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "rsx_hybrid_fuse_train_fwd": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f,
+                                        c_u64, c_u64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p]),
+    "rsx_hybrid_fuse_bwd_workspace_floats": (c_i64, [c_i64, c_i64]),
+    "rsx_hybrid_fuse_bwd": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_u64,
+                                  c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

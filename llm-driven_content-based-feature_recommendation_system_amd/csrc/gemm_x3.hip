@@ -19,6 +19,8 @@
 //   EPI_DGELU_DROP C = acc * keep(m, n) / (1 - p) * aux[m][n]   (backward of the above:
 //                  acc = dAct = dY2 . W2)
 //   EPI_RELU       C = max(acc + bias, 0)   (inference only: no aux, no dropout; rsx_gemm_x3's epi 3)
+//   EPI_RELU_DROP  z = acc + bias; C = dropout_p(max(z, 0)); aux = z > 0 ? 1 : 0, so that EPI_DGELU_DROP
+//                  is its backward too (rsx_gemm_x3_relu_train: the ReLU feed-forward with gradients)
 //   EPI_ADDLN      (weight-stationary, N = 128) the residual add + LayerNorm after the
 //                  attention out-projection: C = s = aux + dropout_p(acc + bias),
 //                  y = LayerNorm(s) * ln_w + ln_b, with the row's mean / rstd saved
@@ -46,6 +48,7 @@ constexpr int kF4 = kBK / 8;   // float4 loads per thread and operand per stage 
 constexpr int EPI_BIAS = 0, EPI_GELU_DROP = 1, EPI_DGELU_DROP = 2, EPI_ROWADD = 3, EPI_ADDLN = 4;
 constexpr int EPI_RELU = 5;       // internal number; the public epi 3 of rsx_gemm_x3 / rsx_gemm_x3_ws
 constexpr int kPublicRelu = 3;
+constexpr int EPI_RELU_DROP = 6;  // internal only: rsx_gemm_x3_relu_train
 #ifndef RSX_GEMM_BLOCKS
 #define RSX_GEMM_BLOCKS (1 << 30)  // workgroup budget of the multi-tile stream: at BK 16 one tile each measured best
 #endif
@@ -156,6 +159,11 @@ __device__ __forceinline__ void epilogue(const GArgs& a, f32x16 (&acc)[2][2], in
           if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
         } else if (EPI == EPI_RELU) {
           v = fmaxf(v + bn, 0.0f);
+        } else if (EPI == EPI_RELU_DROP) {
+          v += bn;
+          a.aux[m * a.ldaux + n] = v > 0.0f ? 1.0f : 0.0f;
+          v = fmaxf(v, 0.0f);
+          if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
         } else if (a.drop.active()) {
           v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
         }
@@ -336,6 +344,11 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_k(GArgs a) {
     if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
   } else if (EPI == EPI_RELU) {
     v = fmaxf(v + bn, 0.0f);
+  } else if (EPI == EPI_RELU_DROP) {
+    v += bn;
+    a.aux[m * a.ldaux + n] = v > 0.0f ? 1.0f : 0.0f;
+    v = fmaxf(v, 0.0f);
+    if (a.drop.active()) v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
   } else if (a.drop.active()) {
     v = keep(a.drop, (uint32_t)m * (uint32_t)a.N + (uint32_t)n) ? v * a.drop.scale : 0.0f;
   }
@@ -440,7 +453,8 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws_k(WsArgs w) {
     int64_t m = (s_first + (int64_t)(t / KC) * s_step) * 32 + c;
     if (m >= a.M) m = a.M - 1;
     float* crow = a.C + m * a.ldc + n0 + 4 * h;
-    float* xrow = (EPI == EPI_GELU_DROP || EPI == EPI_DGELU_DROP) ? a.aux + m * a.ldaux + n0 + 4 * h : nullptr;
+    float* xrow = (EPI == EPI_GELU_DROP || EPI == EPI_DGELU_DROP || EPI == EPI_RELU_DROP)
+                      ? a.aux + m * a.ldaux + n0 + 4 * h : nullptr;
     // EPI_DGELU_DROP / EPI_ROWADD: the strip's saved GELU derivatives / added table rows are
     // loaded before its MFMAs (vmcnt retires in order, so a load issued at the epilogue
     // would drain the prefetched strips)
@@ -560,6 +574,12 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws_k(WsArgs w) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
         }
+        if (EPI == EPI_RELU_DROP) {
+          *reinterpret_cast<float4*>(xrow + o) = make_float4(v[0] > 0.0f ? 1.0f : 0.0f, v[1] > 0.0f ? 1.0f : 0.0f,
+                                                             v[2] > 0.0f ? 1.0f : 0.0f, v[3] > 0.0f ? 1.0f : 0.0f);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.0f);
+        }
         if (EPI == EPI_GELU_DROP) {
           float d[4];
 #pragma unroll
@@ -568,7 +588,7 @@ __global__ __launch_bounds__(kWsThreads, 1) void gemm_ws_k(WsArgs w) {
           }
           if (a.aux) *reinterpret_cast<float4*>(xrow + o) = make_float4(d[0], d[1], d[2], d[3]);
         }
-        if ((EPI == EPI_GELU_DROP || EPI == EPI_DGELU_DROP) && a.drop.active()) {
+        if ((EPI == EPI_GELU_DROP || EPI == EPI_DGELU_DROP || EPI == EPI_RELU_DROP) && a.drop.active()) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = keep(a.drop, e0 + o + e) ? v[e] * a.drop.scale : 0.0f;
         }
@@ -649,6 +669,8 @@ void launch_ws(const GArgs& g, hipStream_t st) {
     hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_GELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else if (g.epi == EPI_RELU)
     hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_RELU>), dim3(grid), dim3(kWsThreads), 0, st, w);
+  else if (g.epi == EPI_RELU_DROP)
+    hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_RELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
   else hipLaunchKernelGGL((gemm_ws_k<KC, NBW, EPI_DGELU_DROP>), dim3(grid), dim3(kWsThreads), 0, st, w);
 }
 
@@ -680,13 +702,18 @@ RSX_API int64_t rsx_gemm_x3_split_floats(int64_t M, int N, int K) {
 
 static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M,
                         int N, int K, int epi, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C,
-                        int64_t ldc, float* ws, int64_t ws_floats, void* stream) {
+                        int64_t ldc, float* ws, int64_t ws_floats, void* stream, bool relu_train = false) {
   RSX_ARG(A && B && C, "null tensor");
   RSX_ARG(M >= 0 && N > 0 && K > 0 && N % kBN == 0 && K % kBK == 0, "N must be a multiple of 128, K of 32");
   static_assert(kBK == 16 || kBK == 32, "stage depth 16 or 32");
   RSX_ARG(lda >= K && ldb >= K && ldc >= N && lda % 4 == 0 && ldb % 4 == 0, "bad leading dimensions");
   RSX_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0, "A/B must be 16-byte aligned");
-  if (epi == kPublicRelu) {
+  if (relu_train) {
+    RSX_ARG(aux && ldaux >= N && ldaux % 4 == 0 && ((uintptr_t)aux % 16) == 0,
+            "the training ReLU epilogue needs aux [M, >=N], 16-byte aligned, row stride a multiple of 4");
+    RSX_ARG(ldc % 4 == 0 && ((uintptr_t)C % 16) == 0, "C must be 16-byte aligned, row stride a multiple of 4");
+    epi = EPI_RELU_DROP;
+  } else if (epi == kPublicRelu) {
     RSX_ARG(!aux && p_drop == 0.0f, "the ReLU epilogue is inference only: aux must be null and p_drop 0");
     epi = EPI_RELU;
   } else {
@@ -729,6 +756,8 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
     if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_BIAS>, dim3(rb), dim3(256), 0, st, g);
     else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_GELU_DROP>, dim3(rb), dim3(256), 0, st, g);
     else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU>, dim3(rb), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU_DROP)
+      hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU_DROP>, dim3(rb), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_DGELU_DROP>, dim3(rb), dim3(256), 0, st, g);
     RSX_LAUNCHED();
     return 0;
@@ -747,10 +776,14 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
     else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
     else if (epi == EPI_RELU && b32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4, 32>), dim3(grid), dim3(256), 0, st, g);
     else if (epi == EPI_RELU) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4>), dim3(grid), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU_DROP && b32)
+      hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+    else if (epi == EPI_RELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
     else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);  // Q = 4 spills here
   } else if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_BIAS>, dim3(grid), dim3(256), 0, st, g);
   else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_GELU_DROP>, dim3(grid), dim3(256), 0, st, g);
   else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU>, dim3(grid), dim3(256), 0, st, g);
+  else if (epi == EPI_RELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU_DROP>, dim3(grid), dim3(256), 0, st, g);
   else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);
   RSX_LAUNCHED();
   return 0;
@@ -766,6 +799,16 @@ RSX_API int rsx_gemm_x3_ws(const float* A, int64_t lda, const float* B, int64_t 
                            int N, int K, int epi, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C,
                            int64_t ldc, float* ws, int64_t ws_floats, void* stream) {
   return gemm_x3_impl(A, lda, B, ldb, bias, M, N, K, epi, aux, ldaux, p_drop, seed, C, ldc, ws, ws_floats, stream);
+}
+
+// The ReLU feed-forward's first GEMM with gradients: z = A . B^T + bias, C = dropout_p(max(z, 0)) (keep
+// mask = hash(seed, m * N + n), as EPI_GELU_DROP), aux[m][n] = z > 0 ? 1 : 0. Its backward is epi 2 of
+// rsx_gemm_x3 / rsx_gemm_x3_tn with the same aux, p_drop and seed. Shapes and ws as rsx_gemm_x3_ws.
+RSX_API int rsx_gemm_x3_relu_train(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
+                                   int64_t M, int N, int K, float* aux, int64_t ldaux, float p_drop, uint64_t seed,
+                                   float* C, int64_t ldc, float* ws, int64_t ws_floats, void* stream) {
+  return gemm_x3_impl(A, lda, B, ldb, bias, M, N, K, EPI_BIAS, aux, ldaux, p_drop, seed, C, ldc, ws, ws_floats, stream,
+                      true);
 }
 
 // C = epi(A . Bt + bias) with the right operand as stored, Bt [K, N] (row stride ldbt >= N): the

@@ -20,6 +20,9 @@ constexpr int kOwnRows = 32 * kWaves;  // owner rows per workgroup
 constexpr int kLdsStride = kD + 4;     // padded row (conflict-free ds_read_b128 columns)
 
 enum : int { F_EXCL_DIAG = 1, F_MASK_K1 = 2, F_MASK_K2 = 4, F_POS = 8 };
+// the label logit carries no bias: S_ii = <A_i, B_i> / tau ("positive recovery" of
+// efficient_corrected_logq_loss, tower_code/mined_inference.py:772-775); plain kernels, with F_MASK_K1 only
+enum : int { F_DIAG_NOBIAS = 16 };
 enum : int { RSX_NCE_FP32 = 0, RSX_NCE_BF16X3 = 1, RSX_NCE_F16 = 2 };  // logit/gradient precision of the grouped kernels
 constexpr int kNsplitBwdGrouped = 8;  // split partials the grouped backward's region is sized for (GroupedLayout)
 
@@ -73,7 +76,8 @@ struct MergeArgs {
   int nsplit;
   const float* part;
   int pos_mode;      // 0: label = diagonal, 1: label = positive set
-  float* lse;        // [N]
+  int diag_nobias;   // F_DIAG_NOBIAS: the label logit without its bias
+  float* lse;       // [N]
   float* row_loss;   // [N]
   float* row_valid;  // [N] 0/1
   float* inv_cnt;    // [N] (pos mode) or nullptr
@@ -153,7 +157,8 @@ inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 inline bool valid_flags(int f) {
   // supported combinations (see header)
-  return f == 0 || f == F_MASK_K1 || f == (F_MASK_K1 | F_MASK_K2) || f == (F_EXCL_DIAG | F_POS);
+  return f == 0 || f == F_MASK_K1 || f == (F_MASK_K1 | F_MASK_K2) || f == (F_EXCL_DIAG | F_POS) ||
+         f == (F_MASK_K1 | F_DIAG_NOBIAS);
 }
 
 // fn(std::integral_constant<int, FL>) for the kernel instantiation FL of a valid flag combination
@@ -163,6 +168,7 @@ void with_flags(int flags, Fn&& fn) {
     case 0: fn(std::integral_constant<int, 0>{}); break;
     case F_MASK_K1: fn(std::integral_constant<int, F_MASK_K1>{}); break;
     case F_MASK_K1 | F_MASK_K2: fn(std::integral_constant<int, F_MASK_K1 | F_MASK_K2>{}); break;
+    case F_MASK_K1 | F_DIAG_NOBIAS: fn(std::integral_constant<int, F_MASK_K1 | F_DIAG_NOBIAS>{}); break;
     default: fn(std::integral_constant<int, F_EXCL_DIAG | F_POS>{}); break;
   }
 }

@@ -13,6 +13,9 @@
 //   * duorec_loss_refined sup      v1_refine_usertower.py:595-625: excluded = (i==j),
 //       positives M_ij = (t_i==t_j) && t_i!=0 && i!=j, loss_i = LSE_i - sum_j M_ij S_ij / sum_j M_ij
 //   * item-tower SimCSE loss       item_tower.py:1075-1082 (both directions = two calls)
+//   * logq_correction_loss         tower_code/mined_inference.py:738-749: flags 2, bias_j = lambda log(p_j + 1e-4) / tau
+//   * efficient_corrected_logq_loss  mined_inference.py:751-789: the same with the label logit restored to
+//       <A_i, B_i> / tau (F_DIAG_NOBIAS: the bias applies off the diagonal only)
 //
 // This file: the plain (ungrouped) kernels and the small kernels every family launches, behind
 // nce_common.h's launchers. Grouped form: nce_grouped*.hip; emphasis: nce_emphasis.hip.
@@ -116,9 +119,9 @@ __global__ __launch_bounds__(256, 2) void nce_fwd_k(FwdArgs a) {
         for (int e = 0; e < 4; ++e) {
           const int r = 4 * q4 + e;
           const int64_t j = j0 + rbase + e;
-          const float s = acc[r] * a.inv_tau - bia[e];
-          bool excl = (j >= j_end) || !row_ok;
           const bool offdiag = (j != i + a.diag_off);
+          const float s = acc[r] * a.inv_tau - (((FL & F_DIAG_NOBIAS) && !offdiag) ? 0.0f : bia[e]);
+          bool excl = (j >= j_end) || !row_ok;
           if (FL & F_EXCL_DIAG) excl = excl || !offdiag;
           if (FL & F_MASK_K1) excl = excl || (offdiag && kk1[e] == k1i);
           if (FL & F_MASK_K2) excl = excl || (offdiag && kk2[e] == k2i);
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(256) void nce_merge_k(MergeArgs a) {
     const float2 y = reinterpret_cast<const float2*>(a.B + (i + a.diag_off) * a.ldb)[lane];
     float d = x.x * y.x + x.y * y.y;
     for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-    const float sii = d * a.inv_tau - (a.bias ? a.bias[i + a.diag_off] : 0.0f);
+    const float sii = d * a.inv_tau - ((a.bias && !a.diag_nobias) ? a.bias[i + a.diag_off] : 0.0f);
     loss = lse - sii;
     valid = 1.0f;
   } else {
@@ -351,9 +354,9 @@ __global__ __launch_bounds__(256, 2) void nce_bwd_k(BwdArgs a) {
             lse_i = mm0[e]; w_i = mm1[e]; icnt_i = mm2[e]; bias_j = o_bias;
             k1_i = kk1[e]; k1_j = o_k1; k2_i = kk2[e]; k2_j = o_k2;
           }
-          const float sv = acc[r] * a.inv_tau - bias_j;
-          bool excl = (sidx >= s_end) || !own_ok;
           const bool offdiag = (jj != ii + a.diag_off);
+          const float sv = acc[r] * a.inv_tau - (((FL & F_DIAG_NOBIAS) && !offdiag) ? 0.0f : bias_j);
+          bool excl = (sidx >= s_end) || !own_ok;
           if (FL & F_EXCL_DIAG) excl = excl || !offdiag;
           if (FL & F_MASK_K1) excl = excl || (offdiag && k1_i == k1_j);
           if (FL & F_MASK_K2) excl = excl || (offdiag && k2_i == k2_j);
@@ -463,6 +466,7 @@ int plain_fwd(const float* A, const float* B, const float* bias, const int* k1a,
   ma.nsplit = L.nf;
   ma.part = fa.part;
   ma.pos_mode = (flags & F_POS) ? 1 : 0;
+  ma.diag_nobias = (flags & F_DIAG_NOBIAS) ? 1 : 0;
   ma.lse = ws + L.lse; ma.row_loss = ws + L.row_loss; ma.row_valid = ws + L.row_valid; ma.inv_cnt = ws + L.inv_cnt;
   hipLaunchKernelGGL(nce_merge_k, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, ma);
   RSX_LAUNCHED();

@@ -18,6 +18,7 @@ NCE_PLAIN = 0
 NCE_MASK_ITEM = 2
 NCE_MASK_ITEM_USER = 6
 NCE_SUPCON = 9
+NCE_MASK_ITEM_POS = 18  # NCE_MASK_ITEM with the label logit left without its bias (plain kernels only)
 
 _NSPLIT_FWD = 8
 # partial slots of the grouped forward; the fused forward (rsx_nce_grouped_fwd_grad) accepts 1/2/4/8 and
@@ -747,6 +748,8 @@ def nce_sum(A, B, bias=None, k1a=None, k1b=None, k2a=None, k2b=None, tau=0.1, fl
             tag="nce", precision=None):
     """(sum of row losses, valid-row count) of S = A B^T / tau - bias; row i's label column
     is i + diag_offset (see include/recsys_amd.h).
+    flags: NCE_PLAIN, NCE_MASK_ITEM, NCE_MASK_ITEM_USER, NCE_SUPCON, or NCE_MASK_ITEM_POS (18: NCE_MASK_ITEM
+    with the label logit S_ii left without its bias; plain kernels).
     precision: None = the plain kernels (bf16x3, or fp32 under set_nce_precision("fp32")), bit for bit
     what they always gave. "bf16x3" | "f16" (the grouped loss's modes, as ops.nce_precision() names them)
     = the fused grouped kernels where they apply (flags 0, and flags 9 without a bias, when A needs a
@@ -1761,15 +1764,42 @@ def profile_linear(x, profile, weight, bias, tok_user, seg):
     return _ProfileLinear.apply(_c(x), _c(profile), weight, bias, _c(tok_user), _c(seg))
 
 
+def gemm_x3_relu_train(a, b, bias, aux, p_drop=0.0, seed=0, tag=None):
+    """dropout_p(relu(a [M, K] @ b [N, K]^T + bias)) on rsx_gemm_x3_relu_train; writes the 0/1 mask
+    z > 0 into aux [M, N], the multiplier EPI_DGELU_DROP takes in the backward (same p_drop, seed)."""
+    a = _c(a)
+    b = _c(b)
+    M, K = a.shape
+    n = b.shape[0]
+    if tuple(aux.shape) != (M, n) or aux.dtype != torch.float32 or aux.stride(1) != 1:
+        raise ValueError(f"gemm_x3_relu_train: aux must be a float32 [{M}, {n}] tensor with unit column stride")
+    out = torch.empty(M, n, device=a.device, dtype=torch.float32)
+    if M == 0:
+        return out
+    nws = N.lib().rsx_gemm_x3_split_floats(M, n, K)
+    ws = torch.empty(nws, device=a.device, dtype=torch.float32) if nws > 0 else None
+    with timed(tag or "gemm_x3"):
+        rc = N.lib().rsx_gemm_x3_relu_train(N.ptr(a), a.stride(0), N.ptr(b), b.stride(0),
+                                            N.ptr(None if bias is None else _c(bias)), M, n, K, N.ptr(aux),
+                                            aux.stride(0), float(p_drop), int(seed), N.ptr(out), out.stride(0),
+                                            N.ptr(ws), nws, N.stream())
+    N.check(rc, "gemm_x3_relu_train")
+    return out
+
+
 class _FFN(torch.autograd.Function):
-    """linear2(dropout(gelu(linear1(h)))) with the GELU and the dropout in the GEMM epilogues
-    (rsx_gemm_x3 EPI_GELU_DROP forward, EPI_DGELU_DROP for the backward through them)."""
+    """linear2(dropout(act(linear1(h)))) with the activation and the dropout in the GEMM epilogues:
+    act "gelu": rsx_gemm_x3 EPI_GELU_DROP forward (aux = gelu'(pre)); act "relu":
+    rsx_gemm_x3_relu_train (aux = pre > 0). EPI_DGELU_DROP is the backward through either."""
 
     @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2, p_drop, seed):
+    def forward(ctx, h, w1, b1, w2, b2, p_drop, seed, act_name="gelu"):
         h = _c(h)
-        ggrad = torch.empty(h.shape[0], w1.shape[0], device=h.device, dtype=torch.float32)  # gelu'(pre)
-        act = gemm_x3(h, w1, b1, EPI_GELU_DROP, ggrad, p_drop, seed, tag="ffn_fwd1")
+        ggrad = torch.empty(h.shape[0], w1.shape[0], device=h.device, dtype=torch.float32)  # act'(pre)
+        if act_name == "relu":
+            act = gemm_x3_relu_train(h, w1, b1, ggrad, p_drop, seed, tag="ffn_relu_fwd1")
+        else:
+            act = gemm_x3(h, w1, b1, EPI_GELU_DROP, ggrad, p_drop, seed, tag="ffn_fwd1")
         f = gemm_x3(act, w2, b2, tag="ffn_fwd2")
         ctx.save_for_backward(h, w1, w2, ggrad, act)
         ctx.cfg = (p_drop, seed, b1 is not None, b2 is not None)
@@ -1791,15 +1821,16 @@ class _FFN(torch.autograd.Function):
         if need[1] or need[2]:
             dw1, db1 = linear_wgrad(dpre, h, w1.shape, has_b1 and need[2])
         dh = _dx(dpre, w1, tag="ffn_dh") if need[0] else None
-        return dh, dw1, db1, dw2, db2, None, None
+        return dh, dw1, db1, dw2, db2, None, None, None
 
 
 def ffn(h, w1, b1, w2, b2, p_drop=0.0, training=True, act="gelu"):
     """linear2(dropout(act(linear1(h)))) over a token axis (nn.TransformerEncoderLayer's
     feed-forward block). act="gelu": bf16x3 mode with GEMM-shaped widths: two fused GEMM launches
     forward, three plus two weight gradients backward; otherwise the unfused ops. act="relu" (the
-    layer's default activation): inference only on the fused path (rsx_gemm_x3's EPI_RELU, gradients
-    off and no dropout); with gradients enabled the unfused PyTorch form."""
+    layer's default activation): the same fused pair on rsx_gemm_x3_relu_train, with or without gradients;
+    with gradients off and no dropout rsx_gemm_x3's EPI_RELU, which saves nothing; shapes outside the
+    GEMMs take the unfused PyTorch form."""
     if act not in ("gelu", "relu"):
         raise ValueError(f"ffn: act must be 'gelu' or 'relu', got {act!r}")
     p = float(p_drop) if training else 0.0
@@ -1811,11 +1842,14 @@ def ffn(h, w1, b1, w2, b2, p_drop=0.0, training=True, act="gelu"):
         if shaped and p == 0.0 and not torch.is_grad_enabled():
             a = gemm_x3(h2, w1, b1, EPI_RELU, tag="ffn_relu_fwd1")
             return gemm_x3(a, w2, b2, tag="ffn_fwd2").reshape(*shp[:-1], w2.shape[0])
+        if shaped:
+            seed = next_seed() if p > 0 else 0
+            return _FFN.apply(h2, w1, b1, w2, b2, p, seed, "relu").reshape(*shp[:-1], w2.shape[0])
         F = torch.nn.functional
         return F.linear(F.dropout(F.relu(F.linear(h, w1, b1)), p, training), w2, b2)
     if shaped:
         seed = next_seed() if p > 0 else 0
-        f = _FFN.apply(h2, w1, b1, w2, b2, p, seed)
+        f = _FFN.apply(h2, w1, b1, w2, b2, p, seed, "gelu")
         return f.reshape(*shp[:-1], w2.shape[0])
     return linear_tok(torch.nn.functional.dropout(torch.nn.functional.gelu(linear_tok(h, w1, b1)), p, training),
                       w2, b2)
@@ -3164,8 +3198,14 @@ def _scatter_add_sorted(dst, src, idx):
     plan and rsx_segment_sum_rows: no atomics). dst [rows, D] contiguous, src [m, D] contiguous."""
     if idx.numel() == 0:
         return
+    _scatter_add_plan(dst, src, sort_segments(idx))
+
+
+def _scatter_add_plan(dst, src, plan):
+    """_scatter_add_sorted with the plan of ops.sort_segments(idx) given: one sort serves every table that is
+    indexed by the same ids."""
     D = dst.shape[1]
-    perm, cb, chunk_ids, ch_off, uniq = sort_segments(idx)
+    perm, cb, chunk_ids, ch_off, uniq = plan
     part = torch.empty(chunk_ids.numel(), D, device=dst.device, dtype=torch.float32)
     rc = N.lib().rsx_segment_sum_rows(N.ptr(src), D, N.ptr(perm), N.ptr(cb), N.ptr(chunk_ids), chunk_ids.numel(), D,
                                       None, -1, N.ptr(part), D, 0, N.stream())
@@ -3588,6 +3628,7 @@ HYBRID_GATE_HIDDEN = 64
 HYBRID_MAX_LEN = 64
 HYBRID_TIME_ROWS = 1001
 _HYBRID_IDS = IdRangeGuard("HybridUserTower ids (item ids, time deltas or token rows)")
+_LOGQ_IDS = IdRangeGuard("pos_item_ids of the tower's logQ losses (rows of item_probs / precomputed_log_q)")
 
 
 class AdapterParams:
@@ -3745,6 +3786,208 @@ def hybrid_fuse(seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, rows=None, l
     N.check(rc, fn)
     _HYBRID_IDS.watch(flag)
     return out, v, gate
+
+
+class _HybridAdapterTrain(torch.autograd.Function):
+    """The adapter with gradients (rsx_hybrid_adapter_train_fwd / rsx_hybrid_adapter_bwd). Saved for the
+    backward: the gathered rows (768 bytes per token) and the two pre-LayerNorm products (1,024): the
+    LayerNorm statistics, the GELUs and the keep masks are recomputed."""
+
+    @staticmethod
+    def forward(ctx, content, gnn, time_tab, ids, deltas, wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b, ln_eps, scale,
+                p_drop, seed_c, seed_g):
+        Dc, Dg, D = HYBRID_WIDTHS
+        dev, R = content.device, ids.numel()
+        new = lambda w: torch.empty(R, w, device=dev, dtype=torch.float32)  # noqa: E731
+        out, xc, xg, zc, zg = new(D), new(Dc), new(Dg), new(D), new(D)
+        seq = deltas is not None
+        params = tuple(_c(t.detach()) for t in (wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b))
+        if R > 0:
+            flag = torch.zeros(1, device=dev, dtype=torch.int32)
+            tab_c, tab_g = _hybrid_table("hybrid_adapter_train", "content", content, Dc), \
+                _hybrid_table("hybrid_adapter_train", "gnn", gnn, Dg)
+            with timed("hybrid/adapter_train"):
+                rc = N.lib().rsx_hybrid_adapter_train_fwd(
+                    N.ptr(tab_c), tab_c.stride(0), tab_c.shape[0], Dc, N.ptr(tab_g), tab_g.stride(0), tab_g.shape[0],
+                    Dg, N.ptr(ids), R, *(N.ptr(t) for t in params), float(ln_eps), N.ptr(deltas),
+                    N.ptr(None if time_tab is None else _c(time_tab.detach())), float(scale), float(p_drop),
+                    int(seed_c), int(seed_g), None if seq else N.ptr(out), N.ptr(out) if seq else None, N.ptr(xc),
+                    N.ptr(xg), N.ptr(zc), N.ptr(zg), N.ptr(flag), N.stream())
+            N.check(rc, "hybrid_adapter_train")
+            _HYBRID_IDS.watch(flag)
+        ctx.save_for_backward(ids, deltas, xc, xg, zc, zg, *params)
+        ctx.cfg = (float(ln_eps), float(scale) if seq else 1.0, float(p_drop), int(seed_c), int(seed_g),
+                   content.shape[0], gnn.shape[0], None if time_tab is None else time_tab.shape[0])
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        ids, deltas, xc, xg, zc, zg, wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b = ctx.saved_tensors
+        ln_eps, gscale, p_drop, seed_c, seed_g, n_c, n_g, n_t = ctx.cfg
+        Dc, Dg, D = HYBRID_WIDTHS
+        dev, R = dy.device, ids.numel()
+        need = ctx.needs_input_grad
+        dy = _c(dy.to(torch.float32))
+        new = lambda w: torch.empty(R, w, device=dev, dtype=torch.float32)  # noqa: E731
+        dzc, dzg, dc, dg = new(D), new(D), new(Dc), new(Dg)
+        dln = torch.empty(4, D, device=dev, dtype=torch.float32)
+        nws = N.lib().rsx_hybrid_adapter_bwd_workspace_floats(R)
+        ws = torch.empty(max(nws, 1), device=dev, dtype=torch.float32)
+        with timed("hybrid/adapter_bwd"):
+            rc = N.lib().rsx_hybrid_adapter_bwd(N.ptr(dy), gscale, R, N.ptr(zc), N.ptr(zg), N.ptr(wc), N.ptr(wg),
+                                                N.ptr(lnc_w), N.ptr(lnc_b), N.ptr(lng_w), N.ptr(lng_b), ln_eps, p_drop,
+                                                seed_c, seed_g, N.ptr(dzc), N.ptr(dzg), N.ptr(dc), N.ptr(dg),
+                                                N.ptr(dln), N.ptr(ws), nws, N.stream())
+        N.check(rc, "hybrid_adapter_bwd")
+        dwc = dbc = dwg = dbg = None
+        if need[5] or need[6]:
+            dwc, dbc = linear_wgrad(dzc, xc, (D, Dc), True, tag="hybrid/adapter_wgrad", precision="fp32")
+        if need[9] or need[10]:
+            dwg, dbg = linear_wgrad(dzg, xg, (D, Dg), True, tag="hybrid/adapter_wgrad", precision="fp32")
+        dcontent = dgnn = dtime = None
+        if (need[0] or need[1]) and R > 0:
+            plan = sort_segments(ids)   # one sort for both item tables
+            if need[0]:
+                dcontent = torch.zeros(n_c, Dc, device=dev, dtype=torch.float32)
+                _scatter_add_plan(dcontent, dc, plan)
+            if need[1]:
+                dgnn = torch.zeros(n_g, Dg, device=dev, dtype=torch.float32)
+                _scatter_add_plan(dgnn, dg, plan)
+        if need[2] and deltas is not None:
+            dtime = torch.zeros(n_t, D, device=dev, dtype=torch.float32)
+            _scatter_add_sorted(dtime, dy, deltas.clamp(0, HYBRID_TIME_ROWS - 1))   # the second sort
+        return (dcontent, dgnn, dtime, None, None, dwc, dbc, dln[0], dln[1], dwg, dbg, dln[2], dln[3], None, None,
+                None, None, None)
+
+
+def hybrid_adapter_train(content, gnn, time_tab, ids, deltas, params, ln_eps=1e-5, scale=1.0, p_drop=0.0,
+                         training=True):
+    """ParallelAdapter with gradients over gathered rows: m = (drop(gelu(LN(Wc c + bc))) + c) +
+    drop(gelu(LN(Wg g + bg))), c = content[ids], g = gnn[ids]. With deltas: seq_in = m scale +
+    time_tab[min(deltas, 1000)] [T, 128]; with deltas None (time_tab may be None): merged = m, the item side of
+    a loss. params: the eight adapter tensors (wc, bc, lnc_w, lnc_b, wg, bg, lng_w, lng_b) as they take
+    gradients. In training mode with p_drop > 0 the two dropout sites draw ops.next_seed(), content first;
+    otherwise no seed is drawn. Table gradients are dense; repeated ids are summed in a fixed order
+    (ops.sort_segments: a host synchronisation in the backward). Deterministic. An id outside the tables is
+    replaced by 0 before the forward (IdRangeGuard: IndexError at the next call or at
+    ops._HYBRID_IDS.check()); the forward and the backward both use the replaced ids, and the time rows are
+    min(max(delta, 0), 1000), so no gather or scatter leaves its table even if backward() runs before the
+    error is raised."""
+    fn = "hybrid_adapter_train"
+    Dc, Dg, D = HYBRID_WIDTHS
+    _f32(fn, "content", content)
+    _f32(fn, "gnn", gnn, content)
+    if _rows2(fn, "content", content) != Dc or _rows2(fn, "gnn", gnn) != Dg:
+        raise ValueError(f"{fn}: content must have {Dc} columns and gnn {Dg}")
+    if len(params) != 8:
+        raise ValueError(f"{fn}: params must be the adapter's eight tensors")
+    AdapterParams(*params, ln_eps=ln_eps).check(fn, content)
+    ids = _index(fn, "ids", ids, content).reshape(-1)
+    if deltas is not None:
+        if time_tab is None:
+            raise ValueError(f"{fn}: deltas need time_tab")
+        _time_table(fn, time_tab, content)
+        deltas = _c(_index(fn, "deltas", deltas, content, ids.numel())).reshape(-1)
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError(f"{fn}: p_drop must be in [0, 1)")
+    N.ensure_device(content)
+    # the ids as the kernels and the backward's scatter read them: an id outside the tables becomes 0 here
+    # (rsx_ids_check) and is reported by _HYBRID_IDS, so the table gradients' segment sums stay in bounds
+    if ids.numel() > 0:
+        ids = _HYBRID_IDS(ids, min(content.shape[0], gnn.shape[0]))
+    p = float(p_drop) if training else 0.0
+    seed_c = next_seed() if p > 0 else 0
+    seed_g = next_seed() if p > 0 else 0
+    return _HybridAdapterTrain.apply(content, gnn, time_tab if deltas is not None else None, ids, deltas, *params,
+                                     float(ln_eps), float(scale), p, seed_c, seed_g)
+
+
+class _HybridFuseTrain(torch.autograd.Function):
+    """The fusion with gradients (rsx_hybrid_fuse_train_fwd / rsx_hybrid_fuse_bwd). Nothing but the inputs
+    and v_seq (an output) is saved: the backward recomputes the forward per tile."""
+
+    @staticmethod
+    def forward(ctx, seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, ln_eps, eps, p_drop, seed_a, seed_b):
+        B, L, D = seq_out.shape
+        dev, n = seq_out.device, B * L
+        ts = tuple(_c(t.detach()) for t in (seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b))
+        out = torch.empty(B, L, D, device=dev, dtype=torch.float32)
+        v = torch.empty(B, L, D, device=dev, dtype=torch.float32)
+        gate = torch.zeros(2, device=dev, dtype=torch.float32)
+        if n > 0:
+            slots = N.lib().rsx_hybrid_fuse_slots(n)
+            ws = torch.empty(2 * slots, device=dev, dtype=torch.float64)
+            flag = torch.zeros(1, device=dev, dtype=torch.int32)
+            with timed("hybrid/fuse_train"):
+                rc = N.lib().rsx_hybrid_fuse_train_fwd(*(N.ptr(t) for t in ts[:1]), B, L, *(N.ptr(t) for t in ts[1:]),
+                                                       float(ln_eps), float(eps), float(p_drop), int(seed_a),
+                                                       int(seed_b), N.ptr(out), N.ptr(v), N.ptr(gate), N.ptr(ws),
+                                                       16 * slots, N.ptr(flag), N.stream())
+            N.check(rc, "hybrid_fuse_train")
+        ctx.save_for_backward(*ts, v)
+        ctx.cfg = (float(ln_eps), float(eps), float(p_drop), int(seed_a), int(seed_b))
+        ctx.mark_non_differentiable(gate)
+        return out, v, gate
+
+    @staticmethod
+    def backward(ctx, dout, dv, _dgate):
+        seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, v = ctx.saved_tensors
+        ln_eps, eps, p_drop, seed_a, seed_b = ctx.cfg
+        B, L, D = seq_out.shape
+        H = HYBRID_GATE_HIDDEN
+        dev, n = seq_out.device, B * L
+        need = ctx.needs_input_grad
+        dout = torch.zeros_like(seq_out) if dout is None else _c(dout.to(torch.float32))
+        dv = None if dv is None else _c(dv.to(torch.float32))
+        dx = torch.empty(B, L, D, device=dev, dtype=torch.float32)
+        dpre = torch.empty(n, H, device=dev, dtype=torch.float32)
+        dug = torch.zeros(B, D, device=dev, dtype=torch.float32)
+        dum = torch.zeros(B, D, device=dev, dtype=torch.float32)
+        dsmall = torch.empty(2 * D + 2 * H + 2, device=dev, dtype=torch.float32)
+        nws = N.lib().rsx_hybrid_fuse_bwd_workspace_floats(B, L)
+        ws = torch.empty(max(nws, 4), device=dev, dtype=torch.float32)
+        with timed("hybrid/fuse_bwd"):
+            rc = N.lib().rsx_hybrid_fuse_bwd(N.ptr(seq_out), B, L, N.ptr(u_gnn), N.ptr(u_meta), N.ptr(w1), N.ptr(b1),
+                                             N.ptr(w2), N.ptr(b2), N.ptr(ln_w), N.ptr(ln_b), ln_eps, eps, p_drop,
+                                             seed_a, seed_b, N.ptr(dout), N.ptr(dv), N.ptr(dx), N.ptr(dpre),
+                                             N.ptr(dug), N.ptr(dum), N.ptr(dsmall), N.ptr(ws), nws, N.stream())
+        N.check(rc, "hybrid_fuse_bwd")
+        dw1 = db1 = None
+        if need[3] or need[4]:
+            dw1, db1 = linear_wgrad(dpre, v.view(n, D), (H, D), True, tag="hybrid/fuse_wgrad", precision="fp32")
+        return (dx, dug, dum, dw1, db1, dsmall[2 * D:2 * D + 2 * H].view(2, H), dsmall[2 * D + 2 * H:], dsmall[:D],
+                dsmall[D:2 * D], None, None, None, None, None)
+
+
+def hybrid_fuse_train(seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, ln_eps=1e-5, eps=1e-12, p_drop=0.0,
+                      training=True):
+    """SequenceCentricFusion with gradients over all token rows (hybrid_fuse's arithmetic): returns (out
+    [B, L, 128], v_seq [B, L, 128], gate_mean [2]); out and v_seq are differentiable in seq_out, u_gnn, u_meta
+    and the six parameters, gate_mean (the means of the gates before dropout) is not. In training mode with
+    p_drop > 0 each token draws its own keep masks over its copies of u_gnn[u] and u_meta[u] (two
+    ops.next_seed() draws, the GNN row's first); otherwise no seed is drawn. Deterministic."""
+    fn = "hybrid_fuse_train"
+    D = HYBRID_WIDTHS[2]
+    _f32(fn, "seq_out", seq_out)
+    if seq_out.dim() != 3 or seq_out.shape[2] != D:
+        raise ValueError(f"{fn}: seq_out must be [B, L, {D}], got shape {tuple(seq_out.shape)}")
+    B, L = seq_out.shape[:2]
+    if not 1 <= L <= HYBRID_MAX_LEN:
+        raise ValueError(f"{fn}: L must be in [1, {HYBRID_MAX_LEN}], got {L}")
+    for name, t, shp in (("u_gnn", u_gnn, (B, D)), ("u_meta", u_meta, (B, D)), ("w1", w1, (HYBRID_GATE_HIDDEN, D)),
+                         ("b1", b1, (HYBRID_GATE_HIDDEN,)), ("w2", w2, (2, HYBRID_GATE_HIDDEN)), ("b2", b2, (2,)),
+                         ("ln_w", ln_w, (D,)), ("ln_b", ln_b, (D,))):
+        _f32(fn, name, t, seq_out)
+        if tuple(t.shape) != shp:
+            raise ValueError(f"{fn}: {name} has shape {tuple(t.shape)}, expected {shp}")
+    if not 0.0 <= float(p_drop) < 1.0:
+        raise ValueError(f"{fn}: p_drop must be in [0, 1)")
+    N.ensure_device(seq_out)
+    p = float(p_drop) if training else 0.0
+    seed_a = next_seed() if p > 0 else 0
+    seed_b = next_seed() if p > 0 else 0
+    return _HybridFuseTrain.apply(seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, float(ln_eps), float(eps), p,
+                                  seed_a, seed_b)
 
 
 # ----------------------------------------------------------------------------------------

@@ -52,8 +52,10 @@ DROPOUT = 0.3                   # the reference's module constant (:30)
 # HybridUserTower (:607-734) with its ParallelAdapter (:582-602) and SequenceCentricFusion (:514-577):
 # the model whose vectors are the sequence side of the evaluators below. In eval mode with gradients
 # off on the device it runs on csrc/hybrid.hip, the bf16x3 encoder stack (ReLU feed-forward) and
-# ops.linear / layer_norm / l2_normalize; in every other case (training, gradients, CPU, other widths,
-# L > 64) the plain PyTorch composition of the same modules runs. See DESIGN.md, section 4.
+# ops.linear / layer_norm / l2_normalize; with gradients or in training mode on the device it runs on
+# the training forms of the same kernels (ops.hybrid_adapter_train, encoder_stack, ops.hybrid_fuse_train)
+# unless native_training is False; in every other case (CPU, other widths, L > 64) the plain PyTorch
+# composition of the same modules runs. See DESIGN.md, section 4.
 def user_tower_collate_fn(batch):
     """The reference's collate (:180-189): sequences RIGHT-padded with 0 by pad_sequence, seq_mask =
     (seq_ids != 0), last_target = each sample's last target id (0 without targets)."""
@@ -111,6 +113,8 @@ class ParallelAdapter(nn.Module):
 class HybridUserTower(nn.Module):
     """Reference :607-734; construction order, sub-module names and state_dict as there."""
 
+    native_training = True   # False: calls with gradients / in training mode take the PyTorch composition
+
     def __init__(self, num_users, num_items, gnn_user_init, gnn_item_init, item_content_init):
         super().__init__()
         self.embed_dim = 128
@@ -147,8 +151,17 @@ class HybridUserTower(nn.Module):
     # -- dispatch ---------------------------------------------------------------------------
     def native_ok(self, seq_ids):
         """The device path: eval mode, gradients off, device tensors, the reference's widths, L <= 64."""
+        return not self.training and not torch.is_grad_enabled() and self._native_shapes(seq_ids)
+
+    def native_train_ok(self, seq_ids):
+        """The device path with gradients: as native_ok where that is false only because gradients are
+        on or the module is in training mode (and native_training is left True)."""
+        return (self.native_training and (self.training or torch.is_grad_enabled())
+                and self._native_shapes(seq_ids))
+
+    def _native_shapes(self, seq_ids):
         layer = self.seq_encoder.layers[0]
-        return (not self.training and not torch.is_grad_enabled() and seq_ids.is_cuda
+        return (seq_ids.is_cuda
                 and self.item_content_emb.weight.is_cuda and seq_ids.dim() == 2
                 and 1 <= seq_ids.shape[1] <= ops.HYBRID_MAX_LEN
                 and self.item_content_emb.weight.shape[1] == 128 and self.gnn_item_emb.weight.shape[1] == 64
@@ -244,9 +257,45 @@ class HybridUserTower(nn.Module):
         return ops.hybrid_fuse(seq_out, u_gnn, u_meta, g0.weight, g0.bias, g2.weight, g2.bias, fl.final_ln.weight,
                                fl.final_ln.bias, rows=rows, ln_eps=fl.final_ln.eps, want_v=want_v, want_gate=want_gate)
 
+    # -- the device path with gradients -----------------------------------------------------------
+    def _train_user_side(self, u_dense, u_cat):
+        """(U_gnn, U_meta) [B, 128] on the PyTorch modules (B rows; their gradient arrives through the
+        fusion's d u_gnn / d u_meta). The GNN user vector is zero (:672), so gnn_projector and gnn_user_emb
+        are not evaluated and get no gradient, and the Bernoulli user mask over zeros (:673-681) is not
+        drawn; U_gnn = LayerNorm(gnn_proj's bias) expanded, gnn_proj.0.weight sees a zero input."""
+        fl = self.fusion_layer
+        gp, mp = fl.gnn_proj, fl.meta_proj
+        B = u_dense.shape[0]
+        zero = torch.zeros(B, self.embed_dim, device=u_dense.device, dtype=torch.float32)
+        u_gnn = gp[1](gp[0](zero))
+        v_meta = F.normalize(self.meta_mlp(torch.cat([u_dense.to(torch.float32), self.channel_emb(u_cat)], dim=1)),
+                             p=2, dim=1)
+        return u_gnn, mp[1](mp[0](v_meta))
+
+    def _native_train_forward(self, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat):
+        B, L = seq_ids.shape
+        ad, fl = self.seq_adapter, self.fusion_layer
+        c, g = ad.content_proj, ad.gnn_proj
+        params = (c[0].weight, c[0].bias, c[1].weight, c[1].bias, g[0].weight, g[0].bias, g[1].weight, g[1].bias)
+        seq_in = ops.hybrid_adapter_train(self.item_content_emb.weight, self.gnn_item_emb.weight, self.time_emb.weight,
+                                          seq_ids, seq_deltas, params, ln_eps=c[1].eps,
+                                          scale=math.sqrt(self.embed_dim), p_drop=c[3].p, training=self.training)
+        seq_out = encoder_stack(self.seq_encoder.layers, seq_in.view(B, L, self.embed_dim), seq_mask == 0,
+                                DROPOUT if self.training else 0.0, self.training, causal=True, act="relu")
+        u_gnn, u_meta = self._train_user_side(u_dense, u_cat)
+        g0, g2 = fl.context_gate[0], fl.context_gate[2]
+        out, v, gate = ops.hybrid_fuse_train(seq_out, u_gnn, u_meta, g0.weight, g0.bias, g2.weight, g2.bias,
+                                             fl.final_ln.weight, fl.final_ln.bias, ln_eps=fl.final_ln.eps,
+                                             p_drop=fl.gnn_proj[2].p, training=self.training)
+        ratios = gate.tolist()        # the forward's one host read
+        ops._HYBRID_IDS.check()
+        return out, v, ratios
+
     def forward(self, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat):
         """(output [B, L, 128], v_seq [B, L, 128], [gnn_ratio, meta_ratio]); right-padded sequences."""
         if not self.native_ok(seq_ids):
+            if self.native_train_ok(seq_ids):
+                return self._native_train_forward(u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat)
             return self._torch_forward(u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat)
         B, L = seq_ids.shape
         seq_out = self._native_seq_out(seq_ids, seq_deltas, seq_mask)
@@ -288,6 +337,73 @@ def encode_users(model, u_idx, seq_ids, seq_deltas, seq_mask, u_dense, u_cat, me
         rows = torch.arange(B, device=last.device, dtype=torch.int64) * L + last
         out, _, _ = model._native_fuse(seq_out, u_gnn, u_meta, rows=rows, want_v=False, want_gate=False)
         return out
+
+
+# ----------------------------------------------------------------------------------------
+# The tower's two in-batch losses (:738-789). On 128-wide fp32 device rows they run on the fused
+# contrastive kernels (ops.nce_sum: no B x B logit matrix); anything else takes the PyTorch formula.
+def _nce_loss_ok(user_emb, item_emb, pos_item_ids, temperature):
+    return (user_emb.is_cuda and item_emb.is_cuda and pos_item_ids.is_cuda and user_emb.dim() == 2
+            and item_emb.dim() == 2 and user_emb.shape[1] == 128 and item_emb.shape == user_emb.shape
+            and user_emb.shape[0] > 0 and pos_item_ids.shape == (user_emb.shape[0],)
+            and user_emb.dtype == torch.float32 and item_emb.dtype == torch.float32
+            and not (torch.is_tensor(temperature) and temperature.requires_grad))
+
+
+def _collisions(pos_item_ids):
+    """[B, B] bool: another row with the same positive item (the diagonal is never a collision)."""
+    return (pos_item_ids.unsqueeze(1) == pos_item_ids.unsqueeze(0)).fill_diagonal_(False)
+
+
+def logq_correction_loss(user_emb, item_emb, pos_item_ids, item_probs, temperature=0.07, lambda_logq=0.0):
+    """Reference :738-749: cross-entropy over (U I^T - lambda log(item_probs[pos] + 1e-4)) / temperature with
+    the label on the diagonal and the other rows of the same positive item filled with -1e4. On the device:
+    ops.nce_sum flags 2 with bias_j = lambda log(item_probs[pos_j] + 1e-4) / temperature; the fill is
+    exclusion there (exp(-1e4 - max) is 0 in fp32 beside the diagonal). An id outside item_probs is
+    reported through ops._LOGQ_IDS (IndexError at the next call or at its check()), the read clamped."""
+    if not _nce_loss_ok(user_emb, item_emb, pos_item_ids, temperature):
+        scores = torch.matmul(user_emb, item_emb.T)
+        if lambda_logq > 0.0:
+            scores = scores - lambda_logq * torch.log(item_probs[pos_item_ids] + 1e-4).view(1, -1)
+        logits = (scores / temperature).masked_fill(_collisions(pos_item_ids), -1e4)
+        return F.cross_entropy(logits, torch.arange(logits.size(0), device=logits.device))
+    tau = float(temperature)
+    bias = None
+    if lambda_logq > 0.0:
+        ids = ops._LOGQ_IDS(pos_item_ids, item_probs.shape[0])
+        probs = item_probs.detach().to(device=user_emb.device, dtype=torch.float32)
+        bias = torch.log(probs[ids] + 1e-4) * (float(lambda_logq) / tau)
+    return ops.nce_loss(user_emb, item_emb, bias, k1a=pos_item_ids, k1b=pos_item_ids, tau=tau,
+                        flags=ops.NCE_MASK_ITEM, tag="logq_correction")
+
+
+def efficient_corrected_logq_loss(user_emb, item_emb, pos_item_ids, precomputed_log_q, temperature=0.1,
+                                  lambda_logq=0.1):
+    """Reference :751-789: cross-entropy over U I^T / temperature - lambda log_q[pos_j], the diagonal
+    restored to its uncorrected logit when lambda > 0, same-item rows off the diagonal filled with -1e9. On
+    the device: ops.nce_sum flags 18 (NCE_MASK_ITEM_POS) with bias_j = lambda log_q[pos_j], flags 2 without a
+    bias at lambda = 0. The reference's host assert on the ids is the device check of ops._LOGQ_IDS
+    (IndexError at the next call or at its check(); the read clamped); the PyTorch formula raises at once."""
+    n_q = precomputed_log_q.size(0)
+    if not _nce_loss_ok(user_emb, item_emb, pos_item_ids, temperature):
+        if pos_item_ids.numel() and not 0 <= int(pos_item_ids.min()) <= int(pos_item_ids.max()) < n_q:
+            raise IndexError(f"efficient_corrected_logq_loss: pos_item_ids outside [0, {n_q})")
+        logits = torch.matmul(user_emb, item_emb.T) / temperature
+        if lambda_logq > 0.0:
+            logits = logits - precomputed_log_q[pos_item_ids].view(1, -1) * lambda_logq
+            pos = torch.einsum("bd,bd->b", user_emb, item_emb) / temperature
+            eye = torch.eye(logits.size(0), dtype=torch.bool, device=logits.device)
+            logits = torch.where(eye, pos.view(-1, 1), logits)
+        mask_value = -30000.0 if logits.dtype == torch.float16 else -1e9
+        logits = logits.masked_fill(_collisions(pos_item_ids), mask_value)
+        return F.cross_entropy(logits, torch.arange(logits.size(0), device=logits.device))
+    ids = ops._LOGQ_IDS(pos_item_ids, n_q)
+    bias, flags = None, ops.NCE_MASK_ITEM
+    if lambda_logq > 0.0:
+        log_q = precomputed_log_q.detach().to(device=user_emb.device, dtype=torch.float32)
+        bias, flags = log_q[ids] * float(lambda_logq), ops.NCE_MASK_ITEM_POS
+    return ops.nce_loss(user_emb, item_emb, bias, k1a=pos_item_ids, k1b=pos_item_ids, tau=float(temperature),
+                        flags=flags, tag="efficient_logq")
 
 
 def alpha_grid(alpha_step):

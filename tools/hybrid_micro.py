@@ -10,7 +10,13 @@ alternating in one loop after warm-up, each call between HIP events. Three lines
   * forward        the module's full forward (per-token adapter, fusion of all B L rows, gate ratios read
                    on the host) against the PyTorch forward.
 Medians with min / max over the timed calls; "native_below_torch" tells whether the native range lies
-wholly below PyTorch's. Writes --out (profiles/hybrid_micro.json)."""
+wholly below PyTorch's. Writes --out (profiles/hybrid_micro.json).
+
+--train measures one more line instead, written to --train-out (profiles/hybrid_train_micro.json):
+  * forward_backward  the module in training mode (dropout 0.3 / 0.1 as the reference's modules), forward and
+                      the backward of sum(out * w) over the valid positions: the device training path
+                      (native_training = True) against the PyTorch composition (native_training = False), the
+                      same weights and inputs, alternating in one loop."""
 import argparse
 import json
 import os
@@ -52,8 +58,38 @@ def ab(native, plain, warmup, iters):
             "native_below_torch": max(ours) < min(theirs)}
 
 
+def train_line(model, args, warmup, iters):
+    """Forward + backward in training mode: native training path and PyTorch composition, alternating."""
+    model.train()
+    w = torch.randn(args[1].shape[0], args[1].shape[1], 128, device=args[1].device) * (args[3] != 0)[..., None]
+
+    def step(native):
+        model.native_training = native
+        model.zero_grad(set_to_none=True)
+        out, _, _ = model(*args)
+        (out * w).sum().backward()
+
+    ours, theirs = [], []
+    for i in range(warmup + iters):
+        t0, t1 = timed_ms(lambda: step(True)), timed_ms(lambda: step(False))
+        if i >= warmup:
+            ours.append(t0)
+            theirs.append(t1)
+    model.native_training = True
+    ops.timing_start()
+    for _ in range(5):
+        step(True)
+    phases = {k: v[1] / 5 for k, v in ops.timing_stop().items()}
+    model.eval()
+    return {"native": summary(ours), "torch": summary(theirs),
+            "speedup_over_torch": statistics.median(theirs) / statistics.median(ours),
+            "native_below_torch": max(ours) < min(theirs), "native_phase_ms": phases}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="measure the forward + backward line only")
+    ap.add_argument("--train-out", default=os.path.join("profiles", "hybrid_train_micro.json"))
     ap.add_argument("--items", type=int, default=105_000)
     ap.add_argument("--users", type=int, default=4096, help="users per batch (and rows of the user table)")
     ap.add_argument("--len", type=int, default=50)
@@ -81,6 +117,15 @@ def main():
     rows = torch.arange(B, device=dev)
     content, gnn = model.item_content_emb.weight, model.gnn_item_emb.weight
     result = {"items": a.items, "users": B, "len": L, "device": torch.cuda.get_device_name(0)}
+    if a.train:
+        result["p_drop"] = {"adapter": MI.DROPOUT, "encoder": MI.DROPOUT, "fusion": 0.1}
+        result["forward_backward"] = train_line(model, args, a.warmup, a.iters)
+        print(json.dumps({"forward_backward": result["forward_backward"]}), flush=True)
+        ops._HYBRID_IDS.check()
+        os.makedirs(os.path.dirname(a.train_out) or ".", exist_ok=True)
+        with open(a.train_out, "w") as fh:
+            json.dump(result, fh, indent=1, sort_keys=True)
+        return
 
     result["item_table"] = ab(lambda: MI.hybrid_item_vectors(model),
                               lambda: F.normalize(model.seq_adapter(content[1:], gnn[1:]), p=2, dim=1),
