@@ -1066,6 +1066,71 @@ int rsx_hybrid_fuse_bwd(const float* seq_out, int64_t B, int64_t L, const float*
                         const float* dout, const float* dv, float* dx, float* dpre, float* du_gnn, float* du_meta,
                         float* dsmall, float* ws, int64_t ws_floats, void* stream);
 
+/* ---- A17 oblivious-tree boosting: the rerank stage's classifier, csrc/gbdt.hip ------------------------
+ * The reference reranks with CatBoostClassifier(iterations=1000, learning_rate=0.05, depth=6, Logloss)
+ * over the FeatureEngineer columns (temp_model/ranker_skelet.py:95-149). CatBoost's GPU trainer is CUDA-only
+ * and its file format and ordered boosting are not reproduced: the model below is self-contained.
+ *   bins   uint8 [F, R], F <= 32 features, 1 <= R < 2^31 rows. A numeric column has at most 254 ascending
+ *          fp32 borders and bin = #{borders < x} (NaN: 0); a categorical column's bin is its code (0 = unknown).
+ *   F0     = log(p / (1 - p)) of the training base rate. Per tree: g = y - sigmoid(F), h = sigmoid(F)(1 -
+ *          sigmoid(F)) in fp32 (the sigmoid itself evaluated in fp64 and rounded once), quantised once to qg =
+ *          llrint(g 2^30), qh = llrint(h 2^30) (round half to even; both fit an int32). Every sum of g or h is
+ *          an exact int64 sum of these.
+ *   level d < depth <= 6: hist [2^d, F, 256, 2] int64 = the sums of (qg, qh) per (leaf, feature, bin). The
+ *          candidate (f, b), b < n_bins[f], sends bin > b right (numeric) or bin == b right (categorical) and
+ *          scores sum over the leaves in ascending order of G_L^2 / (H_L + l2) + G_R^2 / (H_R + l2) in fp64 with
+ *          G = (double)sum 2^-30. The level takes the argmax, ties to the lowest f, then the lowest b. No
+ *          validity rule: a candidate with an empty side scores the parent term (a real split may score
+ *          below it, each side paying l2; the level then leaves the leaves as they are). leaf = 2 leaf + right.
+ *   leaf values: (float)(lr (G / (H + l2))) in fp64 from the children's exact sums (an empty leaf: 0), then
+ *          F += value[leaf] in fp32. Prediction adds F0 and then the values in tree order in fp32, so it
+ *          equals the training approximant after the same number of trees bit for bit.
+ * Integer LDS and global atomics only: every output has the same bits every run. Nothing synchronises with
+ * the host; splits are read from device memory. flag (int32, OR-ed): bit 0 = a leaf index >= n_leaves
+ * (rsx_gbdt_histogram skips the row), bit 1 = a split feature >= F or a leaf index >= n_leaves
+ * (rsx_gbdt_apply_split uses feature 0 / the index masked); every access stays in bounds. */
+/* trees predict_k stages in LDS at a time; the row slabs rsx_gbdt_histogram cuts R rows of F features into */
+int64_t rsx_gbdt_tree_chunk(void);
+int64_t rsx_gbdt_histogram_slabs(int64_t R, int F);
+/* x [Fn, R] fp32 -> bins rows 0..Fn-1 of a [*, R] uint8 matrix; borders [Fn, 256] ascending, the first
+ * n_borders[j] <= 254 (int32, device) of row j valid. */
+int rsx_gbdt_bin(const float* x, const float* borders, const int* n_borders, int64_t R, int Fn, uint8_t* bins,
+                 void* stream);
+/* F, y [R] fp32 -> qg, qh [R] int32. */
+int rsx_gbdt_grad(const float* F, const float* y, int64_t R, int* qg, int* qh, void* stream);
+/* leaf uint8 [R] < n_leaves in {1, 2, 4, 8, 16, 32} -> hist [n_leaves, F, 256, 2] int64 (zeroed here). */
+int rsx_gbdt_histogram(const uint8_t* bins, const uint8_t* leaf, const int* qg, const int* qh, int64_t R, int F,
+                       int n_leaves, int64_t* hist, int* flag, void* stream);
+/* is_cat uint8 [F], n_bins int32 [F] (device), l2 > 0, ws 16 F bytes (16-byte aligned) -> split int32 [2] =
+ * (f, b) and, when score is not NULL, the winning score. */
+int rsx_gbdt_best_split(const int64_t* hist, const uint8_t* is_cat, const int* n_bins, int F, int n_leaves, double l2,
+                        void* ws, int* split, double* score, void* stream);
+/* leaf = 2 leaf + right in place. hist not NULL marks the last level (hist = that level's histogram): then
+ * leaf_sums int64 [2 n_leaves, 2] and leaf_values fp32 [2 n_leaves] are written and Fx [R] += value[leaf]. */
+int rsx_gbdt_apply_split(const uint8_t* bins, int64_t R, int F, const int* split, const uint8_t* is_cat, int n_leaves,
+                         uint8_t* leaf, const int64_t* hist, double lr, double l2, int64_t* leaf_sums,
+                         float* leaf_values, float* Fx, int* flag, void* stream);
+/* One whole tree on Fx [R] (the stages above enqueued back to back: 2 + 4 depth kernels and 1 + depth fills): qg, qh
+ * int32 [R], leaf uint8 [R], hist int64 [2^(depth-1) F 512] and ws (16 F bytes) are scratch; splits int32
+ * [depth, 2], leaf_sums int64 [2^depth, 2] and leaf_values fp32 [2^depth] are the tree. */
+int rsx_gbdt_tree(const uint8_t* bins, const float* y, int64_t R, int F, const uint8_t* is_cat, const int* n_bins,
+                  int depth, double lr, double l2, float* Fx, int* qg, int* qh, uint8_t* leaf, int64_t* hist, void* ws,
+                  int* splits, int64_t* leaf_sums, float* leaf_values, int* flag, void* stream);
+/* out [R] = (init ? init : f0) + the leaf values of the trees [tree_begin, tree_end) in order; splits int32
+ * [T, 6, 2] (the first depth levels used) and leaf_values fp32 [T, 64]; out may be init. One row per lane. */
+int rsx_gbdt_predict(const uint8_t* bins, int64_t R, int F, const int* splits, const float* leaf_values,
+                     const uint8_t* is_cat, int depth, int tree_begin, int tree_end, const float* init, float f0,
+                     float* out, void* stream);
+/* The FeatureEngineer numeric columns (temp_model/ranker_skelet.py:29-68) of the candidates cand [Q, K]
+ * (int64 item ids < N) with their retrieval scores score [Q, K]: U [Q, d] user vectors, V [N, d] item vectors,
+ * item_price [N], user_avg_price [Q] -> feats fp32 [7, Q K] = two_tower_score; the mean, the maximum and the
+ * population standard deviation of u * v; item_price; user_avg_price; price_diff_ratio = (price - avg) / avg
+ * where avg > 0, else 0. ids int64 [Q K] = the candidates with an id outside [0, N) replaced by 0, which sets
+ * flag bit 0. One wave per candidate. */
+int rsx_rerank_tabular(const int64_t* cand, const float* score, const float* U, const float* V, const float* item_price,
+                       const float* user_avg_price, int64_t Q, int64_t K, int64_t N, int64_t d, float* feats,
+                       int64_t* ids, int* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 15 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 16 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -212,6 +212,17 @@ _SIGS = {
     "rsx_hybrid_fuse_bwd_workspace_floats": (c_i64, [c_i64, c_i64]),
     "rsx_hybrid_fuse_bwd": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_f, c_f, c_u64,
                                   c_u64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p]),
+    "rsx_gbdt_tree_chunk": (c_i64, []),
+    "rsx_gbdt_histogram_slabs": (c_i64, [c_i64, c_i]),
+    "rsx_gbdt_bin": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p, c_p]),
+    "rsx_gbdt_grad": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_gbdt_histogram": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_p, c_p]),
+    "rsx_gbdt_best_split": (c_i, [c_p, c_p, c_p, c_i, c_i, c_d, c_p, c_p, c_p, c_p]),
+    "rsx_gbdt_apply_split": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_i, c_p, c_p, c_d, c_d, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_gbdt_tree": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                            c_p, c_p]),
+    "rsx_gbdt_predict": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
+    "rsx_rerank_tabular": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -3991,6 +3991,311 @@ def hybrid_fuse_train(seq_out, u_gnn, u_meta, w1, b1, w2, b2, ln_w, ln_b, ln_eps
 
 
 # ----------------------------------------------------------------------------------------
+# A17 oblivious-tree boosting, the rerank stage's classifier (csrc/gbdt.hip; the model:
+# include/recsys_amd.h, "oblivious-tree boosting")
+GBDT_MAX_FEATURES = 32
+GBDT_BINS = 256
+GBDT_MAX_BORDERS = 254
+GBDT_MAX_DEPTH = 6
+GBDT_LEAF_STRIDE = 64
+GBDT_SCALE = float(2 ** 30)     # qg = llrint(g * GBDT_SCALE)
+RERANK_TABULAR_COLUMNS = ("two_tower_score", "vec_prod_mean", "vec_prod_max", "vec_prod_std", "item_price",
+                          "user_avg_price", "price_diff_ratio")
+
+
+class GBDTModel:
+    """The trees gbdt_predict reads, all on one device: splits int32 [T, 6, 2] = (feature, bin) per level
+    (the first `depth` levels used), leaf_values fp32 [T, 64], is_cat uint8 [F], f0 (host float, exactly
+    an fp32 value) and n_trees <= T, the trees in use."""
+
+    def __init__(self, splits, leaf_values, is_cat, depth, f0, n_trees):
+        self.splits, self.leaf_values, self.is_cat = splits, leaf_values, is_cat
+        self.depth, self.f0, self.n_trees = int(depth), float(f0), int(n_trees)
+
+
+def _gbdt_rows(fn, name, t, dtype, R, ref):
+    """t is a contiguous dtype vector of R elements on ref's device."""
+    if t.dtype != dtype:
+        raise TypeError(f"{fn}: {name} must be {dtype}, got {t.dtype}")
+    if t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+    if t.dim() != 1 or t.numel() != R or not t.is_contiguous():
+        raise ValueError(f"{fn}: {name} must be a contiguous vector of {R} elements, got shape {tuple(t.shape)}")
+
+
+def _gbdt_bins(fn, bins):
+    """bins is a contiguous uint8 [F, R] device matrix, F <= 32, 1 <= R < 2^31; returns (F, R)."""
+    N.ensure_device(bins)
+    if bins.dtype != torch.uint8:
+        raise TypeError(f"{fn}: bins must be uint8, got {bins.dtype}")
+    if bins.dim() != 2 or not bins.is_contiguous():
+        raise ValueError(f"{fn}: bins must be a contiguous [F, R] matrix, got shape {tuple(bins.shape)}")
+    F, R = bins.shape
+    if not (1 <= F <= GBDT_MAX_FEATURES and 1 <= R < 2 ** 31):
+        raise ValueError(f"{fn}: need 1 <= F <= {GBDT_MAX_FEATURES} and 1 <= R < 2^31 (got F {F}, R {R})")
+    return F, R
+
+
+def _gbdt_leaves(fn, n_leaves):
+    if n_leaves not in (1, 2, 4, 8, 16, 32):
+        raise ValueError(f"{fn}: n_leaves must be 1, 2, 4, 8, 16 or 32 (got {n_leaves!r})")
+
+
+_GBDT_GUARD = IdRangeGuard("gbdt: a leaf index or a split feature")
+_RERANK_GUARD = IdRangeGuard("rerank_tabular candidate ids")
+
+
+def gbdt_bin(x, borders, n_borders, out=None):
+    """Numeric columns x [Fn, R] (fp32, device) -> their bins uint8 [Fn, R]: bin = #{borders < x}, NaN -> 0
+    (rsx_gbdt_bin). borders [Fn, 256] fp32 ascending, the first n_borders[j] <= 254 (int32 [Fn], device) of
+    row j valid. out: a contiguous uint8 [F >= Fn, R] matrix whose first Fn rows are written instead."""
+    N.ensure_device(x)
+    _f32("gbdt_bin", "x", x)
+    if x.dim() != 2 or not x.is_contiguous():
+        raise ValueError(f"gbdt_bin: x must be a contiguous [Fn, R] matrix, got shape {tuple(x.shape)}")
+    Fn, R = x.shape
+    if not (1 <= Fn <= GBDT_MAX_FEATURES and 1 <= R < 2 ** 31):
+        raise ValueError(f"gbdt_bin: need 1 <= Fn <= {GBDT_MAX_FEATURES} and 1 <= R < 2^31 (got {Fn}, {R})")
+    _f32("gbdt_bin", "borders", borders, x)
+    if tuple(borders.shape) != (Fn, GBDT_BINS) or not borders.is_contiguous():
+        raise ValueError(f"gbdt_bin: borders must be a contiguous [{Fn}, {GBDT_BINS}] matrix, got {tuple(borders.shape)}")
+    _gbdt_rows("gbdt_bin", "n_borders", n_borders, torch.int32, Fn, x)
+    if out is None:
+        out = torch.empty(Fn, R, device=x.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] < Fn or out.shape[1] != R or not out.is_contiguous() \
+            or out.device != x.device:
+        raise ValueError(f"gbdt_bin: out must be a contiguous uint8 [>= {Fn}, {R}] matrix on {x.device}")
+    with timed("gbdt/bin"):
+        N.check(N.lib().rsx_gbdt_bin(N.ptr(x), N.ptr(borders), N.ptr(n_borders), R, Fn, N.ptr(out), N.stream()), "gbdt_bin")
+    return out
+
+
+def gbdt_grad(F, y, out=None):
+    """(qg, qh) int32 [R] of the approximant F [R] and the labels y [R] (both fp32, device): g = y -
+    sigmoid(F) and h = sigmoid(F)(1 - sigmoid(F)) in fp32, each quantised to llrint(x 2^30) (rsx_gbdt_grad).
+    out: a (qg, qh) pair to write."""
+    N.ensure_device(F)
+    _f32("gbdt_grad", "F", F)
+    R = F.numel()
+    if R < 1 or R >= 2 ** 31:
+        raise ValueError(f"gbdt_grad: need 1 <= R < 2^31 rows (got {R})")
+    _gbdt_rows("gbdt_grad", "F", F, torch.float32, R, F)
+    _gbdt_rows("gbdt_grad", "y", y, torch.float32, R, F)
+    qg, qh = out if out is not None else (torch.empty(R, device=F.device, dtype=torch.int32) for _ in range(2))
+    _gbdt_rows("gbdt_grad", "qg", qg, torch.int32, R, F)
+    _gbdt_rows("gbdt_grad", "qh", qh, torch.int32, R, F)
+    with timed("gbdt/grad"):
+        N.check(N.lib().rsx_gbdt_grad(N.ptr(F), N.ptr(y), R, N.ptr(qg), N.ptr(qh), N.stream()), "gbdt_grad")
+    return qg, qh
+
+
+def gbdt_histogram(bins, leaf, qg, qh, n_leaves, out=None):
+    """hist int64 [n_leaves, F, 256, 2]: the exact sums of (qg, qh) (int32 [R]) over the rows of every
+    (leaf, feature, bin); bins uint8 [F, R], leaf uint8 [R] < n_leaves in {1, 2, 4, 8, 16, 32}
+    (rsx_gbdt_histogram: LDS and global integer atomics, the same bits every run). A leaf index out of
+    range is skipped and raises IndexError at a later call."""
+    F, R = _gbdt_bins("gbdt_histogram", bins)
+    _gbdt_leaves("gbdt_histogram", n_leaves)
+    _gbdt_rows("gbdt_histogram", "leaf", leaf, torch.uint8, R, bins)
+    _gbdt_rows("gbdt_histogram", "qg", qg, torch.int32, R, bins)
+    _gbdt_rows("gbdt_histogram", "qh", qh, torch.int32, R, bins)
+    shape = (n_leaves, F, GBDT_BINS, 2)
+    if out is None:
+        out = torch.empty(shape, device=bins.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != bins.device:
+        raise ValueError(f"gbdt_histogram: out must be a contiguous int64 {shape} tensor on {bins.device}")
+    flag = torch.zeros(1, device=bins.device, dtype=torch.int32)
+    with timed("gbdt/histogram"):
+        N.check(N.lib().rsx_gbdt_histogram(N.ptr(bins), N.ptr(leaf), N.ptr(qg), N.ptr(qh), R, F, n_leaves, N.ptr(out),
+                                           N.ptr(flag), N.stream()), "gbdt_histogram")
+    _GBDT_GUARD.watch(flag)
+    return out
+
+
+def _gbdt_features(fn, is_cat, n_bins, F, ref):
+    _gbdt_rows(fn, "is_cat", is_cat, torch.uint8, F, ref)
+    if n_bins is not None:
+        _gbdt_rows(fn, "n_bins", n_bins, torch.int32, F, ref)
+
+
+def _gbdt_l2(fn, l2):
+    if not float(l2) > 0.0:
+        raise ValueError(f"{fn}: l2 must be positive (got {l2!r})")
+
+
+def gbdt_best_split(hist, is_cat, n_bins, l2, out=None):
+    """The best candidate of a level: (split int32 [2] = (f, b), score float64 [1]), on the device. hist
+    int64 [n_leaves, F, 256, 2]; is_cat uint8 [F]; n_bins int32 [F]: the candidates of feature f are b <
+    n_bins[f]; a numeric one sends bin > b right, a categorical one bin == b; the score is the sum over the
+    leaves of G_L^2 / (H_L + l2) + G_R^2 / (H_R + l2) in fp64; ties go to the lowest f, then the lowest b
+    (rsx_gbdt_best_split). out: the int32 [2] tensor to write the split to."""
+    N.ensure_device(hist)
+    if hist.dtype != torch.int64 or hist.dim() != 4 or tuple(hist.shape[2:]) != (GBDT_BINS, 2) or not hist.is_contiguous():
+        raise ValueError(f"gbdt_best_split: hist must be a contiguous int64 [n_leaves, F, {GBDT_BINS}, 2] tensor")
+    n_leaves, F = hist.shape[:2]
+    _gbdt_leaves("gbdt_best_split", n_leaves)
+    if not 1 <= F <= GBDT_MAX_FEATURES:
+        raise ValueError(f"gbdt_best_split: need 1 <= F <= {GBDT_MAX_FEATURES} (got {F})")
+    _gbdt_features("gbdt_best_split", is_cat, n_bins, F, hist)
+    _gbdt_l2("gbdt_best_split", l2)
+    split = out if out is not None else torch.empty(2, device=hist.device, dtype=torch.int32)
+    _gbdt_rows("gbdt_best_split", "out", split, torch.int32, 2, hist)
+    score = torch.empty(1, device=hist.device, dtype=torch.float64)
+    ws = torch.empty(16 * F, device=hist.device, dtype=torch.uint8)
+    with timed("gbdt/best_split"):
+        N.check(N.lib().rsx_gbdt_best_split(N.ptr(hist), N.ptr(is_cat), N.ptr(n_bins), F, n_leaves, float(l2), N.ptr(ws),
+                                            N.ptr(split), N.ptr(score), N.stream()), "gbdt_best_split")
+    return split, score
+
+
+def gbdt_apply_split(bins, leaf, split, is_cat, n_leaves, hist=None, F=None, lr=None, l2=None):
+    """leaf = 2 leaf + right in place for the device split (f, b) (int32 [2]) of a level with n_leaves leaves
+    (rsx_gbdt_apply_split). With hist (that level's histogram) the level is the tree's last: returns
+    (leaf_sums int64 [2 n_leaves, 2], leaf_values fp32 [2 n_leaves]) with value = (float)(lr (G / (H +
+    l2))) from the children's exact sums (an empty leaf: 0) and adds value[leaf] to the approximant F [R] in
+    place; else returns None. A split feature or leaf index out of range raises IndexError at a later call."""
+    nF, R = _gbdt_bins("gbdt_apply_split", bins)
+    _gbdt_leaves("gbdt_apply_split", n_leaves)
+    _gbdt_rows("gbdt_apply_split", "leaf", leaf, torch.uint8, R, bins)
+    _gbdt_rows("gbdt_apply_split", "split", split, torch.int32, 2, bins)
+    _gbdt_features("gbdt_apply_split", is_cat, None, nF, bins)
+    sums = values = None
+    if hist is not None:
+        shape = (n_leaves, nF, GBDT_BINS, 2)
+        if hist.dtype != torch.int64 or tuple(hist.shape) != shape or not hist.is_contiguous() or hist.device != bins.device:
+            raise ValueError(f"gbdt_apply_split: hist must be a contiguous int64 {shape} tensor on {bins.device}")
+        if F is None or lr is None or l2 is None:
+            raise ValueError("gbdt_apply_split: the last level (hist given) needs F, lr and l2")
+        _gbdt_rows("gbdt_apply_split", "F", F, torch.float32, R, bins)
+        _gbdt_l2("gbdt_apply_split", l2)
+        sums = torch.empty(2 * n_leaves, 2, device=bins.device, dtype=torch.int64)
+        values = torch.empty(2 * n_leaves, device=bins.device, dtype=torch.float32)
+    flag = torch.zeros(1, device=bins.device, dtype=torch.int32)
+    with timed("gbdt/apply_split"):
+        N.check(N.lib().rsx_gbdt_apply_split(N.ptr(bins), R, nF, N.ptr(split), N.ptr(is_cat), n_leaves, N.ptr(leaf),
+                                             N.ptr(hist), float(lr or 0.0), float(l2 or 0.0), N.ptr(sums), N.ptr(values),
+                                             N.ptr(F) if hist is not None else None, N.ptr(flag), N.stream()),
+                "gbdt_apply_split")
+    _GBDT_GUARD.watch(flag)
+    return None if hist is None else (sums, values)
+
+
+class GBDTScratch:
+    """The buffers gbdt_tree reuses from tree to tree (R rows, F features, one device)."""
+
+    def __init__(self, R, F, depth, device):
+        self.qg = torch.empty(R, device=device, dtype=torch.int32)
+        self.qh = torch.empty(R, device=device, dtype=torch.int32)
+        self.leaf = torch.empty(R, device=device, dtype=torch.uint8)
+        self.hist = torch.empty(1 << (depth - 1), F, GBDT_BINS, 2, device=device, dtype=torch.int64)
+        self.ws = torch.empty(16 * F, device=device, dtype=torch.uint8)
+        self.sums = torch.empty(GBDT_LEAF_STRIDE, 2, device=device, dtype=torch.int64)
+        self.flag = torch.zeros(1, device=device, dtype=torch.int32)
+        self.key = (R, F, depth, torch.device(device))
+
+
+def gbdt_tree(bins, y, Fx, is_cat, n_bins, depth, lr, l2, splits, leaf_values, scratch):
+    """One whole tree on the approximant Fx [R] (updated in place), enqueued by one native call
+    (rsx_gbdt_tree: gradients, then per level histogram, split search and leaf update, the last level with the
+    leaf values and the update of Fx; 2 + 4 depth kernels and 1 + depth fills, no host synchronisation).
+    Writes splits int32 [>= depth, 2] and leaf_values fp32 [>= 2^depth] (a tree's rows of a GBDTModel).
+    scratch: a GBDTScratch(R, F, depth, device); its flag collects range errors (the caller watches it)."""
+    F, R = _gbdt_bins("gbdt_tree", bins)
+    if not 1 <= depth <= GBDT_MAX_DEPTH:
+        raise ValueError(f"gbdt_tree: need 1 <= depth <= {GBDT_MAX_DEPTH} (got {depth})")
+    _gbdt_rows("gbdt_tree", "y", y, torch.float32, R, bins)
+    _gbdt_rows("gbdt_tree", "F", Fx, torch.float32, R, bins)
+    _gbdt_features("gbdt_tree", is_cat, n_bins, F, bins)
+    _gbdt_l2("gbdt_tree", l2)
+    if scratch.key != (R, F, depth, bins.device):
+        raise ValueError(f"gbdt_tree: the scratch was sized for {scratch.key}, not {(R, F, depth, bins.device)}")
+    if splits.dtype != torch.int32 or splits.numel() < 2 * depth or not splits.is_contiguous() or splits.device != bins.device:
+        raise ValueError(f"gbdt_tree: splits must be a contiguous int32 [>= {depth}, 2] tensor on {bins.device}")
+    if (leaf_values.dtype != torch.float32 or leaf_values.numel() < (1 << depth) or not leaf_values.is_contiguous()
+            or leaf_values.device != bins.device):
+        raise ValueError(f"gbdt_tree: leaf_values must be a contiguous fp32 [>= {1 << depth}] tensor on {bins.device}")
+    s = scratch
+    with timed("gbdt/tree"):
+        N.check(N.lib().rsx_gbdt_tree(N.ptr(bins), N.ptr(y), R, F, N.ptr(is_cat), N.ptr(n_bins), int(depth), float(lr),
+                                      float(l2), N.ptr(Fx), N.ptr(s.qg), N.ptr(s.qh), N.ptr(s.leaf), N.ptr(s.hist),
+                                      N.ptr(s.ws), N.ptr(splits), N.ptr(s.sums), N.ptr(leaf_values), N.ptr(s.flag),
+                                      N.stream()), "gbdt_tree")
+
+
+def gbdt_predict(bins, model, ntree_end=None, ntree_begin=0, init=None, out=None):
+    """The raw scores [R] (fp32) of the binned rows bins uint8 [F, R] under a GBDTModel: f0 (or init [R], for
+    a running sum) plus the leaf values of the trees [ntree_begin, ntree_end) in tree order, added in fp32
+    one row per lane (rsx_gbdt_predict), so the result equals the training approximant after the same
+    trees bit for bit. ntree_end None: model.n_trees. out may be init."""
+    F, R = _gbdt_bins("gbdt_predict", bins)
+    end = model.n_trees if ntree_end is None else int(ntree_end)
+    begin = int(ntree_begin)
+    T = model.splits.shape[0]
+    if not 0 <= begin <= end <= T:
+        raise ValueError(f"gbdt_predict: need 0 <= ntree_begin <= ntree_end <= {T} (got {begin}, {end})")
+    if not 1 <= model.depth <= GBDT_MAX_DEPTH:
+        raise ValueError(f"gbdt_predict: need 1 <= depth <= {GBDT_MAX_DEPTH} (got {model.depth})")
+    sp, lv = model.splits, model.leaf_values
+    if sp.dtype != torch.int32 or tuple(sp.shape[1:]) != (GBDT_MAX_DEPTH, 2) or not sp.is_contiguous() or sp.device != bins.device:
+        raise ValueError(f"gbdt_predict: model.splits must be a contiguous int32 [T, {GBDT_MAX_DEPTH}, 2] tensor on {bins.device}")
+    if lv.dtype != torch.float32 or tuple(lv.shape) != (T, GBDT_LEAF_STRIDE) or not lv.is_contiguous() or lv.device != bins.device:
+        raise ValueError(f"gbdt_predict: model.leaf_values must be a contiguous fp32 [{T}, {GBDT_LEAF_STRIDE}] tensor on "
+                         f"{bins.device}")
+    _gbdt_features("gbdt_predict", model.is_cat, None, F, bins)
+    if init is not None:
+        _gbdt_rows("gbdt_predict", "init", init, torch.float32, R, bins)
+    if out is None:
+        out = torch.empty(R, device=bins.device, dtype=torch.float32)
+    else:
+        _gbdt_rows("gbdt_predict", "out", out, torch.float32, R, bins)
+    with timed("gbdt/predict"):
+        N.check(N.lib().rsx_gbdt_predict(N.ptr(bins), R, F, N.ptr(sp), N.ptr(lv), N.ptr(model.is_cat), model.depth, begin,
+                                         end, N.ptr(init), model.f0, N.ptr(out), N.stream()), "gbdt_predict")
+    return out
+
+
+def rerank_tabular(cand_ids, cand_scores, user_vectors, item_vectors, item_price, user_avg_price):
+    """The FeatureEngineer numeric columns of the candidates cand_ids [Q, K] (item ids) with their retrieval
+    scores cand_scores [Q, K]: (feats fp32 [7, Q K] in the order RERANK_TABULAR_COLUMNS, ids int64 [Q K]) on
+    rsx_rerank_tabular, one wave per candidate. user_vectors [Q, d], item_vectors [N, d], item_price [N],
+    user_avg_price [Q], all fp32 on the device. vec_prod_std is the population standard deviation (np.std);
+    price_diff_ratio is 0 where user_avg_price is not positive. An id outside [0, N) reads item 0 (ids holds
+    the ids used) and raises IndexError at a later call."""
+    N.ensure_device(cand_ids)
+    if cand_ids.dim() != 2:
+        raise ValueError(f"rerank_tabular: cand_ids must be [Q, K], got shape {tuple(cand_ids.shape)}")
+    Q, K = cand_ids.shape
+    if Q < 1 or K < 1 or Q * K >= 2 ** 31:
+        raise ValueError(f"rerank_tabular: need Q, K >= 1 and Q K < 2^31 (got {Q}, {K})")
+    cand = _c(_index("rerank_tabular", "cand_ids", cand_ids))
+    _f32("rerank_tabular", "cand_scores", cand_scores, cand)
+    if cand_scores.shape != cand_ids.shape:
+        raise ValueError(f"rerank_tabular: cand_scores has shape {tuple(cand_scores.shape)}, cand_ids {tuple(cand_ids.shape)}")
+    d = _rows2("rerank_tabular", "user_vectors", user_vectors)
+    if _rows2("rerank_tabular", "item_vectors", item_vectors) != d or user_vectors.shape[0] != Q:
+        raise ValueError(f"rerank_tabular: need user_vectors [{Q}, d] and item_vectors [N, d] (got "
+                         f"{tuple(user_vectors.shape)} and {tuple(item_vectors.shape)})")
+    n_items = item_vectors.shape[0]
+    if n_items < 1 or d < 1:
+        raise ValueError("rerank_tabular: item_vectors is empty")
+    for name, t in (("user_vectors", user_vectors), ("item_vectors", item_vectors)):
+        if t.device != cand.device:
+            raise RuntimeError(f"rerank_tabular: {name} is on {t.device}, expected {cand.device}")
+    _f32_vec("rerank_tabular", "item_price", item_price, n_items, cand)
+    _f32_vec("rerank_tabular", "user_avg_price", user_avg_price, Q, cand)
+    R = Q * K
+    feats = torch.empty(len(RERANK_TABULAR_COLUMNS), R, device=cand.device, dtype=torch.float32)
+    ids = torch.empty(R, device=cand.device, dtype=torch.int64)
+    flag = torch.zeros(1, device=cand.device, dtype=torch.int32)
+    with timed("gbdt/rerank_tabular"):
+        N.check(N.lib().rsx_rerank_tabular(N.ptr(cand), N.ptr(_c(cand_scores)), N.ptr(_c(user_vectors)),
+                                           N.ptr(_c(item_vectors)), N.ptr(_c(item_price)), N.ptr(_c(user_avg_price)), Q, K,
+                                           n_items, d, N.ptr(feats), N.ptr(ids), N.ptr(flag), N.stream()), "rerank_tabular")
+    _RERANK_GUARD.watch(flag, n_items)
+    return feats, ids
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 

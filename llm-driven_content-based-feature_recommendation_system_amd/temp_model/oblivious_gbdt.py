@@ -1,0 +1,339 @@
+"""Oblivious-tree gradient boosting on the device: the classifier behind the reference's rerank stage.
+
+Reference: RecommendationRanker (temp_model/ranker_skelet.py:95-149) boosts 1000 symmetric trees of depth 6
+with CatBoostClassifier (learning_rate 0.05, Logloss, eval_metric AUC, early_stopping_rounds 50,
+use_best_model) over the FeatureEngineer columns. CatBoost's GPU trainer is CUDA-only, so on an MI355X
+`ObliviousBoostingClassifier` takes its place behind the same calls (fit with eval_set, predict_proba,
+save_model / load_model, best_iteration_, evals_result_). It is a model of its own, specified in
+include/recsys_amd.h ("oblivious-tree boosting") and restated by tests/gbdt_ref.py: plain (not ordered)
+boosting, quantile-free borders at the midpoints of the distinct values, categorical columns as one-hot
+candidates over host-built codes (no target statistics), no feature combinations. Parity with CatBoost's
+own trees is not claimed.
+
+Compute: ops.gbdt_bin (borders -> bins), ops.gbdt_tree (one native call per tree: rsx_gbdt_grad,
+rsx_gbdt_histogram, rsx_gbdt_best_split, rsx_gbdt_apply_split), ops.gbdt_predict; the metrics on
+ops.binary_eval / ops.group_eval. Every sum is an integer sum, so two fits of the same data give the same
+model bit for bit.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from .. import ops
+from .ranker_skelet import _fit_args, _fit_eval_groups, _fit_eval_labels, _parse_eval_metric
+
+_MAX_CODES = 255     # known values of a categorical column: codes 1..255, 0 = unknown / unseen
+
+
+def build_borders(x, border_count=ops.GBDT_MAX_BORDERS):
+    """The borders of the numeric columns x [Fn, R] (fp32, any device; no host read): (borders fp32
+    [Fn, 256] ascending and padded with +inf, n_borders int32 [Fn]). A column's borders are the midpoints
+    a/2 + b/2 of its consecutive distinct non-NaN values; with more than border_count midpoints, those at
+    the ranks ((2 j + 1) (m - 1)) // (2 border_count), j < border_count, of the m - 1."""
+    if not 1 <= border_count <= ops.GBDT_MAX_BORDERS:
+        raise ValueError(f"border_count must be in [1, {ops.GBDT_MAX_BORDERS}] (got {border_count})")
+    Fn, R = x.shape
+    dev = x.device
+    xs, _ = torch.sort(x, dim=1)                      # NaN sorts last
+    first = ~torch.isnan(xs)
+    first[:, 1:] &= xs[:, 1:] != xs[:, :-1]           # the first occurrence of every distinct value
+    rank = torch.cumsum(first, 1) - 1
+    distinct = torch.full((Fn, R + 1), float("inf"), device=dev, dtype=torch.float32)
+    distinct.scatter_(1, torch.where(first, rank, torch.full_like(rank, R)), xs)   # slot R takes the repeats
+    mids = (first.sum(1) - 1).clamp(min=0)            # midpoints a column has
+    n_borders = mids.clamp(max=border_count)
+    j = torch.arange(border_count, device=dev, dtype=torch.int64)[None, :]
+    idx = torch.where(mids[:, None] <= border_count, j, ((2 * j + 1) * mids[:, None]) // (2 * border_count))
+    idx = idx.clamp(min=0, max=R - 1)
+    mid = distinct.gather(1, idx) * 0.5 + distinct.gather(1, idx + 1) * 0.5
+    borders = torch.full((Fn, ops.GBDT_BINS), float("inf"), device=dev, dtype=torch.float32)
+    borders[:, :border_count] = torch.where(j < n_borders[:, None], mid, torch.full_like(mid, float("inf")))
+    return borders, n_borders.to(torch.int32)
+
+
+def _is_frame(X):
+    return hasattr(X, "columns") and hasattr(X, "iloc")
+
+
+class ObliviousBoostingClassifier:
+    """Binary classifier of `iterations` oblivious trees of `depth` <= 6 levels boosted on Logloss.
+
+    X is a dict or DataFrame of columns (those named in cat_features are categorical: any hashable
+    values, coded by a vocabulary built from the training rows, code 0 = unseen; at most 255 distinct
+    values; the others numeric), or a pair (numeric [R, Fn] float, categorical [R, Fc] integer) of tensors
+    or arrays, either may be None; there the categorical values are codes already, in [0, 255] (a value
+    outside it predicts as 0). Internally the numeric columns come first, then the categorical ones: that
+    is the order in which ties between equally good splits are broken.
+
+    After fit: tree_count_, feature_names_, and with an eval_set evals_result_, best_iteration_ (the
+    0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
+
+    def __init__(self, iterations=1000, learning_rate=0.05, depth=6, l2_leaf_reg=3.0, border_count=254,
+                 cat_features=None, early_stopping_rounds=None, metric_period=1, device=None):
+        if iterations < 1:
+            raise ValueError("iterations must be >= 1")
+        if not 1 <= depth <= ops.GBDT_MAX_DEPTH:
+            raise ValueError(f"depth must be in [1, {ops.GBDT_MAX_DEPTH}] (got {depth})")
+        if not l2_leaf_reg > 0:
+            raise ValueError("l2_leaf_reg must be positive")
+        if not 1 <= border_count <= ops.GBDT_MAX_BORDERS:
+            raise ValueError(f"border_count must be in [1, {ops.GBDT_MAX_BORDERS}] (got {border_count})")
+        if metric_period < 1:
+            raise ValueError("metric_period must be >= 1")
+        self.iterations, self.learning_rate, self.depth = int(iterations), float(learning_rate), int(depth)
+        self.l2_leaf_reg, self.border_count = float(l2_leaf_reg), int(border_count)
+        self.cat_features = list(cat_features) if cat_features is not None else []
+        self.early_stopping_rounds, self.metric_period = early_stopping_rounds, int(metric_period)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.model_, self._fitted_names = None, None
+        self.tree_count_ = 0
+        self.evals_result_, self.best_iteration_, self.best_score_ = None, None, None
+
+    # ---- columns -> bins ---------------------------------------------------------------------------
+    def _split_columns(self, X):
+        """(numeric fp32 [Fn, R] device tensor or None, categorical: a list of host value lists (vocabulary
+        path) or an integer [Fc, R] device tensor of codes, or None, numeric names, categorical names)."""
+        dev = self.device
+        if isinstance(X, dict) or _is_frame(X):
+            names = list(X.keys()) if isinstance(X, dict) else list(X.columns)
+            cats = [n for i, n in enumerate(names) if n in self.cat_features or i in self.cat_features]
+            nums = [n for n in names if n not in cats]
+            if self.model_ is not None and self._fitted_names is not None:
+                nums, cats = self._fitted_names      # predict: the training columns, by name
+            num = None
+            if nums:
+                cols = [np.asarray(X[n], dtype=np.float32) for n in nums]
+                num = torch.from_numpy(np.stack(cols)).to(dev)
+            cat = [list(np.asarray(X[n], dtype=object)) for n in cats] if cats else None
+            return num, cat, nums, cats
+        if not isinstance(X, (tuple, list)) or len(X) != 2:
+            raise TypeError("X must be a dict or DataFrame of columns, or a pair (numeric [R, Fn], categorical [R, Fc])")
+        num, cat = X
+        if num is not None:
+            num = torch.as_tensor(num).to(dev, torch.float32)
+            if num.dim() != 2:
+                raise ValueError(f"the numeric block must be [R, Fn] (got {tuple(num.shape)})")
+            num = num.t().contiguous()
+        if cat is not None:
+            cat = torch.as_tensor(cat)
+            if cat.dim() != 2 or cat.dtype not in (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64):
+                raise ValueError("the categorical block must be an integer [R, Fc] tensor")
+            cat = cat.to(dev, torch.int64).t().contiguous()
+        nums = [f"num{i}" for i in range(0 if num is None else num.shape[0])]
+        cats = [f"cat{i}" for i in range(0 if cat is None else cat.shape[0])]
+        return num, cat, nums, cats
+
+    def _bins(self, X):
+        """The uint8 [F, R] bins of X under the fitted borders and vocabularies (no host read)."""
+        num, cat, nums, cats = self._split_columns(X)
+        Fn, Fc = len(nums), len(cats)
+        if (Fn, Fc) != (len(self._fitted_names[0]), len(self._fitted_names[1])):
+            raise ValueError(f"X has {Fn} numeric and {Fc} categorical columns, the model was fitted on "
+                             f"{len(self._fitted_names[0])} and {len(self._fitted_names[1])}")
+        R = num.shape[1] if num is not None else (cat.shape[1] if torch.is_tensor(cat) else len(cat[0]))
+        bins = torch.empty(Fn + Fc, R, device=self.device, dtype=torch.uint8)
+        if Fn:
+            ops.gbdt_bin(num, self.borders_, self.n_borders_, out=bins)
+        if Fc:
+            bins[Fn:] = self._codes(cat, R)
+        return bins
+
+    def _codes(self, cat, R):
+        if torch.is_tensor(cat):
+            return torch.where((cat < 0) | (cat > _MAX_CODES), torch.zeros_like(cat), cat).to(torch.uint8)
+        host = np.empty((len(cat), R), np.uint8)
+        for k, (vals, vocab) in enumerate(zip(cat, self.vocab_)):
+            host[k] = [vocab.get(v, 0) for v in vals]
+        return torch.from_numpy(host).to(self.device)
+
+    # ---- training ----------------------------------------------------------------------------------
+    @torch.no_grad()
+    def fit(self, X, y, eval_set=None, eval_metric="AUC", use_best_model=None, eval_group_id=None,
+            record_approximants=()):
+        """Boost `iterations` trees on X / y [R] in {0, 1}. Nothing synchronises with the host inside a tree
+        and the splits stay on the device; a plain fit reads the host once (the label counts, with the largest
+        code of tensor-given categorical columns in the same copy).
+
+        eval_set=(X_val, y_val) adds the reference's validation (:98-108, :123-135) with the semantics
+        DeepFM.fit documents: after every metric_period-th tree (and the last) the validation scores are
+        advanced by the new trees and evaluated on the device (ops.binary_eval; with eval_group_id also
+        ops.group_eval), one host read per evaluation that also carries the training Logloss after that tree.
+        eval_metric "AUC", "Logloss", "NDCG", "NDCG:top=K" or "QueryAUC" picks the best evaluation (only a
+        strictly better one replaces it), early_stopping_rounds (the constructor's) stops after that many
+        evaluations without an improvement, and use_best_model (default True with an eval_set) truncates the
+        model to best_iteration_ + 1 trees. record_approximants: tree counts t after which the training
+        approximant is kept (approximants_[t], a device tensor), for tests."""
+        esr = self.early_stopping_rounds if eval_set is not None else None
+        use_best_model = _fit_args(eval_set, eval_metric, esr, use_best_model, None, eval_group_id)
+        metric, top = _parse_eval_metric(eval_metric)
+        dev = self.device
+        self.model_, self._fitted_names = None, None
+        num, cat, nums, cats = self._split_columns(X)
+        Fn, Fc = len(nums), len(cats)
+        F = Fn + Fc
+        if not 1 <= F <= ops.GBDT_MAX_FEATURES:
+            raise ValueError(f"need between 1 and {ops.GBDT_MAX_FEATURES} columns (got {F})")
+        y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(dev, torch.float32).reshape(-1).contiguous()
+        R = y.numel()
+        stats = [(y == 1).sum(), (y == 0).sum()]
+        n_bins = [self.border_count + 1] * Fn
+        self.vocab_ = []
+        if Fc and torch.is_tensor(cat):
+            stats += [cat.max(), cat.min()] + list(cat.max(dim=1).values)
+        elif Fc:
+            for name, vals in zip(cats, cat):
+                vocab = {}
+                for v in vals:
+                    if v not in vocab:
+                        vocab[v] = len(vocab) + 1
+                if len(vocab) > _MAX_CODES:
+                    raise ValueError(f"categorical column {name!r} has {len(vocab)} distinct values: at most "
+                                     f"{_MAX_CODES} are supported (no target-statistic encoding)")
+                self.vocab_.append(vocab)
+                n_bins.append(len(vocab) + 1)
+        for name, block in (("numeric", num), ("categorical", cat)):
+            n = None if block is None else (block.shape[1] if torch.is_tensor(block) else len(block[0]))
+            if n is not None and n != R:
+                raise ValueError(f"the {name} columns hold {n} rows for {R} labels")
+        host = [int(v) for v in torch.stack([s.to(torch.int64) for s in stats]).tolist()]     # the one host read
+        n_pos, n_neg = host[:2]
+        if n_pos + n_neg != R:
+            raise ValueError("labels must be 0 or 1")
+        if n_pos == 0 or n_neg == 0:
+            raise ValueError("the training labels hold a single class")
+        if Fc and torch.is_tensor(cat):
+            if host[2] > _MAX_CODES or host[3] < 0:
+                raise ValueError(f"categorical codes must be in [0, {_MAX_CODES}] (got {host[3]} .. {host[2]}): at most "
+                                 f"{_MAX_CODES} known values besides 0 = unknown")
+            n_bins += [m + 1 for m in host[4:]]
+        self._fitted_names = (nums, cats)
+        self.feature_names_ = nums + cats
+        if Fn:
+            self.borders_, self.n_borders_ = build_borders(num, self.border_count)
+        else:
+            self.borders_, self.n_borders_ = None, None
+        is_cat = torch.tensor([0] * Fn + [1] * Fc, dtype=torch.uint8, device=dev)
+        self.n_bins_ = torch.tensor(n_bins, dtype=torch.int32, device=dev)
+        f0 = float(np.float32(math.log(n_pos / R / (1.0 - n_pos / R))))
+        T = self.iterations
+        model = ops.GBDTModel(torch.zeros(T, ops.GBDT_MAX_DEPTH, 2, device=dev, dtype=torch.int32),
+                              torch.zeros(T, ops.GBDT_LEAF_STRIDE, device=dev, dtype=torch.float32), is_cat, self.depth,
+                              f0, 0)
+        self.model_ = model
+        bins = torch.empty(F, R, device=dev, dtype=torch.uint8)
+        if Fn:
+            ops.gbdt_bin(num, self.borders_, self.n_borders_, out=bins)
+        if Fc:
+            bins[Fn:] = self._codes(cat, R)
+
+        validate = eval_set is not None
+        if validate:
+            Xv, yv = eval_set
+            yv = torch.as_tensor(np.asarray(yv) if not torch.is_tensor(yv) else yv).to(dev, torch.float32).reshape(-1)
+            yv = yv.contiguous()
+            _fit_eval_labels(yv, eval_metric)
+            gv = None if eval_group_id is None else _fit_eval_groups(yv, eval_group_id, eval_metric)
+            bins_v = self._bins(Xv)
+            if bins_v.shape[1] != yv.numel():
+                raise ValueError(f"eval_set has {bins_v.shape[1]} rows for {yv.numel()} labels")
+            Fv = torch.full((yv.numel(),), f0, device=dev, dtype=torch.float32)
+            self.evals_result_ = {"learn": {"Logloss": []}, "validation": {"Logloss": [], "AUC": []}}
+            self.best_iteration_, self.best_score_ = None, None
+        best, since, scored = None, 0, 0
+
+        Fx = torch.full((R,), f0, device=dev, dtype=torch.float32)
+        scratch = ops.GBDTScratch(R, F, self.depth, dev)
+        keep = set(int(t) for t in record_approximants)
+        self.approximants_ = {}
+        built = 0
+        for t in range(T):
+            ops.gbdt_tree(bins, y, Fx, is_cat, self.n_bins_, self.depth, self.learning_rate, self.l2_leaf_reg,
+                          model.splits[t], model.leaf_values[t], scratch)
+            built = t + 1
+            if built in keep:
+                self.approximants_[built] = Fx.clone()
+            if not validate or (built % self.metric_period != 0 and built != T):
+                continue
+            ops.gbdt_predict(bins_v, model, ntree_begin=scored, ntree_end=built, init=Fv, out=Fv)
+            scored = built
+            learn = ops.binary_eval(Fx, y).loss_sum / R
+            be = ops.binary_eval(Fv, yv)
+            if gv is None:
+                res, (learn,) = be.result(also=learn)
+                now = {"Logloss": res["logloss"], "AUC": res["auc"]}
+            else:
+                res, grp, (learn,) = ops._fetch_evals(be, ops.group_eval(Fv, yv, gv, top=top), also=learn)
+                now = {"Logloss": res["logloss"], "AUC": res["auc"], "NDCG": grp["ndcg"], "QueryAUC": grp["query_auc"]}
+            ev = self.evals_result_
+            ev["learn"]["Logloss"].append(learn)
+            for name, value in now.items():
+                ev["validation"].setdefault(name, []).append(value)
+            score = -now["Logloss"] if metric == "Logloss" else now[metric]
+            if best is None or score > best:
+                best, since = score, 0
+                self.best_iteration_ = t
+                self.best_score_ = {"validation": now}
+            else:
+                since += 1
+            if esr is not None and since >= esr:
+                break
+        ops._GBDT_GUARD.watch(scratch.flag)      # a range error is reported by the next gbdt call, or by check()
+        model.n_trees = self.best_iteration_ + 1 if (validate and use_best_model) else built
+        self.tree_count_ = model.n_trees
+        return self
+
+    # ---- prediction ----------------------------------------------------------------------------------
+    def _fitted(self):
+        if self.model_ is None:
+            raise RuntimeError("the model is not fitted")
+        return self.model_
+
+    @torch.no_grad()
+    def predict_logits(self, X, ntree_end=None):
+        """The raw scores [R] (fp32 device tensor) of X after the first ntree_end trees (default: tree_count_):
+        bit-identical to the training approximant after as many trees."""
+        model = self._fitted()
+        if ntree_end is not None and not 0 <= ntree_end <= model.splits.shape[0]:
+            raise ValueError(f"ntree_end must be in [0, {model.splits.shape[0]}] (got {ntree_end})")
+        return ops.gbdt_predict(self._bins(X), model, ntree_end=ntree_end)
+
+    def predict_proba(self, X) -> np.ndarray:
+        """CatBoost's shape: [R, 2] = (1 - p, p) with p = sigmoid(raw score), a host array."""
+        p = torch.sigmoid(self.predict_logits(X))
+        return torch.stack([1.0 - p, p], dim=1).cpu().numpy()
+
+    # ---- persistence -----------------------------------------------------------------------------------
+    def save_model(self, path):
+        """torch.save of the trees in use, the borders and the vocabularies."""
+        m = self._fitted()
+        n = m.n_trees
+        cpu = lambda t: None if t is None else t.detach().cpu()   # noqa: E731
+        torch.save({"format": "oblivious_gbdt/1", "splits": cpu(m.splits[:n]), "leaf_values": cpu(m.leaf_values[:n]),
+                    "is_cat": cpu(m.is_cat), "depth": m.depth, "f0": m.f0, "borders": cpu(self.borders_),
+                    "n_borders": cpu(self.n_borders_), "n_bins": cpu(self.n_bins_), "vocab": self.vocab_,
+                    "names": self._fitted_names,
+                    "params": {"iterations": self.iterations, "learning_rate": self.learning_rate, "depth": self.depth,
+                               "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
+                               "cat_features": self.cat_features},
+                    "best_iteration": self.best_iteration_, "best_score": self.best_score_,
+                    "evals_result": self.evals_result_}, path)
+
+    def load_model(self, path):
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        if sd.get("format") != "oblivious_gbdt/1":
+            raise ValueError(f"{path} is not an ObliviousBoostingClassifier model")
+        dev = self.device
+        to = lambda t: None if t is None else t.to(dev).contiguous()   # noqa: E731
+        for k, v in sd["params"].items():
+            setattr(self, k, v)
+        self.model_ = ops.GBDTModel(to(sd["splits"]), to(sd["leaf_values"]), to(sd["is_cat"]), sd["depth"], sd["f0"],
+                                    sd["splits"].shape[0])
+        self.borders_, self.n_borders_, self.n_bins_ = to(sd["borders"]), to(sd["n_borders"]), to(sd["n_bins"])
+        self.vocab_, self._fitted_names = sd["vocab"], tuple(sd["names"])
+        self.feature_names_ = list(self._fitted_names[0]) + list(self._fitted_names[1])
+        self.best_iteration_, self.best_score_, self.evals_result_ = sd["best_iteration"], sd["best_score"], sd["evals_result"]
+        self.tree_count_ = self.model_.n_trees
+        return self

@@ -15,7 +15,9 @@ over ops.binary_eval (rsx_binary_eval: exact tie-aware AUC and Logloss on the de
 that carry the per-customer group id of the reference's ranker data (utils/monitor/log_importer.py),
 ops.group_eval (rsx_group_eval: per-query NDCG@top and QueryAUC; evaluate(group_id=...),
 fit(eval_group_id=..., eval_metric="NDCG" | "NDCG:top=K" | "QueryAUC")); retrieval
-(user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk).
+(user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk). The
+boosted-tree ranker itself (RecommendationRanker, :95-149) runs on the device as backend "native":
+oblivious_gbdt.ObliviousBoostingClassifier (rsx_gbdt_*), served in batches through rsx_rerank_tabular.
 """
 from __future__ import annotations
 
@@ -482,18 +484,61 @@ class FeatureEngineer:
 
 
 class RecommendationRanker:
-    """Reference :95-149 (CatBoost). Importable without catboost; constructing it needs it."""
+    """Reference :95-149: the boosted-tree ranker over the FeatureEngineer columns, with the reference's
+    hyper-parameters (1000 trees of depth 6, learning rate 0.05, Logloss, AUC, early_stopping_rounds 50,
+    use_best_model). backend "catboost": CatBoostClassifier, as the reference (constructing it needs
+    catboost); "native": ObliviousBoostingClassifier (oblivious_gbdt.py: trained and served on the device,
+    a model of its own, not CatBoost's trees); "auto": catboost where it imports, so nothing changes where
+    the class worked before, else native."""
 
-    def __init__(self, model_path: str = None):
-        from catboost import CatBoostClassifier  # noqa: F401  (absent in this image: raises ImportError)
+    def __init__(self, model_path: str = None, backend: str = "auto"):
+        if backend not in ("auto", "catboost", "native"):
+            raise ValueError(f'backend must be "auto", "catboost" or "native" (got {backend!r})')
+        if backend == "auto":
+            try:
+                import catboost  # noqa: F401
+                backend = "catboost"
+            except ImportError:
+                backend = "native"
+        self.backend = backend
         self.engineer = FeatureEngineer()
-        self.model = CatBoostClassifier(iterations=1000, learning_rate=0.05, depth=6, loss_function="Logloss",
-                                        eval_metric="AUC", verbose=100, early_stopping_rounds=50,
-                                        cat_features=self.engineer.cat_features, random_seed=42)
+        if backend == "catboost":
+            from catboost import CatBoostClassifier
+            self.model = CatBoostClassifier(iterations=1000, learning_rate=0.05, depth=6, loss_function="Logloss",
+                                            eval_metric="AUC", verbose=100, early_stopping_rounds=50,
+                                            cat_features=self.engineer.cat_features, random_seed=42)
+        else:
+            from .oblivious_gbdt import ObliviousBoostingClassifier
+            self.model = ObliviousBoostingClassifier(iterations=1000, learning_rate=0.05, depth=6,
+                                                     early_stopping_rounds=50,
+                                                     cat_features=self.engineer.cat_features)
         self.is_fitted = False
         if model_path:
-            self.model.load_model(model_path)
-            self.is_fitted = True
+            self.load_model(model_path)
+
+    def train(self, train_data: List[Dict], val_data: List[Dict] = None):
+        """Reference :114-137: train_data / val_data are FeatureEngineer.prepare_batch rows with a "label"
+        (1 = bought). With val_data the model is validated on it (AUC), stops early and keeps its best
+        iteration."""
+        df = self.engineer.prepare_batch(train_data)
+        X, y = df.drop(columns=["target"]), df["target"]
+        eval_set = None
+        if val_data:
+            dv = self.engineer.prepare_batch(val_data)
+            eval_set = (dv.drop(columns=["target"]), dv["target"])
+        if self.backend == "catboost":
+            self.model.fit(X, y, eval_set=eval_set, use_best_model=True)
+        else:
+            self.model.fit(X, y.to_numpy(), eval_set=None if eval_set is None else (eval_set[0], eval_set[1].to_numpy()),
+                           eval_metric="AUC", use_best_model=True if eval_set is not None else None)
+        self.is_fitted = True
+
+    def save_model(self, path: str):
+        self.model.save_model(path)
+
+    def load_model(self, path: str):
+        self.model.load_model(path)
+        self.is_fitted = True
 
     def predict_proba(self, X) -> np.ndarray:
         return self.model.predict_proba(X)[:, 1]
@@ -552,15 +597,29 @@ class ReRankingSystem:
         return [{"product_id": int(idx_cpu[o]), "two_tower_score": float(sc_cpu[o]), "final_score": float(probs[o])}
                 for o in order]
 
-    def rerank_batch(self, cand_ids: torch.Tensor, cand_scores: torch.Tensor, user_buckets: torch.Tensor,
-                     final_k: int = 10, features=None):
-        """The DeepFM half of recommend for a batch of queries, on the device: candidates [Q, K]
-        (global item ids) -> rerank ids (features(cand_ids, user_buckets) -> [Q, K, F]; default the
-        hashed (user bucket, item) crosses of hashed_cross_features) -> DeepFM probabilities -> the
-        final_k most probable per query (torch.topk: probability desc). Returns (product ids,
-        two-tower scores, final scores), each [Q, final_k]."""
+    def rerank_batch(self, cand_ids: torch.Tensor, cand_scores: torch.Tensor, user_buckets: torch.Tensor = None,
+                     final_k: int = 10, features=None, user_vectors: torch.Tensor = None, user_meta=None):
+        """The rerank half of recommend for a batch of queries, on the device. Returns (product ids,
+        two-tower scores, final scores), each [Q, final_k].
+
+        DeepFM ranker: candidates [Q, K] (global item ids) -> rerank ids (features(cand_ids,
+        user_buckets) -> [Q, K, F]; default the hashed (user bucket, item) crosses of
+        hashed_cross_features) -> DeepFM probabilities -> the final_k most probable per query
+        (torch.topk: probability desc).
+
+        Native RecommendationRanker (backend "native", trained on FeatureEngineer rows): user_vectors
+        [Q, d] and user_meta (a list of Q dicts as recommend's user_meta_raw; default {}) ->
+        ops.rerank_tabular (the numeric FeatureEngineer columns of every candidate from the item
+        vectors and the per-item / per-user price tensors) -> ops.gbdt_bin with the model's borders,
+        the categorical codes gathered from per-item code tables built once from item_db_metadata ->
+        ops.gbdt_predict -> torch.topk. user_buckets and features are not used."""
+        if _is_native_ranker(self.ranker):
+            if user_vectors is None:
+                raise ValueError("rerank_batch with the native tree ranker needs user_vectors [Q, d]")
+            return self._rerank_tabular(cand_ids, cand_scores, user_vectors, user_meta, final_k)
         if not isinstance(self.ranker, DeepFM):
-            raise TypeError("rerank_batch needs a DeepFM ranker (the CatBoost path is per-user, recommend)")
+            raise TypeError("rerank_batch needs a DeepFM or a native RecommendationRanker (the CatBoost path is "
+                            "per-user, recommend)")
         Q, K = cand_ids.shape
         if features is not None:
             feats = features(cand_ids, user_buckets)
@@ -575,17 +634,91 @@ class ReRankingSystem:
         return torch.gather(cand_ids, 1, top_j), torch.gather(cand_scores, 1, top_j), top_p
 
     def recommend_batch(self, user_vectors: torch.Tensor, user_buckets: torch.Tensor = None,
-                        top_k_retrieval: int = 100, final_k: int = 10):
-        """recommend (reference :170-237) for a batch of users with a DeepFM ranker, entirely on the
-        device: exact top-k retrieval of user_vectors [Q, D] against the item vectors
-        (rsx_retrieve_topk), then rerank_batch. user_buckets [Q] int64 (default: q % 1000).
-        Returns (product ids, two-tower scores, final scores), each [Q, final_k]."""
+                        top_k_retrieval: int = 100, final_k: int = 10, user_meta=None):
+        """recommend (reference :170-237) for a batch of users with a DeepFM or a native
+        RecommendationRanker, entirely on the device: exact top-k retrieval of user_vectors [Q, D]
+        against the item vectors (rsx_retrieve_topk), then rerank_batch. user_buckets [Q] int64
+        (DeepFM; default: q % 1000); user_meta: Q dicts (native ranker). Returns (product ids,
+        two-tower scores, final scores), each [Q, final_k]."""
         uv = user_vectors.to(self.device, torch.float32)
         Q = uv.shape[0]
+        if _is_native_ranker(self.ranker):
+            sc, idx = ops.retrieve_topk(uv, self.item_vectors, top_k_retrieval)
+            return self.rerank_batch(idx, sc, None, final_k, user_vectors=uv, user_meta=user_meta)
         if user_buckets is None:
             user_buckets = torch.arange(Q, device=self.device, dtype=torch.int64) % 1000
         sc, idx = ops.retrieve_topk(uv, self.item_vectors, top_k_retrieval)
         return self.rerank_batch(idx, sc, user_buckets, final_k)
+
+
+    # the FeatureEngineer columns the meta dicts feed: column -> (whose meta, its key)
+    _TABULAR_CATS = {"season": ("user", "season"), "gender": ("user", "gender"),
+                     "item_category": ("item", "category"), "item_material": ("item", "material"),
+                     "item_fit": ("item", "fit")}
+
+    def _tabular_tables(self, clf):
+        """Per-item tensors of the native rerank path, built once per fitted model from item_db_metadata
+        (item i = row i of the item vectors): price fp32 [N] and, per categorical item column of the model,
+        its codes uint8 [N] under the model's vocabulary."""
+        cached = self.__dict__.get("_tabular")
+        if cached is not None and cached["model"] is clf.model_:
+            return cached
+        n = self.item_vectors.shape[0]
+        metas = [self.item_metadata.get(i, {}) for i in range(n)]
+        nums, cats = clf._fitted_names
+        unknown = [c for c in nums if c not in ops.RERANK_TABULAR_COLUMNS]
+        if unknown or not clf.vocab_ and cats:
+            raise ValueError(f"the native ranker was not fitted on FeatureEngineer rows (columns {unknown or cats})")
+        codes = {}
+        for name, vocab in zip(cats, clf.vocab_):
+            side, key = self._TABULAR_CATS.get(name, (None, None))
+            if side == "item":
+                host = np.fromiter((vocab.get(m.get(key, "unknown"), 0) for m in metas), np.uint8, n)
+                codes[name] = torch.from_numpy(host).to(self.device)
+        price = torch.tensor([float(m.get("price", 0)) for m in metas], dtype=torch.float32, device=self.device)
+        col = {c: i for i, c in enumerate(ops.RERANK_TABULAR_COLUMNS)}
+        rows = [col[c] for c in nums]
+        cached = self.__dict__["_tabular"] = {
+            "model": clf.model_, "price": price, "codes": codes,
+            "rows": None if rows == list(range(len(col))) else torch.tensor(rows, device=self.device)}
+        return cached
+
+    @torch.no_grad()
+    def _rerank_tabular(self, cand_ids, cand_scores, user_vectors, user_meta, final_k):
+        clf = self.ranker.model
+        if clf.model_ is None:
+            raise RuntimeError("the native ranker is not fitted")
+        Q, K = cand_ids.shape
+        user_meta = [{}] * Q if user_meta is None else list(user_meta)
+        if len(user_meta) != Q:
+            raise ValueError(f"user_meta holds {len(user_meta)} dicts for {Q} queries")
+        tab = self._tabular_tables(clf)
+        uv = user_vectors.to(self.device, torch.float32)
+        avg = torch.tensor([float(m.get("avg_price", 0.0)) for m in user_meta], dtype=torch.float32, device=self.device)
+        feats, ids = ops.rerank_tabular(cand_ids, cand_scores.to(torch.float32), uv, self.item_vectors, tab["price"], avg)
+        nums, cats = clf._fitted_names
+        bins = torch.empty(len(nums) + len(cats), Q * K, device=self.device, dtype=torch.uint8)
+        if nums:
+            x = feats if tab["rows"] is None else feats.index_select(0, tab["rows"])
+            ops.gbdt_bin(x, clf.borders_, clf.n_borders_, out=bins)
+        for k, (name, vocab) in enumerate(zip(cats, clf.vocab_)):
+            side, key = self._TABULAR_CATS.get(name, (None, None))
+            row = bins[len(nums) + k]
+            if side == "item":
+                row.copy_(tab["codes"][name].index_select(0, ids))
+            elif side == "user":
+                per_user = torch.tensor([vocab.get(m.get(key, "unknown"), 0) for m in user_meta], dtype=torch.uint8,
+                                        device=self.device)
+                row.copy_(per_user.repeat_interleave(K))
+            else:
+                row.zero_()
+        prob = torch.sigmoid(ops.gbdt_predict(bins, clf.model_)).view(Q, K)
+        top_p, top_j = torch.topk(prob, final_k, dim=1)
+        return torch.gather(cand_ids, 1, top_j), torch.gather(cand_scores, 1, top_j), top_p
+
+
+def _is_native_ranker(ranker) -> bool:
+    return isinstance(ranker, RecommendationRanker) and ranker.backend == "native"
 
 
 class CrossNet(nn.Module):
