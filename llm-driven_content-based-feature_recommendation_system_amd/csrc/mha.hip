@@ -11,14 +11,27 @@
 // Semantics pinned to the training-mode (non fast-path) reference: a query row whose keys
 // are all masked (left-padded positions under the causal mask) gets all-zero
 // probabilities, so its attention output is exactly 0 (=> out_proj.bias after out_proj).
-// Attention-probability dropout (p > 0) uses the counter-based hash in rsx_common.h.
+// Attention-probability dropout (p > 0) uses the counter-based hash in rsx_common.h, indexed by
+// drop_row(query token, head) + key: the forwards and grad_elem take the index from that one place.
 //
-// One 64-lane workgroup per (batch, head): lane i owns query row i. K/V rows of the head
-// are staged in LDS and read by broadcast; scores live in registers (L <= 64).
+// The unit of work is one (sequence, head). Which kernel serves which configuration:
+//   precision  head dim  forward              backward
+//   fp32       16        mha_fwd_k<16>        mha_bwd_k<16>
+//   fp32       32        mha_fwd_k<32>        mha_bwd_mfma_k
+//   fp32       64        mha_fwd_k<64>        mha_bwd64_k<32> (L <= 32), mha_bwd64_k<64>
+//   bf16x3     32        mha_fwd_x3b_k        mha_bwd_x3s_k (causal), mha_bwd_x3p_k (non-causal)
+//   bf16x3     64        mha_fwd_x3b64_k      the fp32 mha_bwd64_k
+//   bf16x3     32, H = 4 mha_qkv_fwd_x3_k<4>  as bf16x3 32 (in_proj fused into the forward)
+// mha_fwd_k, mha_bwd_k and mha_bwd64_k run one 64-lane workgroup per unit with the head's rows in LDS;
+// every other kernel runs one wave per unit, four per workgroup, on MFMAs without LDS (mha_bwd_x3s_k:
+// a per-wave dS stash). Written once for all of them: the unit prologue (seq_span, wave_unit), the
+// backward's token statistics (token_stats) and softmax-gradient element (grad_elem), the bf16x3
+// forwards' query block (attn_qblock) and the bf16x3 backwards' pass 1 (bwd_x3_pass1).
 #include "rsx_common.h"
 #include "rsx_x3.h"
 #include <math.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -35,17 +48,123 @@ struct FwdArgs {
   rsx::Dropout drop;
 };
 
+struct BwdArgs {
+  const float* qkv;
+  const uint8_t* kpad;
+  const int* seg;
+  const float* out;   // forward output O [T, D]
+  const float* lse;   // [T, H]
+  const float* dout;  // [T, D]
+  float* dqkv;        // [T, 3D] (written)
+  int B, L, H, causal;
+  float scale;
+  rsx::Dropout drop;
+};
+
+// Sequence b of the batch: its first token, and its length clamped to cap, the most tokens the kernel
+// holds (packed segments are <= 51 by construction; mha_bwd64_k<LM>: the host sizes LM by the longest
+// sequence).
+template <class A>
+__device__ __forceinline__ int seq_span(const A& a, int b, int cap, int64_t& tok0) {
+  tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
+  const int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
+  return L > cap ? cap : L;
+}
+
+// One wave per unit, four per workgroup: body(hd, tok0, L) for this wave's unit, unless it has none or
+// an empty sequence (nothing written). A continuation, not a bool result: the early exits stay exits.
+template <class A, class F>
+__device__ __forceinline__ void wave_unit(const A& a, int wave, F body) {
+  const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
+  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
+  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
+  int64_t tok0;
+  const int L = seq_span(a, b, kLMax, tok0);
+  if (L <= 0) return;
+  body(hd, tok0, L);
+}
+
+__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+__device__ __forceinline__ int blocks16(int L) { return __builtin_amdgcn_readfirstlane((L + 15) >> 4); }
+
+// f(integral_constant NB) with NB = the 1 .. 4 16-token blocks of a sequence of L tokens
+template <class F>
+__device__ __forceinline__ void for_blocks(int L, F f) {
+  const int nb = blocks16(L);
+  if (nb == 1) f(std::integral_constant<int, 1>{});
+  else if (nb == 2) f(std::integral_constant<int, 2>{});
+  else if (nb == 3) f(std::integral_constant<int, 3>{});
+  else f(std::integral_constant<int, 4>{});
+}
+
+__device__ __forceinline__ int key_pad(const uint8_t* kpad, int64_t tok) { return kpad ? (int)kpad[tok] : 0; }
+
+// dropout hash index of (query token, head, key 0); key j adds j
+__device__ __forceinline__ uint64_t drop_row(int64_t tok, int H, int hd) { return ((uint64_t)tok * H + hd) * kLMax; }
+
+// Backward statistics of one token of head hd: lse, delta = dO . O (holds with dropout:
+// sum_j P_ij dP_ij = dO_i . O_i) and the key pad flag.
+template <int DH>
+__device__ __forceinline__ void token_stats(const BwdArgs& a, int64_t tok, int hd, float& lse, float& delta,
+                                            int& pad) {
+  const int D = a.H * DH;
+  lse = a.lse[tok * a.H + hd];
+  const float4* op = reinterpret_cast<const float4*>(a.out + tok * D + hd * DH);
+  const float4* gp = reinterpret_cast<const float4*>(a.dout + tok * D + hd * DH);
+  float d = 0.0f;
+#pragma unroll
+  for (int t = 0; t < DH / 4; ++t) {
+    const float4 x = op[t], y = gp[t];
+    d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
+  }
+  delta = d;
+  pad = key_pad(a.kpad, tok);
+}
+
+// Element (query i, key j) of the softmax gradient, from the score s and dp = dO_i . V_j: P = exp(s sc -
+// lse_i), the keep bit of the forward's dropout, Pd = the dropped-out P (pd_out) and the returned
+// dS = P (dPd - delta_i) sc. Both are 0 where the mask does not allow the pair.
+__device__ __forceinline__ float grad_elem(const BwdArgs& a, float sc, int64_t tok0, int hd, int i, int j, float s,
+                                           float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
+  pd_out = 0.0f;
+  if (!allowed) return 0.0f;
+  const float p = __expf(s * sc - lse_i);
+  float pd = p, dpd = dp;
+  if (a.drop.active()) {
+    const bool keep = rsx::hash_u32(a.drop.seed, drop_row(tok0 + i, a.H, hd) + j) >= a.drop.thresh;
+    pd = keep ? p * a.drop.scale : 0.0f;
+    dpd = keep ? dp * a.drop.scale : 0.0f;
+  }
+  pd_out = pd;
+  return p * (dpd - delta_i) * sc;
+}
+
+// Q, K and dO rows of the head into LDS (the fp32 backwards on the VALU)
+template <int DH, int LM>
+__device__ __forceinline__ void stage_q_k_do(const float* base, const float* dob, int hd, int D, int L,
+                                             float (&sQ)[LM][DH], float (&sK)[LM][DH], float (&sdO)[LM][DH]) {
+  constexpr int V4 = DH / 4;
+  for (int t = threadIdx.x; t < L * V4; t += 64) {
+    const int r = t / V4, c4 = t % V4;
+    const float4* rowp = reinterpret_cast<const float4*>(base + (int64_t)r * 3 * D);
+    reinterpret_cast<float4*>(&sQ[r][0])[c4] = rowp[(hd * DH) / 4 + c4];
+    reinterpret_cast<float4*>(&sK[r][0])[c4] = rowp[(D + hd * DH) / 4 + c4];
+    reinterpret_cast<float4*>(&sdO[r][0])[c4] = reinterpret_cast<const float4*>(dob + (int64_t)r * D + hd * DH)[c4];
+  }
+}
+
+// ---- fp32 on the VALU: one 64-lane workgroup per unit, lane i owns query row i. K/V rows of the head
+// are staged in LDS and read by broadcast; scores live in registers (L <= 64).
 template <int DH>
 __global__ __launch_bounds__(64) void mha_fwd_k(FwdArgs a) {
   __shared__ __attribute__((aligned(16))) float sK[kLMax][DH];
   __shared__ __attribute__((aligned(16))) float sV[kLMax][DH];
   __shared__ int sPad[kLMax];
   const int D = a.H * DH;
-  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
   const int i = threadIdx.x;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;  // packed segments are <= 51 by construction
+  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
+  int64_t tok0;
+  const int L = seq_span(a, b, kLMax, tok0);
   const float* base = a.qkv + tok0 * 3 * D;
 
   constexpr int V4 = DH / 4;
@@ -55,7 +174,7 @@ __global__ __launch_bounds__(64) void mha_fwd_k(FwdArgs a) {
     reinterpret_cast<float4*>(&sK[r][0])[c4] = rowp[(D + hd * DH) / 4 + c4];
     reinterpret_cast<float4*>(&sV[r][0])[c4] = rowp[(2 * D + hd * DH) / 4 + c4];
   }
-  if (i < L) sPad[i] = a.kpad ? (int)a.kpad[tok0 + i] : 0;
+  if (i < L) sPad[i] = key_pad(a.kpad, tok0 + i);
   __syncthreads();
   if (i >= L) return;
 
@@ -104,7 +223,7 @@ __global__ __launch_bounds__(64) void mha_fwd_k(FwdArgs a) {
     }
     const float inv = 1.0f / sum;
     lse = mx + logf(sum);
-    const uint64_t rowidx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax;
+    const uint64_t rowidx = drop_row(tok0 + i, a.H, hd);
 #pragma unroll
     for (int j = 0; j < kLMax; ++j) {
       if (j < L) {
@@ -129,19 +248,6 @@ __global__ __launch_bounds__(64) void mha_fwd_k(FwdArgs a) {
   if (a.lse) a.lse[(tok0 + i) * a.H + hd] = lse;
 }
 
-struct BwdArgs {
-  const float* qkv;
-  const uint8_t* kpad;
-  const int* seg;
-  const float* out;   // forward output O [T, D]
-  const float* lse;   // [T, H]
-  const float* dout;  // [T, D]
-  float* dqkv;        // [T, 3D] (written)
-  int B, L, H, causal;
-  float scale;
-  rsx::Dropout drop;
-};
-
 template <int DH>
 __global__ __launch_bounds__(64) void mha_bwd_k(BwdArgs a) {
   __shared__ __attribute__((aligned(16))) float sQ[kLMax][DH];
@@ -151,36 +257,16 @@ __global__ __launch_bounds__(64) void mha_bwd_k(BwdArgs a) {
   __shared__ int sPad[kLMax];
   __shared__ float sdS[kLMax][kLMax + 1];
   const int D = a.H * DH;
-  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
   const int lane = threadIdx.x;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;  // packed segments are <= 51 by construction
+  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
+  int64_t tok0;
+  const int L = seq_span(a, b, kLMax, tok0);
   const float* base = a.qkv + tok0 * 3 * D;
   const float* dob = a.dout + tok0 * D;
   constexpr int V4 = DH / 4;
 
-  for (int t = threadIdx.x; t < L * V4; t += 64) {
-    const int r = t / V4, c4 = t % V4;
-    const float4* rowp = reinterpret_cast<const float4*>(base + (int64_t)r * 3 * D);
-    reinterpret_cast<float4*>(&sQ[r][0])[c4] = rowp[(hd * DH) / 4 + c4];
-    reinterpret_cast<float4*>(&sK[r][0])[c4] = rowp[(D + hd * DH) / 4 + c4];
-    reinterpret_cast<float4*>(&sdO[r][0])[c4] = reinterpret_cast<const float4*>(dob + (int64_t)r * D + hd * DH)[c4];
-  }
-  if (lane < L) {
-    sPad[lane] = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
-    sLse[lane] = a.lse[(tok0 + lane) * a.H + hd];
-    // delta_i = dO_i . O_i  (holds with dropout: sum_j P_ij dP_ij = dO_i . O_i)
-    const float4* op = reinterpret_cast<const float4*>(a.out + (tok0 + lane) * D + hd * DH);
-    const float4* dp = reinterpret_cast<const float4*>(dob + (int64_t)lane * D + hd * DH);
-    float d = 0.0f;
-#pragma unroll
-    for (int t = 0; t < V4; ++t) {
-      const float4 x = op[t], y = dp[t];
-      d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    sDelta[lane] = d;
-  }
+  stage_q_k_do(base, dob, hd, D, L, sQ, sK, sdO);
+  if (lane < L) token_stats<DH>(a, tok0 + lane, hd, sLse[lane], sDelta[lane], sPad[lane]);
   __syncthreads();
 
   // ---- pass A: lane j owns key/value row j: dK_j, dV_j, and dS column j into LDS ----
@@ -219,15 +305,8 @@ __global__ __launch_bounds__(64) void mha_bwd_k(BwdArgs a) {
         pdot = fmaf(gv.x, vj[4 * t], pdot); pdot = fmaf(gv.y, vj[4 * t + 1], pdot);
         pdot = fmaf(gv.z, vj[4 * t + 2], pdot); pdot = fmaf(gv.w, vj[4 * t + 3], pdot);
       }
-      const float p = __expf(sdot * a.scale - lse_i);
-      const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-      float pd = p, dp = pdot;
-      if (a.drop.active()) {
-        const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-        pd = keep ? p * a.drop.scale : 0.0f;
-        dp = keep ? pdot * a.drop.scale : 0.0f;
-      }
-      ds = p * (dp - sDelta[i]) * a.scale;
+      float pd;
+      ds = grad_elem(a, a.scale, tok0, hd, i, j, sdot, pdot, lse_i, sDelta[i], true, pd);
 #pragma unroll
       for (int t = 0; t < V4; ++t) {
         const float4 qv = reinterpret_cast<const float4*>(&sQ[i][0])[t];
@@ -293,33 +372,14 @@ __global__ __launch_bounds__(64) void mha_bwd64_k(BwdArgs a) {
   __shared__ float sLse[LM], sDelta[LM];
   __shared__ int sPad[LM];
   const int D = a.H * DH;
-  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
   const int lane = threadIdx.x;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > LM) L = LM;  // the host sizes LM by the longest sequence
+  const int b = blockIdx.x / a.H, hd = blockIdx.x % a.H;
+  int64_t tok0;
+  const int L = seq_span(a, b, LM, tok0);
   const float* base = a.qkv + tok0 * 3 * D;
   const float* dob = a.dout + tok0 * D;
-  for (int t = lane; t < L * V4; t += 64) {
-    const int r = t / V4, c4 = t % V4;
-    const float4* rowp = reinterpret_cast<const float4*>(base + (int64_t)r * 3 * D);
-    reinterpret_cast<float4*>(&sQ[r][0])[c4] = rowp[(hd * DH) / 4 + c4];
-    reinterpret_cast<float4*>(&sK[r][0])[c4] = rowp[(D + hd * DH) / 4 + c4];
-    reinterpret_cast<float4*>(&sdO[r][0])[c4] = reinterpret_cast<const float4*>(dob + (int64_t)r * D + hd * DH)[c4];
-  }
-  if (lane < L) {
-    sPad[lane] = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
-    sLse[lane] = a.lse[(tok0 + lane) * a.H + hd];
-    const float4* op = reinterpret_cast<const float4*>(a.out + (tok0 + lane) * D + hd * DH);
-    const float4* dp = reinterpret_cast<const float4*>(dob + (int64_t)lane * D + hd * DH);
-    float d = 0.0f;
-#pragma unroll
-    for (int t = 0; t < V4; ++t) {
-      const float4 x = op[t], y = dp[t];
-      d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    sDelta[lane] = d;
-  }
+  stage_q_k_do(base, dob, hd, D, L, sQ, sK, sdO);
+  if (lane < L) token_stats<DH>(a, tok0 + lane, hd, sLse[lane], sDelta[lane], sPad[lane]);
   __syncthreads();
   const int j = lane;
   const bool jok = j < L;
@@ -350,16 +410,7 @@ __global__ __launch_bounds__(64) void mha_bwd64_k(BwdArgs a) {
           pdot = fmaf(gv.x, vj[4 * t], pdot); pdot = fmaf(gv.y, vj[4 * t + 1], pdot);
           pdot = fmaf(gv.z, vj[4 * t + 2], pdot); pdot = fmaf(gv.w, vj[4 * t + 3], pdot);
         }
-        const float p = __expf(sdot * a.scale - lse_i);
-        const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-        pd = p;
-        float dp = pdot;
-        if (a.drop.active()) {
-          const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-          pd = keep ? p * a.drop.scale : 0.0f;
-          dp = keep ? pdot * a.drop.scale : 0.0f;
-        }
-        ds = p * (dp - sDelta[i]) * a.scale;
+        ds = grad_elem(a, a.scale, tok0, hd, i, j, sdot, pdot, lse_i, sDelta[i], true, pd);
       }
       if (j < LM) {
         sDS[i][j] = ds;
@@ -470,18 +521,21 @@ __device__ __forceinline__ void acc_colT(f32x16& acc, const float* base, int64_t
   }
 }
 
+// This kernel keeps its own unit prologue and token statistics: on wave_unit / token_stats (its wave index
+// is per lane, its O and dO rows come off the head's base pointers) the two seg loads merge, delta's products
+// contract differently (dqkv no longer bit-equal) and it measured 0.5 % slower; DESIGN.md has the figures.
 __global__ __launch_bounds__(256) void mha_bwd_mfma_k(BwdArgs a) {
   constexpr int DH = 32;
   const int lane = threadIdx.x & 63, c = lane & 31, h = lane >> 5;
   const int64_t unit = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
   const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int D = a.H * DH;
-  const int64_t ld = 3 * (int64_t)D;
   const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
   int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
   if (L > kLMax) L = kLMax;
   if (L <= 0) return;
+  const int D = a.H * DH;
+  const int64_t ld = 3 * (int64_t)D;
   const int nb = (L + 31) >> 5;
   const float* Qb = a.qkv + tok0 * ld + hd * DH;
   const float* Kb = Qb + D;
@@ -510,21 +564,8 @@ __global__ __launch_bounds__(256) void mha_bwd_mfma_k(BwdArgs a) {
     my_delta = d;
     my_pad = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
   }
-
-  // element (query i, key j) -> (p, pd, dpd factor) ; returns dS and Pd
-  auto grad_elem = [&](int i, int j, float s, float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
-    pd_out = 0.0f;
-    if (!allowed) return 0.0f;
-    const float p = __expf(s * sc - lse_i);
-    float pd = p, dpd = dp;
-    if (a.drop.active()) {
-      const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-      const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-      pd = keep ? p * a.drop.scale : 0.0f;
-      dpd = keep ? dp * a.drop.scale : 0.0f;
-    }
-    pd_out = pd;
-    return p * (dpd - delta_i) * sc;
+  auto elem = [&](int i, int j, float s, float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
+    return grad_elem(a, sc, tok0, hd, i, j, s, dp, lse_i, delta_i, allowed, pd_out);
   };
 
   // ---- key block on the lanes: dK, dV ----
@@ -553,7 +594,7 @@ __global__ __launch_bounds__(256) void mha_bwd_mfma_k(BwdArgs a) {
         const float del_i = __shfl(my_delta, i & 63, 64);
         const bool allowed = jok && i < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
         float pd;
-        S[r] = grad_elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd);
+        S[r] = elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd);
         Pd[r] = pd;
       }
       const int nrows = L - 32 * qb;
@@ -596,7 +637,7 @@ __global__ __launch_bounds__(256) void mha_bwd_mfma_k(BwdArgs a) {
         const int jpad = __shfl(my_pad, j & 63, 64);
         const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
         float pd;
-        S[r] = grad_elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd);
+        S[r] = elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd);
       }
       acc_colT(dqT, Kb, ld, 32 * kb, L - 32 * kb, S, c, h);  // dQ^T[e][i] += sum_j K[j][e] dS^T[j][i]
     }
@@ -642,8 +683,23 @@ __device__ __forceinline__ Col4 split4(const float (&f)[4]) {
   return c;
 }
 
-__device__ __forceinline__ f32x4 dot16_x3(const Row8& a, const Row8& b) {
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+__device__ __forceinline__ Col4 split_col4(const unsigned (&v)[4]) {
+  const float f[4] = {__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
+  return split4(f);
+}
+
+__device__ __forceinline__ Row8 split8(const float (&f)[8]) {
+  Row8 r;
+  rsx::split_x3(f, r.hi, r.lo);
+  return r;
+}
+__device__ __forceinline__ Row8 split8(const u32x4& x0, const u32x4& x1) {
+  const float f[8] = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w),
+                      __uint_as_float(x1.x), __uint_as_float(x1.y), __uint_as_float(x1.z), __uint_as_float(x1.w)};
+  return split8(f);
+}
+
+__device__ __forceinline__ f32x4 dot16_x3(const Row8& a, const Row8& b, f32x4 acc = {0.f, 0.f, 0.f, 0.f}) {
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
@@ -657,29 +713,98 @@ __device__ __forceinline__ f32x4 sum16_x3(const Col4& a, const Col4& b, f32x4 ac
   return acc;
 }
 
+// Buffer resource over a sequence's rows: a load past `bytes` (rows >= L, or the pair after the last
+// of a pipelined walk) reads as zero by the range check, so no load is predicated.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t seq_rsrc(const void* base, unsigned bytes) {
+  const uintptr_t bp = (uintptr_t)base;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)bp);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0,
+                                           (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+
+// Query block qb (16 queries, query i = 16qb + c on this lane's score column) of one head, as the three
+// bf16x3 forwards run it: scores -> mask -> two-step safe softmax -> dropout -> P V -> store -> lse.
+// score(kb) yields the unscaled S^T tile of key block kb ([key 16kb+4g+r][query i]) and vcol(kb, et) V's
+// columns 16et + c of keys 16kb+4g .. +3; the operand loads or projection, and where K is split, stay with
+// the caller. Ob = the head's columns of the sequence's output rows (row stride D).
+template <int NB, int NT, class A, class SF, class VF>
+__device__ __forceinline__ void attn_qblock(const A& a, int qb, int hd, int64_t tok0, int L, int c, int g,
+                                            int my_pad, float* Ob, int D, SF score, VF vcol) {
+  const int i = 16 * qb + c;
+  const bool iok = i < L;
+  const int kb_end = a.causal ? qb : NB - 1;
+  f32x4 sv[NB];
+  float m = -INFINITY;
+#pragma unroll
+  for (int kb = 0; kb < NB; ++kb) {
+    if (kb <= kb_end) {
+      sv[kb] = score(kb);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = 16 * kb + 4 * g + r;
+        const int jpad = __shfl(my_pad, j & 63, 64);
+        const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i);
+        sv[kb][r] = allowed ? sv[kb][r] * a.scale : -INFINITY;
+        m = fmaxf(m, sv[kb][r]);
+      }
+    }
+  }
+  m = fmaxf(m, __shfl_xor(m, 16, 64));
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  float l = 0.0f;
+#pragma unroll
+  for (int kb = 0; kb < NB; ++kb) {
+    if (kb <= kb_end) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float pv = (sv[kb][r] == -INFINITY) ? 0.0f : __expf(sv[kb][r] - m);
+        sv[kb][r] = pv;
+        l += pv;
+      }
+    }
+  }
+  l += __shfl_xor(l, 16, 64);
+  l += __shfl_xor(l, 32, 64);
+  const float inv = (l > 0.0f) ? 1.0f / l : 0.0f;
+  f32x4 o[NT];
+#pragma unroll
+  for (int et = 0; et < NT; ++et) o[et] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint64_t rowidx = drop_row(tok0 + i, a.H, hd);
+#pragma unroll
+  for (int kb = 0; kb < NB; ++kb) {
+    if (kb <= kb_end) {
+      float pr[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pr[r] = a.drop.apply(sv[kb][r] * inv, rowidx + 16 * kb + 4 * g + r);
+      const Col4 pa = split4(pr);
+#pragma unroll
+      for (int et = 0; et < NT; ++et) o[et] = sum16_x3(pa, vcol(kb, et), o[et]);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 16 * qb + 4 * g + r;
+    if (row < L) {
+#pragma unroll
+      for (int et = 0; et < NT; ++et) Ob[(int64_t)row * D + 16 * et + c] = o[et][r];
+    }
+  }
+  if (a.lse && g == 0 && iok) a.lse[(tok0 + i) * a.H + hd] = (l > 0.0f) ? m + logf(l) : -INFINITY;
+}
+
 // Forward with every operand load issued before the first use: the sequence's Q and K rows and
 // V columns of this head for all NB 16-token blocks come in through one buffer resource over the
 // sequence's rows (rows >= L read as zero by the range check: no branches, no per-load waits),
 // so a wave pays one memory latency instead of one or two per query block (loading K / V per
 // query block behind data-dependent branches).
-__device__ __forceinline__ Row8 split_row8(const u32x4& x0, const u32x4& x1) {
-  const float f[8] = {__uint_as_float(x0.x), __uint_as_float(x0.y), __uint_as_float(x0.z), __uint_as_float(x0.w),
-                      __uint_as_float(x1.x), __uint_as_float(x1.y), __uint_as_float(x1.z), __uint_as_float(x1.w)};
-  Row8 r;
-  rsx::split_x3(f, r.hi, r.lo);
-  return r;
-}
 template <int NB>
 __device__ __forceinline__ void mha_fwd_x3b_seq(const FwdArgs& a, int hd, int64_t tok0, int L, int lane) {
   constexpr int DH = 32;
   const int c = lane & 15, g = lane >> 4;
   const int D = a.H * DH;
   const int64_t ld = 3 * (int64_t)D;
-  const uintptr_t bp = (uintptr_t)(a.qkv + tok0 * ld);
-  const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-  const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * ld * 4));
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
+  const auto rs = seq_rsrc(a.qkv + tok0 * ld, (unsigned)(L * ld * 4));
   u32x4 qr[NB][2], kr[NB][2];
   unsigned vr[NB][2][4];
 #pragma unroll
@@ -696,76 +821,17 @@ __device__ __forceinline__ void mha_fwd_x3b_seq(const FwdArgs& a, int hd, int64_
         vr[bb][et][t] = __builtin_amdgcn_raw_buffer_load_b32(
             rs, (unsigned)(((16 * bb + 4 * g + t) * ld + 2 * D + hd * DH + 16 * et + c) * 4), 0, 0);
   }
-  const int my_pad = (lane < L) ? (a.kpad ? (int)a.kpad[tok0 + lane] : 0) : 1;
+  const int my_pad = (lane < L) ? key_pad(a.kpad, tok0 + lane) : 1;
   float* Ob = a.out + tok0 * D + hd * DH;
-  Row8 kx[NB];
+  Row8 kx[NB];  // K is split once, before the query loop
 #pragma unroll
-  for (int bb = 0; bb < NB; ++bb) kx[bb] = split_row8(kr[bb][0], kr[bb][1]);
+  for (int bb = 0; bb < NB; ++bb) kx[bb] = split8(kr[bb][0], kr[bb][1]);
 #pragma unroll
   for (int qb = 0; qb < NB; ++qb) {
-    const int i = 16 * qb + c;  // query of this lane's score column
-    const bool iok = i < L;
-    const Row8 qx = split_row8(qr[qb][0], qr[qb][1]);
-    const int kb_end = a.causal ? qb : NB - 1;
-    f32x4 sv[NB];
-    float m = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        sv[kb] = dot16_x3(kx[kb], qx);  // S^T: [key 16kb+4g+r][query i]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = 16 * kb + 4 * g + r;
-          const int jpad = __shfl(my_pad, j & 63, 64);
-          const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i);
-          sv[kb][r] = allowed ? sv[kb][r] * a.scale : -INFINITY;
-          m = fmaxf(m, sv[kb][r]);
-        }
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = (sv[kb][r] == -INFINITY) ? 0.0f : __expf(sv[kb][r] - m);
-          sv[kb][r] = pv;
-          l += pv;
-        }
-      }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = (l > 0.0f) ? 1.0f / l : 0.0f;
-    f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const uint64_t rowidx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        float pr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pr[r] = a.drop.apply(sv[kb][r] * inv, rowidx + 16 * kb + 4 * g + r);
-        const Col4 pa = split4(pr);
-#pragma unroll
-        for (int et = 0; et < 2; ++et) {
-          const float vf[4] = {__uint_as_float(vr[kb][et][0]), __uint_as_float(vr[kb][et][1]),
-                               __uint_as_float(vr[kb][et][2]), __uint_as_float(vr[kb][et][3])};
-          o[et] = sum16_x3(pa, split4(vf), o[et]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * qb + 4 * g + r;
-      if (row < L) {
-        Ob[(int64_t)row * D + c] = o[0][r];
-        Ob[(int64_t)row * D + 16 + c] = o[1][r];
-      }
-    }
-    if (a.lse && g == 0 && iok) a.lse[(tok0 + i) * a.H + hd] = (l > 0.0f) ? m + logf(l) : -INFINITY;
+    const Row8 qx = split8(qr[qb][0], qr[qb][1]);
+    attn_qblock<NB, 2>(
+        a, qb, hd, tok0, L, c, g, my_pad, Ob, D, [&](int kb) { return dot16_x3(kx[kb], qx); },
+        [&](int kb, int et) { return split_col4(vr[kb][et]); });
   }
 }
 
@@ -777,11 +843,7 @@ __device__ __forceinline__ void mha_fwd_x3b64_seq(const FwdArgs& a, int hd, int6
   const int c = lane & 15, g = lane >> 4;
   const int D = a.H * DH;
   const int64_t ld = 3 * (int64_t)D;
-  const uintptr_t bp = (uintptr_t)(a.qkv + tok0 * ld);
-  const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-  const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * ld * 4));
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
+  const auto rs = seq_rsrc(a.qkv + tok0 * ld, (unsigned)(L * ld * 4));
   u32x4 qr[NB][2][2], kr[NB][2][2];
   unsigned vr[NB][4][4];
 #pragma unroll
@@ -801,109 +863,34 @@ __device__ __forceinline__ void mha_fwd_x3b64_seq(const FwdArgs& a, int hd, int6
         vr[bb][et][t] = __builtin_amdgcn_raw_buffer_load_b32(
             rs, (unsigned)(((16 * bb + 4 * g + t) * ld + 2 * D + hd * DH + 16 * et + c) * 4), 0, 0);
   }
-  const int my_pad = (lane < L) ? (a.kpad ? (int)a.kpad[tok0 + lane] : 0) : 1;
+  const int my_pad = (lane < L) ? key_pad(a.kpad, tok0 + lane) : 1;
   float* Ob = a.out + tok0 * D + hd * DH;
 #pragma unroll
   for (int qb = 0; qb < NB; ++qb) {
-    const int i = 16 * qb + c;  // query of this lane's score column
-    const bool iok = i < L;
-    const Row8 qa = split_row8(qr[qb][0][0], qr[qb][0][1]), qc = split_row8(qr[qb][1][0], qr[qb][1][1]);
-    const int kb_end = a.causal ? qb : NB - 1;
-    f32x4 sv[NB];
-    float m = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        const f32x4 s0 = dot16_x3(split_row8(kr[kb][0][0], kr[kb][0][1]), qa);  // S^T: [key][query i]
-        const f32x4 s1 = dot16_x3(split_row8(kr[kb][1][0], kr[kb][1][1]), qc);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = 16 * kb + 4 * g + r;
-          const int jpad = __shfl(my_pad, j & 63, 64);
-          const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i);
-          sv[kb][r] = allowed ? (s0[r] + s1[r]) * a.scale : -INFINITY;
-          m = fmaxf(m, sv[kb][r]);
-        }
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = (sv[kb][r] == -INFINITY) ? 0.0f : __expf(sv[kb][r] - m);
-          sv[kb][r] = pv;
-          l += pv;
-        }
-      }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = (l > 0.0f) ? 1.0f / l : 0.0f;
-    f32x4 o[4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const uint64_t rowidx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        float pr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pr[r] = a.drop.apply(sv[kb][r] * inv, rowidx + 16 * kb + 4 * g + r);
-        const Col4 pa = split4(pr);
-#pragma unroll
-        for (int et = 0; et < 4; ++et) {
-          const float vf[4] = {__uint_as_float(vr[kb][et][0]), __uint_as_float(vr[kb][et][1]),
-                               __uint_as_float(vr[kb][et][2]), __uint_as_float(vr[kb][et][3])};
-          o[et] = sum16_x3(pa, split4(vf), o[et]);
-        }
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * qb + 4 * g + r;
-      if (row < L) {
-#pragma unroll
-        for (int et = 0; et < 4; ++et) Ob[(int64_t)row * D + 16 * et + c] = o[et][r];
-      }
-    }
-    if (a.lse && g == 0 && iok) a.lse[(tok0 + i) * a.H + hd] = (l > 0.0f) ? m + logf(l) : -INFINITY;
+    const Row8 qa = split8(qr[qb][0][0], qr[qb][0][1]), qc = split8(qr[qb][1][0], qr[qb][1][1]);
+    attn_qblock<NB, 4>(
+        a, qb, hd, tok0, L, c, g, my_pad, Ob, D,
+        [&](int kb) {  // K is split per pair: kept split across the query loop it does not fit the registers
+          return dot16_x3(split8(kr[kb][0][0], kr[kb][0][1]), qa) + dot16_x3(split8(kr[kb][1][0], kr[kb][1][1]), qc);
+        },
+        [&](int kb, int et) { return split_col4(vr[kb][et]); });
   }
 }
 
 __global__ __launch_bounds__(256) void mha_fwd_x3b64_k(FwdArgs a) {
   const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = __builtin_amdgcn_readfirstlane((L + 15) >> 4);
-  if (nb == 1) mha_fwd_x3b64_seq<1>(a, hd, tok0, L, lane);
-  else if (nb == 2) mha_fwd_x3b64_seq<2>(a, hd, tok0, L, lane);
-  else if (nb == 3) mha_fwd_x3b64_seq<3>(a, hd, tok0, L, lane);
-  else mha_fwd_x3b64_seq<4>(a, hd, tok0, L, lane);
+  wave_unit(a, wave_id(), [&](int hd, int64_t tok0, int L) {
+    for_blocks(L, [&](auto NB) { mha_fwd_x3b64_seq<decltype(NB)::value>(a, hd, tok0, L, lane); });
+  });
 }
 
 // three waves per SIMD (168 VGPRs, no spills; the default allocation took 176 and ran two): 166.6 ->
 // 136.7 us on the headline tower's first layer (round 6, tools/tower_micro.py under rocprofv3)
 __global__ __launch_bounds__(256, 3) void mha_fwd_x3b_k(FwdArgs a) {
   const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = __builtin_amdgcn_readfirstlane((L + 15) >> 4);
-  if (nb == 1) mha_fwd_x3b_seq<1>(a, hd, tok0, L, lane);
-  else if (nb == 2) mha_fwd_x3b_seq<2>(a, hd, tok0, L, lane);
-  else if (nb == 3) mha_fwd_x3b_seq<3>(a, hd, tok0, L, lane);
-  else mha_fwd_x3b_seq<4>(a, hd, tok0, L, lane);
+  wave_unit(a, wave_id(), [&](int hd, int64_t tok0, int L) {
+    for_blocks(L, [&](auto NB) { mha_fwd_x3b_seq<decltype(NB)::value>(a, hd, tok0, L, lane); });
+  });
 }
 
 // ---- bf16x3 backward, software-pipelined ----------------------------------------------------
@@ -913,13 +900,6 @@ __global__ __launch_bounds__(256, 3) void mha_fwd_x3b_k(FwdArgs a) {
 // loads over the sequence's rows: rows past L, and the pair after the last, read as zero by the
 // range check, so no load is predicated) while pair n computes, in two ping-pong register sets
 // so that no in-flight load is copied (loading per pair waits one memory latency each).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t seq_rsrc(const void* base, unsigned bytes) {
-  const uintptr_t bp = (uintptr_t)base;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)bp);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)hi << 32) | lo), 0,
-                                           (int)__builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 struct RawRow {  // dims 8g .. 8g+7 of one token row, as loaded
   u32x4 x0, x1;
 };
@@ -937,10 +917,6 @@ __device__ __forceinline__ void load_rawcols(__amdgpu_buffer_rsrc_t rs, int row0
     for (int t = 0; t < 4; ++t)
       v[et][t] = __builtin_amdgcn_raw_buffer_load_b32(rs, (unsigned)(((row0 + t) * ld + col + 16 * et) * 4), 0, 0);
 }
-__device__ __forceinline__ Col4 split_col4(const unsigned (&v)[4]) {
-  const float f[4] = {__uint_as_float(v[0]), __uint_as_float(v[1]), __uint_as_float(v[2]), __uint_as_float(v[3])};
-  return split4(f);
-}
 struct Pair1 {  // pass 1 operands: key block rows (K, V), query block rows (Q, dO) and columns
   RawRow k, v, q, d;
   unsigned qc[2][4], dc[2][4];
@@ -950,122 +926,133 @@ struct Pair2 {  // pass 2 operands: query block rows (Q, dO), key block rows (K,
   unsigned kc[2][4];
 };
 
-__global__ __launch_bounds__(256) void mha_bwd_x3p_k(BwdArgs a) {
+// mha_bwd_x3s_k's stash of dS tiles, [16 query rows][16 key columns] per causal pair
+constexpr int kStashLd = 20;     // tile row stride (floats): conflict-free writes, aligned b128 reads
+constexpr int kStashPairs = 10;  // causal pairs kb <= qb < 4
+__device__ __forceinline__ int stash_slot(int kb, int qb) { return (qb * (qb + 1) >> 1) + kb; }
+
+struct BwdX3 {  // this wave's unit as pass 1 leaves it to pass 2
+  int hd, L, nb, D, ld, cq, ck, cv;  // cq, ck, cv: column offsets of the head in a qkv row
+  int64_t tok0;
+  __amdgpu_buffer_rsrc_t rq, rd;  // over the sequence's qkv and dout rows
+  float sc, my_lse, my_delta;     // token t < L on lane t: lse_t, delta_t = dO_t . O_t, key pad
+  int my_pad;
+};
+
+// The front half of both bf16x3 backwards: the unit, its token statistics, and pass 1 = pairs
+// (kb, qb >= kb causal, every qb otherwise) in kb-major order with key j = 16kb + c on the score
+// columns: S, dP, the softmax gradient, dK and dV (stored when a key block is done). STASH: each pair's
+// dS tile also goes to the wave's `stash` in LDS.
+template <bool STASH>
+__device__ __forceinline__ void bwd_x3_pass1(const BwdArgs& a, int hd, int64_t tok0, int L,
+                                             float (*stash)[16 * kStashLd], BwdX3& u) {
   constexpr int DH = 32;
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
   const int D = a.H * DH;
   const int ld = 3 * D;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = __builtin_amdgcn_readfirstlane((L + 15) >> 4);
+  const int nb = blocks16(L);
   const auto rq = seq_rsrc(a.qkv + tok0 * ld, (unsigned)(L * ld * 4));
   const auto rd = seq_rsrc(a.dout + tok0 * D, (unsigned)(L * D * 4));
   const float sc = a.scale;
-  const int cq = hd * DH, ck = D + hd * DH, cv = 2 * D + hd * DH;  // column offsets in a qkv row
-
-  // per-token softmax statistics (token t < L on lane t): lse_t, delta_t = dO_t . O_t, key pad
+  const int cq = hd * DH, ck = D + hd * DH, cv = 2 * D + hd * DH;
   float my_lse = -INFINITY, my_delta = 0.0f;
   int my_pad = 1;
-  if (lane < L) {
-    my_lse = a.lse[(tok0 + lane) * a.H + hd];
-    const float4* op = reinterpret_cast<const float4*>(a.out + (tok0 + lane) * D + hd * DH);
-    const float4* gp = reinterpret_cast<const float4*>(a.dout + (tok0 + lane) * D + hd * DH);
-    float d = 0.0f;
-#pragma unroll
-    for (int t = 0; t < DH / 4; ++t) {
-      const float4 x = op[t], y = gp[t];
-      d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    my_delta = d;
-    my_pad = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
-  }
-  auto grad_elem = [&](int i, int j, float s, float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
-    pd_out = 0.0f;
-    if (!allowed) return 0.0f;
-    const float p = __expf(s * sc - lse_i);
-    float pd = p, dpd = dp;
-    if (a.drop.active()) {
-      const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-      const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-      pd = keep ? p * a.drop.scale : 0.0f;
-      dpd = keep ? dp * a.drop.scale : 0.0f;
-    }
-    pd_out = pd;
-    return p * (dpd - delta_i) * sc;
-  };
+  if (lane < L) token_stats<DH>(a, tok0 + lane, hd, my_lse, my_delta, my_pad);
 
-  // ---- pass 1: pairs (kb, qb >= kb) in kb-major order; key j = 16kb + c on the score columns ----
-  {
-    auto load1 = [&](Pair1& P, int kb, int qb) {
-      const int j = 16 * kb + c, iq = 16 * qb + c;
-      P.k = load_rawrow(rq, (unsigned)((j * ld + ck + 8 * g) * 4));
-      P.v = load_rawrow(rq, (unsigned)((j * ld + cv + 8 * g) * 4));
-      P.q = load_rawrow(rq, (unsigned)((iq * ld + cq + 8 * g) * 4));
-      P.d = load_rawrow(rd, (unsigned)((iq * D + hd * DH + 8 * g) * 4));
-      load_rawcols(rq, 16 * qb + 4 * g, ld, cq + c, P.qc);
-      load_rawcols(rd, 16 * qb + 4 * g, D, hd * DH + c, P.dc);
-    };
-    f32x4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    int kb = 0, qb = 0;
-    // one pair: prefetch the next one into `fill`, compute this one from `use`; false when done
-    auto step = [&](const Pair1& use, Pair1& fill) -> bool {
-      int nkb = kb, nqb = qb + 1;
-      if (nqb >= nb) { nkb = kb + 1; nqb = a.causal ? nkb : 0; }
-      load1(fill, nkb, nqb);
-      const int j = 16 * kb + c;
-      const bool jok = j < L;
-      const int jpad = __shfl(my_pad, j & 63, 64);
-      const f32x4 S = dot16_x3(split_row8(use.q.x0, use.q.x1), split_row8(use.k.x0, use.k.x1));
-      const f32x4 dP = dot16_x3(split_row8(use.d.x0, use.d.x1), split_row8(use.v.x0, use.v.x1));
-      float ds[4], pd[4];
+  auto load1 = [&](Pair1& P, int kb, int qb) {
+    const int j = 16 * kb + c, iq = 16 * qb + c;
+    P.k = load_rawrow(rq, (unsigned)((j * ld + ck + 8 * g) * 4));
+    P.v = load_rawrow(rq, (unsigned)((j * ld + cv + 8 * g) * 4));
+    P.q = load_rawrow(rq, (unsigned)((iq * ld + cq + 8 * g) * 4));
+    P.d = load_rawrow(rd, (unsigned)((iq * D + hd * DH + 8 * g) * 4));
+    load_rawcols(rq, 16 * qb + 4 * g, ld, cq + c, P.qc);
+    load_rawcols(rd, 16 * qb + 4 * g, D, hd * DH + c, P.dc);
+  };
+  f32x4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  f32x4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+  int kb = 0, qb = 0;
+  // one pair: prefetch the next one into `fill`, compute this one from `use`; false when done
+  auto step = [&](const Pair1& use, Pair1& fill) -> bool {
+    int nkb = kb, nqb = qb + 1;
+    if (nqb >= nb) { nkb = kb + 1; nqb = a.causal ? nkb : 0; }
+    load1(fill, nkb, nqb);
+    const int j = 16 * kb + c;
+    const bool jok = j < L;
+    const int jpad = __shfl(my_pad, j & 63, 64);
+    const f32x4 S = dot16_x3(split8(use.q.x0, use.q.x1), split8(use.k.x0, use.k.x1));
+    const f32x4 dP = dot16_x3(split8(use.d.x0, use.d.x1), split8(use.v.x0, use.v.x1));
+    float ds[4], pd[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = 16 * qb + 4 * g + r;
+      const float lse_i = __shfl(my_lse, i & 63, 64);
+      const float del_i = __shfl(my_delta, i & 63, 64);
+      const bool allowed = jok && i < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
+      ds[r] = grad_elem(a, sc, tok0, hd, i, j, S[r], dP[r], lse_i, del_i, allowed, pd[r]);
+    }
+    if (STASH) {  // dS[16qb + 4g + r][16kb + c] -> tile row 4g + r, column c (read transposed in pass 2)
+      float* t = stash[stash_slot(kb, qb)];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) t[(4 * g + r) * kStashLd + c] = ds[r];
+    }
+    const Col4 pa = split4(pd), sa = split4(ds);
+#pragma unroll
+    for (int et = 0; et < 2; ++et) {
+      dv[et] = sum16_x3(pa, split_col4(use.dc[et]), dv[et]);  // dV[j][e]
+      dk[et] = sum16_x3(sa, split_col4(use.qc[et]), dk[et]);  // dK[j][e]
+    }
+    if (nkb != kb) {
+      float* dKb = a.dqkv + tok0 * ld + ck;
+      float* dVb = a.dqkv + tok0 * ld + cv;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int i = 16 * qb + 4 * g + r;
-        const float lse_i = __shfl(my_lse, i & 63, 64);
-        const float del_i = __shfl(my_delta, i & 63, 64);
-        const bool allowed = jok && i < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
-        ds[r] = grad_elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd[r]);
-      }
-      const Col4 pa = split4(pd), sa = split4(ds);
+        const int row = 16 * kb + 4 * g + r;
+        if (row < L) {
 #pragma unroll
-      for (int et = 0; et < 2; ++et) {
-        dv[et] = sum16_x3(pa, split_col4(use.dc[et]), dv[et]);  // dV[j][e]
-        dk[et] = sum16_x3(sa, split_col4(use.qc[et]), dk[et]);  // dK[j][e]
-      }
-      if (nkb != kb) {
-        float* dKb = a.dqkv + tok0 * ld + ck;
-        float* dVb = a.dqkv + tok0 * ld + cv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * kb + 4 * g + r;
-          if (row < L) {
-#pragma unroll
-            for (int et = 0; et < 2; ++et) {
-              dKb[(int64_t)row * ld + 16 * et + c] = dk[et][r];
-              dVb[(int64_t)row * ld + 16 * et + c] = dv[et][r];
-            }
+          for (int et = 0; et < 2; ++et) {
+            dKb[(int64_t)row * ld + 16 * et + c] = dk[et][r];
+            dVb[(int64_t)row * ld + 16 * et + c] = dv[et][r];
           }
         }
-#pragma unroll
-        for (int et = 0; et < 2; ++et) dk[et] = dv[et] = f32x4{0.f, 0.f, 0.f, 0.f};
       }
-      kb = nkb;
-      qb = nqb;
-      return kb < nb;
-    };
-    Pair1 p0, p1;
-    load1(p0, 0, 0);
-    for (;;) {
-      if (!step(p0, p1)) break;
-      if (!step(p1, p0)) break;
+#pragma unroll
+      for (int et = 0; et < 2; ++et) dk[et] = dv[et] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    kb = nkb;
+    qb = nqb;
+    return kb < nb;
+  };
+  Pair1 p0, p1;
+  load1(p0, 0, 0);
+  for (;;) {
+    if (!step(p0, p1)) break;
+    if (!step(p1, p0)) break;
+  }
+  u = BwdX3{hd, L, nb, D, ld, cq, ck, cv, tok0, rq, rd, sc, my_lse, my_delta, my_pad};
+}
+
+// rows 16qb .. 16qb+15 of dQ from the accumulators of a finished query block, which start over
+__device__ __forceinline__ void store_dq(const BwdArgs& a, const BwdX3& u, int qb, int c, int g, f32x4 (&dq)[2]) {
+  float* dQb = a.dqkv + u.tok0 * u.ld + u.cq;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = 16 * qb + 4 * g + r;
+    if (row < u.L) {
+      dQb[(int64_t)row * u.ld + c] = dq[0][r];
+      dQb[(int64_t)row * u.ld + 16 + c] = dq[1][r];
     }
   }
+  dq[0] = dq[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// Non-causal backward: pass 2 recomputes S, dP and the softmax gradient with the query on the score columns.
+__device__ __forceinline__ void mha_bwd_x3p_seq(const BwdArgs& a, int hd, int64_t tok0, int L) {
+  constexpr int DH = 32;
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  BwdX3 u;
+  bwd_x3_pass1<false>(a, hd, tok0, L, nullptr, u);
+  const int nb = u.nb, D = u.D, ld = u.ld, cq = u.cq, ck = u.ck, cv = u.cv;
+  const auto rq = u.rq, rd = u.rd;
 
   // ---- pass 2: pairs (qb, kb <= qb) in qb-major order; query i = 16qb + c on the score columns ----
   {
@@ -1085,34 +1072,23 @@ __global__ __launch_bounds__(256) void mha_bwd_x3p_k(BwdArgs a) {
       load2(fill, nqb, nkb);
       const int i = 16 * qb + c;
       const bool iok = i < L;
-      const float lse_i = __shfl(my_lse, i & 63, 64);
-      const float del_i = __shfl(my_delta, i & 63, 64);
-      const f32x4 St = dot16_x3(split_row8(use.k.x0, use.k.x1), split_row8(use.q.x0, use.q.x1));
-      const f32x4 dPt = dot16_x3(split_row8(use.v.x0, use.v.x1), split_row8(use.d.x0, use.d.x1));
+      const float lse_i = __shfl(u.my_lse, i & 63, 64);
+      const float del_i = __shfl(u.my_delta, i & 63, 64);
+      const f32x4 St = dot16_x3(split8(use.k.x0, use.k.x1), split8(use.q.x0, use.q.x1));
+      const f32x4 dPt = dot16_x3(split8(use.v.x0, use.v.x1), split8(use.d.x0, use.d.x1));
       float ds[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int j = 16 * kb + 4 * g + r;
-        const int jpad = __shfl(my_pad, j & 63, 64);
+        const int jpad = __shfl(u.my_pad, j & 63, 64);
         const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
         float pd;
-        ds[r] = grad_elem(i, j, St[r], dPt[r], lse_i, del_i, allowed, pd);
+        ds[r] = grad_elem(a, u.sc, u.tok0, hd, i, j, St[r], dPt[r], lse_i, del_i, allowed, pd);
       }
       const Col4 sa = split4(ds);
 #pragma unroll
       for (int et = 0; et < 2; ++et) dq[et] = sum16_x3(sa, split_col4(use.kc[et]), dq[et]);  // dQ[i][e]
-      if (nqb != qb) {
-        float* dQb = a.dqkv + tok0 * ld + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * qb + 4 * g + r;
-          if (row < L) {
-            dQb[(int64_t)row * ld + c] = dq[0][r];
-            dQb[(int64_t)row * ld + 16 + c] = dq[1][r];
-          }
-        }
-        dq[0] = dq[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      if (nqb != qb) store_dq(a, u, qb, c, g, dq);
       qb = nqb;
       kb = nkb;
       return qb < nb;
@@ -1126,6 +1102,9 @@ __global__ __launch_bounds__(256) void mha_bwd_x3p_k(BwdArgs a) {
   }
 }
 
+__global__ __launch_bounds__(256) void mha_bwd_x3p_k(BwdArgs a) {
+  wave_unit(a, wave_id(), [&](int hd, int64_t tok0, int L) { mha_bwd_x3p_seq(a, hd, tok0, L); });
+}
 
 // ---- bf16x3 backward, causal, one dS evaluation per pair ---------------------------------------
 // mha_bwd_x3p_k's pass 1 (key block on the lanes: S, dP, the softmax gradient dS and the dropped-out
@@ -1134,137 +1113,17 @@ __global__ __launch_bounds__(256) void mha_bwd_x3p_k(BwdArgs a) {
 // registers allow). Pass 2 then reads the tiles transposed and forms dQ = dS K with K's columns as
 // its only loads, instead of recomputing S and dP (6 MFMAs), the exp / dropout hash of 16
 // elements and four row splits per pair.
-constexpr int kStashLd = 20;     // tile row stride (floats): conflict-free writes, aligned b128 reads
-constexpr int kStashPairs = 10;  // causal pairs kb <= qb < 4
-__device__ __forceinline__ int stash_slot(int kb, int qb) { return (qb * (qb + 1) >> 1) + kb; }
-
+//
 // Measured and not kept (round 6): a second instance for sequences of <= 32 tokens with a 3-pair stash
 // (15 KB of LDS) at four waves per SIMD: 128 VGPRs with 49 spilled, 319 + 245 us against 367 us for this
 // kernel alone on the headline tower's first layer.
-__global__ __launch_bounds__(256) void mha_bwd_x3s_k(BwdArgs a) {
-  // dS tiles of this wave's (kb, qb <= ... ) pairs, [16 query rows][16 key columns] at row stride 20
-  __shared__ __attribute__((aligned(16))) float sDS[4][kStashPairs][16 * kStashLd];
-  constexpr int DH = 32;
+__device__ __forceinline__ void mha_bwd_x3s_seq(const BwdArgs& a, int hd, int64_t tok0, int L,
+                                                float (*stash)[16 * kStashLd]) {
   const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t unit = (int64_t)blockIdx.x * 4 + wave;
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int D = a.H * DH;
-  const int ld = 3 * D;
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = __builtin_amdgcn_readfirstlane((L + 15) >> 4);
-  const auto rq = seq_rsrc(a.qkv + tok0 * ld, (unsigned)(L * ld * 4));
-  const auto rd = seq_rsrc(a.dout + tok0 * D, (unsigned)(L * D * 4));
-  const float sc = a.scale;
-  const int cq = hd * DH, ck = D + hd * DH, cv = 2 * D + hd * DH;  // column offsets in a qkv row
-
-  // per-token softmax statistics (token t < L on lane t): lse_t, delta_t = dO_t . O_t, key pad
-  float my_lse = -INFINITY, my_delta = 0.0f;
-  int my_pad = 1;
-  if (lane < L) {
-    my_lse = a.lse[(tok0 + lane) * a.H + hd];
-    const float4* op = reinterpret_cast<const float4*>(a.out + (tok0 + lane) * D + hd * DH);
-    const float4* gp = reinterpret_cast<const float4*>(a.dout + (tok0 + lane) * D + hd * DH);
-    float d = 0.0f;
-#pragma unroll
-    for (int t = 0; t < DH / 4; ++t) {
-      const float4 x = op[t], y = gp[t];
-      d += x.x * y.x + x.y * y.y + x.z * y.z + x.w * y.w;
-    }
-    my_delta = d;
-    my_pad = a.kpad ? (int)a.kpad[tok0 + lane] : 0;
-  }
-  auto grad_elem = [&](int i, int j, float s, float dp, float lse_i, float delta_i, bool allowed, float& pd_out) {
-    pd_out = 0.0f;
-    if (!allowed) return 0.0f;
-    const float p = __expf(s * sc - lse_i);
-    float pd = p, dpd = dp;
-    if (a.drop.active()) {
-      const uint64_t idx = ((uint64_t)(tok0 + i) * a.H + hd) * kLMax + j;
-      const bool keep = rsx::hash_u32(a.drop.seed, idx) >= a.drop.thresh;
-      pd = keep ? p * a.drop.scale : 0.0f;
-      dpd = keep ? dp * a.drop.scale : 0.0f;
-    }
-    pd_out = pd;
-    return p * (dpd - delta_i) * sc;
-  };
-
-  // ---- pass 1: pairs (kb, qb >= kb) in kb-major order; key j = 16kb + c on the score columns ----
-  {
-    auto load1 = [&](Pair1& P, int kb, int qb) {
-      const int j = 16 * kb + c, iq = 16 * qb + c;
-      P.k = load_rawrow(rq, (unsigned)((j * ld + ck + 8 * g) * 4));
-      P.v = load_rawrow(rq, (unsigned)((j * ld + cv + 8 * g) * 4));
-      P.q = load_rawrow(rq, (unsigned)((iq * ld + cq + 8 * g) * 4));
-      P.d = load_rawrow(rd, (unsigned)((iq * D + hd * DH + 8 * g) * 4));
-      load_rawcols(rq, 16 * qb + 4 * g, ld, cq + c, P.qc);
-      load_rawcols(rd, 16 * qb + 4 * g, D, hd * DH + c, P.dc);
-    };
-    f32x4 dk[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    f32x4 dv[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    int kb = 0, qb = 0;
-    // one pair: prefetch the next one into `fill`, compute this one from `use`; false when done
-    auto step = [&](const Pair1& use, Pair1& fill) -> bool {
-      int nkb = kb, nqb = qb + 1;
-      if (nqb >= nb) { nkb = kb + 1; nqb = a.causal ? nkb : 0; }
-      load1(fill, nkb, nqb);
-      const int j = 16 * kb + c;
-      const bool jok = j < L;
-      const int jpad = __shfl(my_pad, j & 63, 64);
-      const f32x4 S = dot16_x3(split_row8(use.q.x0, use.q.x1), split_row8(use.k.x0, use.k.x1));
-      const f32x4 dP = dot16_x3(split_row8(use.d.x0, use.d.x1), split_row8(use.v.x0, use.v.x1));
-      float ds[4], pd[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = 16 * qb + 4 * g + r;
-        const float lse_i = __shfl(my_lse, i & 63, 64);
-        const float del_i = __shfl(my_delta, i & 63, 64);
-        const bool allowed = jok && i < L && !jpad && (!a.causal || j <= i) && lse_i != -INFINITY;
-        ds[r] = grad_elem(i, j, S[r], dP[r], lse_i, del_i, allowed, pd[r]);
-      }
-      {  // dS[16qb + 4g + r][16kb + c] -> tile row 4g + r, column c (read transposed in pass 2)
-        float* t = sDS[wave][stash_slot(kb, qb)];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) t[(4 * g + r) * kStashLd + c] = ds[r];
-      }
-      const Col4 pa = split4(pd), sa = split4(ds);
-#pragma unroll
-      for (int et = 0; et < 2; ++et) {
-        dv[et] = sum16_x3(pa, split_col4(use.dc[et]), dv[et]);  // dV[j][e]
-        dk[et] = sum16_x3(sa, split_col4(use.qc[et]), dk[et]);  // dK[j][e]
-      }
-      if (nkb != kb) {
-        float* dKb = a.dqkv + tok0 * ld + ck;
-        float* dVb = a.dqkv + tok0 * ld + cv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * kb + 4 * g + r;
-          if (row < L) {
-#pragma unroll
-            for (int et = 0; et < 2; ++et) {
-              dKb[(int64_t)row * ld + 16 * et + c] = dk[et][r];
-              dVb[(int64_t)row * ld + 16 * et + c] = dv[et][r];
-            }
-          }
-        }
-#pragma unroll
-        for (int et = 0; et < 2; ++et) dk[et] = dv[et] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      kb = nkb;
-      qb = nqb;
-      return kb < nb;
-    };
-    Pair1 p0, p1;
-    load1(p0, 0, 0);
-    for (;;) {
-      if (!step(p0, p1)) break;
-      if (!step(p1, p0)) break;
-    }
-  }
+  BwdX3 u;
+  bwd_x3_pass1<true>(a, hd, tok0, L, stash, u);
+  const int nb = u.nb, ld = u.ld, ck = u.ck;
+  const auto rq = u.rq;
 
   // pass 2 reads dS entries other lanes of this wave wrote in pass 1: order the wave's LDS
   // writes before those reads explicitly (the per-wave stash is never touched by other waves)
@@ -1282,23 +1141,12 @@ __global__ __launch_bounds__(256) void mha_bwd_x3s_k(BwdArgs a) {
       int nqb = qb, nkb = kb + 1;
       if (nkb > qb) { nqb = qb + 1; nkb = 0; }
       load_rawcols(rq, 16 * nkb + 4 * g, ld, ck + c, fill);
-      const float4 t = *reinterpret_cast<const float4*>(&sDS[wave][stash_slot(kb, qb)][c * kStashLd + 4 * g]);
+      const float4 t = *reinterpret_cast<const float4*>(&stash[stash_slot(kb, qb)][c * kStashLd + 4 * g]);
       const float ds[4] = {t.x, t.y, t.z, t.w};
       const Col4 sa = split4(ds);
 #pragma unroll
       for (int et = 0; et < 2; ++et) dq[et] = sum16_x3(sa, split_col4(use[et]), dq[et]);  // dQ[i][e]
-      if (nqb != qb) {
-        float* dQb = a.dqkv + tok0 * ld + cq;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = 16 * qb + 4 * g + r;
-          if (row < L) {
-            dQb[(int64_t)row * ld + c] = dq[0][r];
-            dQb[(int64_t)row * ld + 16 + c] = dq[1][r];
-          }
-        }
-        dq[0] = dq[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      if (nqb != qb) store_dq(a, u, qb, c, g, dq);
       qb = nqb;
       kb = nkb;
       return qb < nb;
@@ -1312,6 +1160,12 @@ __global__ __launch_bounds__(256) void mha_bwd_x3s_k(BwdArgs a) {
   }
 }
 
+__global__ __launch_bounds__(256) void mha_bwd_x3s_k(BwdArgs a) {
+  // dS tiles of each wave's (kb, qb <= ... ) pairs, [16 query rows][16 key columns] at row stride 20
+  __shared__ __attribute__((aligned(16))) float sDS[4][kStashPairs][16 * kStashLd];
+  const int wave = wave_id();
+  wave_unit(a, wave, [&](int hd, int64_t tok0, int L) { mha_bwd_x3s_seq(a, hd, tok0, L, sDS[wave]); });
+}
 
 
 // ---- fused in-projection + attention forward (head dim 32, bf16x3) -------------------------
@@ -1344,30 +1198,11 @@ struct QArgs {
   rsx::Dropout drop;
 };
 
-__device__ __forceinline__ f32x4 dot16_x3_acc(const Row8& a, const Row8& b, f32x4 acc) {
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.lo, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.lo, b.hi, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.hi, b.hi, acc, 0, 0, 0);
-  return acc;
-}
-
-__device__ __forceinline__ Row8 split_f8(const float (&f)[8]) {
-  Row8 r;
-  rsx::split_x3(f, r.hi, r.lo);
-  return r;
-}
-
 template <int NB, int KS>
 __device__ __forceinline__ void mha_qkv_fwd_x3_seq(const QArgs& a, int hd, int64_t tok0, int L, int lane) {
   constexpr int DH = 32, D = 32 * KS;
   const int c = lane & 15, g = lane >> 4;
-  const int H = a.H;
-  // h rows of the sequence through one buffer resource (rows >= L read as zero)
-  const uintptr_t bp = (uintptr_t)(a.x + tok0 * D);
-  const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)bp), bhi = __builtin_amdgcn_readfirstlane((unsigned)(bp >> 32));
-  const unsigned nbytes = __builtin_amdgcn_readfirstlane((unsigned)(L * D * 4));
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(((uintptr_t)bhi << 32) | blo), 0, (int)nbytes, 0x00020000);
+  const auto rs = seq_rsrc(a.x + tok0 * D, (unsigned)(L * D * 4));  // h rows of the sequence
   u32x4 xr[KS][NB][2];
 #pragma unroll
   for (int s = 0; s < KS; ++s)
@@ -1397,16 +1232,16 @@ __device__ __forceinline__ void mha_qkv_fwd_x3_seq(const QArgs& a, int hd, int64
         const float4* p = reinterpret_cast<const float4*>(a.w + (int64_t)(pt * D + hd * DH + 16 * dt + c) * D + 32 * s + 8 * g);
         const float4 v0 = p[0], v1 = p[1];
         const float f[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        wf[pt][dt] = split_f8(f);
+        wf[pt][dt] = split8(f);
       }
 #pragma unroll
     for (int bb = 0; bb < NB; ++bb) {
-      const Row8 xx = split_row8(xr[s][bb][0], xr[s][bb][1]);
+      const Row8 xx = split8(xr[s][bb][0], xr[s][bb][1]);
 #pragma unroll
       for (int dt = 0; dt < 2; ++dt) {
-        qa[bb][dt] = dot16_x3_acc(wf[0][dt], xx, qa[bb][dt]);  // [dim 4g+r][token c]
-        ka[bb][dt] = dot16_x3_acc(wf[1][dt], xx, ka[bb][dt]);
-        va[bb][dt] = dot16_x3_acc(xx, wf[2][dt], va[bb][dt]);  // [token 4g+r][dim c]
+        qa[bb][dt] = dot16_x3(wf[0][dt], xx, qa[bb][dt]);  // [dim 4g+r][token c]
+        ka[bb][dt] = dot16_x3(wf[1][dt], xx, ka[bb][dt]);
+        va[bb][dt] = dot16_x3(xx, wf[2][dt], va[bb][dt]);  // [token 4g+r][dim c]
       }
     }
   }
@@ -1433,8 +1268,8 @@ __device__ __forceinline__ void mha_qkv_fwd_x3_seq(const QArgs& a, int hd, int64
         qf[4 * dt + r] = qa[bb][dt][r] + bq[dt][r];
         kf[4 * dt + r] = ka[bb][dt][r] + bk[dt][r];
       }
-    qxs[bb] = split_f8(qf);
-    kx[bb] = split_f8(kf);
+    qxs[bb] = split8(qf);
+    kx[bb] = split8(kf);
     float vf[2][4];
 #pragma unroll
     for (int et = 0; et < 2; ++et)
@@ -1464,87 +1299,53 @@ __device__ __forceinline__ void mha_qkv_fwd_x3_seq(const QArgs& a, int hd, int64
       }
     }
   }
-  // ---- attention (mha_fwd_x3b_seq's masks, safe softmax, dropout hash, lse)
-  const int my_pad = (lane < L) ? (a.kpad ? (int)a.kpad[tok0 + lane] : 0) : 1;
+  // ---- attention, on the projections straight from registers
+  const int my_pad = (lane < L) ? key_pad(a.kpad, tok0 + lane) : 1;
   float* Ob = a.out + tok0 * D + hd * DH;
 #pragma unroll
-  for (int qb = 0; qb < NB; ++qb) {
-    const int i = 16 * qb + c;
-    const bool iok = i < L;
-    const int kb_end = a.causal ? qb : NB - 1;
-    f32x4 sv[NB];
-    float m = -INFINITY;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        sv[kb] = dot16_x3(kx[kb], qxs[qb]);  // S^T: [key 16kb+4g+r][query i]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int j = 16 * kb + 4 * g + r;
-          const int jpad = __shfl(my_pad, j & 63, 64);
-          const bool allowed = iok && j < L && !jpad && (!a.causal || j <= i);
-          sv[kb][r] = allowed ? sv[kb][r] * a.scale : -INFINITY;
-          m = fmaxf(m, sv[kb][r]);
-        }
-      }
-    }
-    m = fmaxf(m, __shfl_xor(m, 16, 64));
-    m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float l = 0.0f;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float pv = (sv[kb][r] == -INFINITY) ? 0.0f : __expf(sv[kb][r] - m);
-          sv[kb][r] = pv;
-          l += pv;
-        }
-      }
-    }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    const float inv = (l > 0.0f) ? 1.0f / l : 0.0f;
-    f32x4 o[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-    const uint64_t rowidx = ((uint64_t)(tok0 + i) * H + hd) * kLMax;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-      if (kb <= kb_end) {
-        float pr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) pr[r] = a.drop.apply(sv[kb][r] * inv, rowidx + 16 * kb + 4 * g + r);
-        const Col4 pa = split4(pr);
-#pragma unroll
-        for (int et = 0; et < 2; ++et) o[et] = sum16_x3(pa, vc[kb][et], o[et]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * qb + 4 * g + r;
-      if (row < L) {
-        Ob[(int64_t)row * D + c] = o[0][r];
-        Ob[(int64_t)row * D + 16 + c] = o[1][r];
-      }
-    }
-    if (a.lse && g == 0 && iok) a.lse[(tok0 + i) * H + hd] = (l > 0.0f) ? m + logf(l) : -INFINITY;
-  }
+  for (int qb = 0; qb < NB; ++qb)
+    attn_qblock<NB, 2>(
+        a, qb, hd, tok0, L, c, g, my_pad, Ob, D, [&](int kb) { return dot16_x3(kx[kb], qxs[qb]); },
+        [&](int kb, int et) { return vc[kb][et]; });
 }
 
 template <int KS>
 __global__ __launch_bounds__(256) void mha_qkv_fwd_x3_k(QArgs a) {
   const int lane = threadIdx.x & 63;
-  const int64_t unit = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (unit >= (int64_t)a.B * a.H) return;  // whole wave exits together
-  const int b = (int)(unit / a.H), hd = (int)(unit % a.H);
-  const int64_t tok0 = a.seg ? (int64_t)a.seg[b] : (int64_t)b * a.L;
-  int L = a.seg ? (a.seg[b + 1] - a.seg[b]) : a.L;
-  if (L > kLMax) L = kLMax;
-  if (L <= 0) return;
-  const int nb = __builtin_amdgcn_readfirstlane((L + 15) >> 4);
-  if (nb == 1) mha_qkv_fwd_x3_seq<1, KS>(a, hd, tok0, L, lane);
-  else if (nb == 2) mha_qkv_fwd_x3_seq<2, KS>(a, hd, tok0, L, lane);
-  else if (nb == 3) mha_qkv_fwd_x3_seq<3, KS>(a, hd, tok0, L, lane);
-  else mha_qkv_fwd_x3_seq<4, KS>(a, hd, tok0, L, lane);
+  wave_unit(a, wave_id(), [&](int hd, int64_t tok0, int L) {
+    for_blocks(L, [&](auto NB) { mha_qkv_fwd_x3_seq<decltype(NB)::value, KS>(a, hd, tok0, L, lane); });
+  });
+}
+
+// ---- host side: what the five entry points do alike ----
+// The first check an entry point's arguments fail, in the order every one of them checks, or nullptr.
+// The tensor and shape conditions and the shape message are the entry point's own (h_ok: true where it
+// does not check H).
+const char* bad_arg(bool tensors, int64_t L, bool shape_ok, const char* shape_msg, bool h_ok, float p_drop) {
+  if (!tensors) return "null tensor";
+  if (!(L >= 1 && L <= kLMax)) return "L must be in [1,64]";
+  if (!shape_ok) return shape_msg;
+  if (!h_ok) return "H must be >= 1";
+  if (!(p_drop >= 0.0f && p_drop < 1.0f)) return "p_drop must be in [0,1)";
+  return nullptr;
+}
+
+// the fields FwdArgs, BwdArgs and QArgs share
+template <class A>
+void fill_args(A& a, const uint8_t* key_pad, const int* seg_off, int64_t B, int64_t L, int64_t H, int64_t Dh,
+               int causal, float p_drop, uint64_t seed) {
+  a.kpad = key_pad; a.seg = seg_off;
+  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
+  a.scale = 1.0f / sqrtf((float)Dh);
+  a.drop = rsx::make_dropout(p_drop, seed);
+}
+
+// one unit of the B * H per `waves`-wave workgroup (1), or per wave of it (4)
+template <class A>
+void launch(void (*kernel)(A), int waves, const A& a, void* stream) {
+  const int64_t units = (int64_t)a.B * a.H;
+  const dim3 grid((unsigned)((units + waves - 1) / waves));
+  hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), 0, (hipStream_t)stream, a);
 }
 
 }  // namespace
@@ -1552,22 +1353,14 @@ __global__ __launch_bounds__(256) void mha_qkv_fwd_x3_k(QArgs a) {
 RSX_API int rsx_mha_fwd(const float* qkv, const uint8_t* key_pad, const int* seg_off, int64_t B, int64_t L,
                         int64_t H, int64_t Dh, int causal, float p_drop, uint64_t seed, float* out, float* lse,
                         void* stream) {
-  RSX_ARG(qkv && out, "null tensor");
-  RSX_ARG(L >= 1 && L <= kLMax, "L must be in [1,64]");
-  RSX_ARG(Dh == 16 || Dh == 32 || Dh == 64, "head dim must be 16, 32 or 64");
-  RSX_ARG(H >= 1, "H must be >= 1");
-  RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  const char* bad =
+      bad_arg(qkv && out, L, Dh == 16 || Dh == 32 || Dh == 64, "head dim must be 16, 32 or 64", H >= 1, p_drop);
+  RSX_ARG(!bad, bad);
   if (B == 0) return 0;
   FwdArgs a;
-  a.qkv = qkv; a.kpad = key_pad; a.seg = seg_off; a.out = out; a.lse = lse;
-  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
-  a.scale = 1.0f / sqrtf((float)Dh);
-  a.drop = rsx::make_dropout(p_drop, seed);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(B * H));
-  if (Dh == 16) hipLaunchKernelGGL(mha_fwd_k<16>, grid, dim3(64), 0, st, a);
-  else if (Dh == 32) hipLaunchKernelGGL(mha_fwd_k<32>, grid, dim3(64), 0, st, a);
-  else hipLaunchKernelGGL(mha_fwd_k<64>, grid, dim3(64), 0, st, a);
+  a.qkv = qkv; a.out = out; a.lse = lse;
+  fill_args(a, key_pad, seg_off, B, L, H, Dh, causal, p_drop, seed);
+  launch(Dh == 16 ? mha_fwd_k<16> : Dh == 32 ? mha_fwd_k<32> : mha_fwd_k<64>, 1, a, stream);
   RSX_LAUNCHED();
   return 0;
 }
@@ -1575,22 +1368,17 @@ RSX_API int rsx_mha_fwd(const float* qkv, const uint8_t* key_pad, const int* seg
 RSX_API int rsx_mha_bwd(const float* qkv, const uint8_t* key_pad, const int* seg_off, const float* out,
                         const float* lse, const float* dout, int64_t B, int64_t L, int64_t H, int64_t Dh, int causal,
                         float p_drop, uint64_t seed, float* dqkv, void* stream) {
-  RSX_ARG(qkv && out && lse && dout && dqkv, "null tensor");
-  RSX_ARG(L >= 1 && L <= kLMax, "L must be in [1,64]");
-  RSX_ARG(Dh == 16 || Dh == 32 || Dh == 64, "backward head dim must be 16, 32 or 64");
-  RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  const char* bad = bad_arg(qkv && out && lse && dout && dqkv, L, Dh == 16 || Dh == 32 || Dh == 64,
+                            "backward head dim must be 16, 32 or 64", true, p_drop);
+  RSX_ARG(!bad, bad);
   if (B == 0) return 0;
   BwdArgs a;
-  a.qkv = qkv; a.kpad = key_pad; a.seg = seg_off; a.out = out; a.lse = lse; a.dout = dout; a.dqkv = dqkv;
-  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
-  a.scale = 1.0f / sqrtf((float)Dh);
-  a.drop = rsx::make_dropout(p_drop, seed);
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 grid((unsigned)(B * H));
-  if (Dh == 16) hipLaunchKernelGGL(mha_bwd_k<16>, grid, dim3(64), 0, st, a);
-  else if (Dh == 64 && L <= 32) hipLaunchKernelGGL(mha_bwd64_k<32>, grid, dim3(64), 0, st, a);  // L: the longest sequence
-  else if (Dh == 64) hipLaunchKernelGGL(mha_bwd64_k<64>, grid, dim3(64), 0, st, a);
-  else hipLaunchKernelGGL(mha_bwd_mfma_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, st, a);
+  a.qkv = qkv; a.out = out; a.lse = lse; a.dout = dout; a.dqkv = dqkv;
+  fill_args(a, key_pad, seg_off, B, L, H, Dh, causal, p_drop, seed);
+  if (Dh == 16) launch(mha_bwd_k<16>, 1, a, stream);
+  else if (Dh == 64 && L <= 32) launch(mha_bwd64_k<32>, 1, a, stream);  // L: the longest sequence
+  else if (Dh == 64) launch(mha_bwd64_k<64>, 1, a, stream);
+  else launch(mha_bwd_mfma_k, 4, a, stream);
   RSX_LAUNCHED();
   return 0;
 }
@@ -1598,21 +1386,14 @@ RSX_API int rsx_mha_bwd(const float* qkv, const uint8_t* key_pad, const int* seg
 RSX_API int rsx_mha_fwd_x3(const float* qkv, const uint8_t* key_pad, const int* seg_off, int64_t B, int64_t L,
                            int64_t H, int64_t Dh, int causal, float p_drop, uint64_t seed, float* out, float* lse,
                            void* stream) {
-  RSX_ARG(qkv && out, "null tensor");
-  RSX_ARG(L >= 1 && L <= kLMax, "L must be in [1,64]");
-  RSX_ARG(Dh == 32 || Dh == 64, "bf16x3 attention forward head dim must be 32 or 64");
-  RSX_ARG(H >= 1, "H must be >= 1");
-  RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  const char* bad = bad_arg(qkv && out, L, Dh == 32 || Dh == 64, "bf16x3 attention forward head dim must be 32 or 64",
+                            H >= 1, p_drop);
+  RSX_ARG(!bad, bad);
   if (B == 0) return 0;
   FwdArgs a;
-  a.qkv = qkv; a.kpad = key_pad; a.seg = seg_off; a.out = out; a.lse = lse;
-  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
-  a.scale = 1.0f / sqrtf((float)Dh);
-  a.drop = rsx::make_dropout(p_drop, seed);
-  if (Dh == 64)
-    hipLaunchKernelGGL(mha_fwd_x3b64_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(mha_fwd_x3b_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  a.qkv = qkv; a.out = out; a.lse = lse;
+  fill_args(a, key_pad, seg_off, B, L, H, Dh, causal, p_drop, seed);
+  launch(Dh == 64 ? mha_fwd_x3b64_k : mha_fwd_x3b_k, 4, a, stream);
   RSX_LAUNCHED();
   return 0;
 }
@@ -1623,17 +1404,14 @@ RSX_API int rsx_mha_fwd_x3(const float* qkv, const uint8_t* key_pad, const int* 
 RSX_API int rsx_mha_qkv_fwd_x3(const float* x, const float* w, const float* bias, const uint8_t* key_pad,
                                const int* seg_off, int64_t B, int64_t L, int64_t H, int causal, float p_drop,
                                uint64_t seed, float* qkv, float* out, float* lse, void* stream) {
-  RSX_ARG(x && w && out, "null tensor");
-  RSX_ARG(L >= 1 && L <= kLMax, "L must be in [1,64]");
-  RSX_ARG(H == 4, "fused in_proj + attention: D = 128 (4 heads of 32)");
-  RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  const char* bad =
+      bad_arg(x && w && out, L, H == 4, "fused in_proj + attention: D = 128 (4 heads of 32)", true, p_drop);
+  RSX_ARG(!bad, bad);
   if (B == 0) return 0;
   QArgs a;
-  a.x = x; a.w = w; a.bias = bias; a.kpad = key_pad; a.seg = seg_off; a.qkv = qkv; a.out = out; a.lse = lse;
-  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
-  a.scale = 1.0f / sqrtf(32.0f);
-  a.drop = rsx::make_dropout(p_drop, seed);
-  hipLaunchKernelGGL(mha_qkv_fwd_x3_k<4>, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  a.x = x; a.w = w; a.bias = bias; a.qkv = qkv; a.out = out; a.lse = lse;
+  fill_args(a, key_pad, seg_off, B, L, H, 32, causal, p_drop, seed);
+  launch(mha_qkv_fwd_x3_k<4>, 4, a, stream);
   RSX_LAUNCHED();
   return 0;
 }
@@ -1641,20 +1419,14 @@ RSX_API int rsx_mha_qkv_fwd_x3(const float* x, const float* w, const float* bias
 RSX_API int rsx_mha_bwd_x3(const float* qkv, const uint8_t* key_pad, const int* seg_off, const float* out,
                            const float* lse, const float* dout, int64_t B, int64_t L, int64_t H, int64_t Dh,
                            int causal, float p_drop, uint64_t seed, float* dqkv, void* stream) {
-  RSX_ARG(qkv && out && lse && dout && dqkv, "null tensor");
-  RSX_ARG(L >= 1 && L <= kLMax, "L must be in [1,64]");
-  RSX_ARG(Dh == 32, "bf16x3 attention head dim must be 32");
-  RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0,1)");
+  const char* bad = bad_arg(qkv && out && lse && dout && dqkv, L, Dh == 32, "bf16x3 attention head dim must be 32", true,
+                            p_drop);
+  RSX_ARG(!bad, bad);
   if (B == 0) return 0;
   BwdArgs a;
-  a.qkv = qkv; a.kpad = key_pad; a.seg = seg_off; a.out = out; a.lse = lse; a.dout = dout; a.dqkv = dqkv;
-  a.B = (int)B; a.L = (int)L; a.H = (int)H; a.causal = causal;
-  a.scale = 1.0f / sqrtf((float)Dh);
-  a.drop = rsx::make_dropout(p_drop, seed);
-  if (causal)
-    hipLaunchKernelGGL(mha_bwd_x3s_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(mha_bwd_x3p_k, dim3((unsigned)((B * H + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  a.qkv = qkv; a.out = out; a.lse = lse; a.dout = dout; a.dqkv = dqkv;
+  fill_args(a, key_pad, seg_off, B, L, H, Dh, causal, p_drop, seed);
+  launch(causal ? mha_bwd_x3s_k : mha_bwd_x3p_k, 4, a, stream);
   RSX_LAUNCHED();
   return 0;
 }

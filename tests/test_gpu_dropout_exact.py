@@ -16,8 +16,8 @@ CPU generator (ops.next_seed). Four groups:
 Each comparison is reduced to one figure, max |device - ref| / (atol + rtol |ref|) ("excess"; the
 assertion is excess <= 1, a control needs excess >= 100), printed before it is asserted.
 
-Attention: which kernel a configuration reaches (rsx_mha_fwd / rsx_mha_bwd / rsx_mha_fwd_x3 /
-rsx_mha_bwd_x3 in mha.hip:1570-1678; ops._MHA picks the _x3 forward for bf16x3 at head dim 32 and
+Attention: which kernel a configuration reaches (the entry points rsx_mha_fwd / rsx_mha_bwd /
+rsx_mha_fwd_x3 / rsx_mha_bwd_x3 at the end of mha.hip; ops._MHA picks the _x3 forward for bf16x3 at head dim 32 and
 64, the _x3 backward for bf16x3 at head dim 32 only). L is the dense length or the packed max_len:
 
   precision  head dim  forward            backward
