@@ -1116,6 +1116,42 @@ int rsx_gbdt_apply_split(const uint8_t* bins, int64_t R, int F, const int* split
 int rsx_gbdt_tree(const uint8_t* bins, const float* y, int64_t R, int F, const uint8_t* is_cat, const int* n_bins,
                   int depth, double lr, double l2, float* Fx, int* qg, int* qh, uint8_t* leaf, int64_t* hist, void* ws,
                   int* splits, int64_t* leaf_sums, float* leaf_values, int* flag, void* stream);
+/* ---- QuerySoftMax: the listwise objective of the oblivious-tree model, csrc/gbdt_rank.hip ----
+ * Rows carry y in {0, 1} and a group (the reference's per-customer ranker rows: utils/monitor/log_importer.py
+ * returns X_user, X_item, y, groups). They are given in group order: row_group int32 [R] is the dense group
+ * index of each row (ascending), goff int32 [G + 1] the groups' offsets, 1 <= G <= R. Group q has the rows
+ * I_q and the fp32 approximant a; the base score is F0 = 0.
+ *   per group: m_q = max a_i over I_q (fp32, exact);
+ *          E_i = llrint(exp((double)a_i - (double)m_q) 2^32), round half to even, an int64 in [0, 2^32];
+ *          Z_q = sum E_i, an exact int64 sum in any order (no overflow for R < 2^31);
+ *          p_i = (float)((double)E_i / (double)Z_q);   S_q = #{i in I_q : y_i = 1}.
+ *   per row: S_q = 0 -> g_i = h_i = 0 (the group carries no signal); else t_i = y_i ? (float)(1.0 / S_q) : 0,
+ *          g_i = t_i - p_i, h_i = p_i (1 - p_i) in fp32: the negative gradient and the Hessian diagonal of
+ *          L_q = -(1 / S_q) sum_{y_i = 1} log softmax(a)_i, so every group with a positive weighs the same.
+ *          qg = llrint(g 2^30), qh = llrint(h 2^30) as rsx_gbdt_grad writes them (|g| <= 1, h <= 1/4: both
+ *          fit an int32). From there the tree is exactly the tree above.
+ *   monitoring: L_q = -(1 / S_q) sum_{y_i = 1} [(double)a_i - (double)m_q - log((double)Z_q 2^-32)] in fp64;
+ *          the metric QuerySoftMax = sum_{S_q > 0} L_q / #{q : S_q > 0}.
+ * The maximum, Z and S are order-free (a maximum of ordered integer keys, integer sums), so the gradients do
+ * not depend on the order of the rows within or across groups and every run gives the same bits. No thread
+ * walks a group: the cost does not depend on the group sizes. Integer atomics only. A row whose row_group is
+ * outside [0, G) gets g = h = 0 and no access leaves its array. */
+/* bytes of the workspace ws of the three entries below (-1 unless 1 <= R < 2^31 and 1 <= G <= R) */
+int64_t rsx_gbdt_grad_query_softmax_workspace_bytes(int64_t R, int64_t G);
+/* F, y [R] fp32, row_group [R], goff [G + 1] int32 -> qg, qh [R] int32; ws 16-byte aligned. */
+int rsx_gbdt_grad_query_softmax(const float* F, const float* y, const int* row_group, const int* goff, int64_t R,
+                                int64_t G, void* ws, int64_t ws_bytes, int* qg, int* qh, void* stream);
+/* out (16 bytes, 8-byte aligned) = [loss_sum double = sum_{S_q > 0} L_q, live_groups int64 = #{q : S_q > 0}]; the
+ * fp64 sum runs row by row in a fixed order (as rsx_binary_eval's loss_sum): the same bits every run. */
+int rsx_query_softmax_eval(const float* F, const float* y, const int* row_group, const int* goff, int64_t R, int64_t G,
+                           void* ws, int64_t ws_bytes, void* out, void* stream);
+/* rsx_gbdt_tree with the gradient stage replaced by rsx_gbdt_grad_query_softmax (group_ws: its workspace): one
+ * whole tree by one call, three kernels and one fill in place of rsx_gbdt_tree's one gradient kernel. */
+int rsx_gbdt_tree_grouped(const uint8_t* bins, const float* y, const int* row_group, const int* goff, int64_t R,
+                          int64_t G, int F, const uint8_t* is_cat, const int* n_bins, int depth, double lr, double l2,
+                          float* Fx, int* qg, int* qh, uint8_t* leaf, int64_t* hist, void* ws, void* group_ws,
+                          int64_t group_ws_bytes, int* splits, int64_t* leaf_sums, float* leaf_values, int* flag,
+                          void* stream);
 /* out [R] = (init ? init : f0) + the leaf values of the trees [tree_begin, tree_end) in order; splits int32
  * [T, 6, 2] (the first depth levels used) and leaf_values fp32 [T, 64]; out may be init. One row per lane. */
 int rsx_gbdt_predict(const uint8_t* bins, int64_t R, int F, const int* splits, const float* leaf_values,

@@ -221,7 +221,12 @@ _SIGS = {
     "rsx_gbdt_apply_split": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_i, c_p, c_p, c_d, c_d, c_p, c_p, c_p, c_p, c_p]),
     "rsx_gbdt_tree": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                             c_p, c_p]),
-    "rsx_gbdt_predict": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
+    "rsx_gbdt_grad_query_softmax_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rsx_gbdt_grad_query_softmax": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_query_softmax_eval": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p]),
+    "rsx_gbdt_tree_grouped": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i64, c_i, c_p, c_p, c_i, c_d, c_d, c_p, c_p, c_p, c_p,
+                                    c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_gbdt_predict": (c_i,[c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
     "rsx_rerank_tabular": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
 }
 

@@ -18,6 +18,7 @@
 //   apply_k       leaf = 2 leaf + right per row, and at the last level F += value[leaf];
 //   predict_k     one row per lane, the row's bins in LDS, the trees staged through LDS kTreeChunk at a time.
 // Splits never leave the device: apply_k and predict_k read them from memory.
+// rsx_gbdt_tree_grouped runs the same levels on the QuerySoftMax gradients of gbdt_rank.hip.
 #include "rsx_block.h"
 #include "rsx_common.h"
 
@@ -349,6 +350,21 @@ void launch_apply(const uint8_t* bins, int64_t R, int F, const int* split, const
                      hist != nullptr ? leaf_values : nullptr, Fx, flag);
 }
 
+// A tree's levels on the gradients qg / qh already written: what rsx_gbdt_tree and rsx_gbdt_tree_grouped share.
+void launch_levels(const uint8_t* bins, int64_t R, int F, const uint8_t* is_cat, const int* n_bins, int depth, double lr,
+                   double l2, float* Fx, const int* qg, const int* qh, uint8_t* leaf, int64_t* hist, void* ws, int* splits,
+                   int64_t* leaf_sums, float* leaf_values, int* flag, hipStream_t st) {
+  (void)hipMemsetAsync(leaf, 0, (size_t)R, st);
+  for (int d = 0; d < depth; ++d) {
+    const int NL = 1 << d;
+    const bool last = d == depth - 1;
+    launch_hist(bins, leaf, qg, qh, R, F, NL, hist, flag, st);
+    launch_split(hist, is_cat, n_bins, F, NL, l2, ws, splits + 2 * d, nullptr, st);
+    launch_apply(bins, R, F, splits + 2 * d, is_cat, NL, leaf, last ? hist : nullptr, lr, l2, leaf_sums, leaf_values, Fx, flag,
+                 st);
+  }
+}
+
 }  // namespace
 
 RSX_API int64_t rsx_gbdt_tree_chunk(void) { return kTreeChunk; }
@@ -431,15 +447,30 @@ RSX_API int rsx_gbdt_tree(const uint8_t* bins, const float* y, int64_t R, int F,
   RSX_ARG(rsx::aligned16(ws), "ws must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   launch_grad(Fx, y, R, qg, qh, st);
-  (void)hipMemsetAsync(leaf, 0, (size_t)R, st);
-  for (int d = 0; d < depth; ++d) {
-    const int NL = 1 << d;
-    const bool last = d == depth - 1;
-    launch_hist(bins, leaf, qg, qh, R, F, NL, hist, flag, st);
-    launch_split(hist, is_cat, n_bins, F, NL, l2, ws, splits + 2 * d, nullptr, st);
-    launch_apply(bins, R, F, splits + 2 * d, is_cat, NL, leaf, last ? hist : nullptr, lr, l2, leaf_sums, leaf_values, Fx, flag,
-                 st);
-  }
+  launch_levels(bins, R, F, is_cat, n_bins, depth, lr, l2, Fx, qg, qh, leaf, hist, ws, splits, leaf_sums, leaf_values, flag, st);
+  RSX_LAUNCHED();
+  return 0;
+}
+
+RSX_API int rsx_gbdt_tree_grouped(const uint8_t* bins, const float* y, const int* row_group, const int* goff, int64_t R,
+                                  int64_t G, int F, const uint8_t* is_cat, const int* n_bins, int depth, double lr, double l2,
+                                  float* Fx, int* qg, int* qh, uint8_t* leaf, int64_t* hist, void* ws, void* group_ws,
+                                  int64_t group_ws_bytes, int* splits, int64_t* leaf_sums, float* leaf_values, int* flag,
+                                  void* stream) {
+  RSX_ARG(bins && y && row_group && goff && is_cat && n_bins && Fx && qg && qh && leaf && hist && ws && group_ws && splits &&
+              leaf_sums && leaf_values && flag,
+          "null tensor");
+  RSX_ARG(R >= 1 && R < (1ll << 31), "need 1 <= R < 2^31");
+  RSX_ARG(G >= 1 && G <= R, "need 1 <= G <= R");
+  RSX_ARG(F >= 1 && F <= kMaxFeatures, "need 1 <= F <= 32");
+  RSX_ARG(depth >= 1 && depth <= kMaxDepth, "need 1 <= depth <= 6");
+  RSX_ARG(l2 > 0.0, "l2 must be positive");
+  RSX_ARG(rsx::aligned16(ws) && rsx::aligned16(group_ws), "ws and group_ws must be 16-byte aligned");
+  RSX_ARG(group_ws_bytes >= rsx::gbdt_query_softmax_workspace(R, G),
+          "group workspace too small (rsx_gbdt_grad_query_softmax_workspace_bytes)");
+  hipStream_t st = (hipStream_t)stream;
+  rsx::gbdt_query_softmax_launch(Fx, y, row_group, goff, R, (int)G, group_ws, qg, qh, st);
+  launch_levels(bins, R, F, is_cat, n_bins, depth, lr, l2, Fx, qg, qh, leaf, hist, ws, splits, leaf_sums, leaf_values, flag, st);
   RSX_LAUNCHED();
   return 0;
 }

@@ -120,6 +120,12 @@ int train_head_launch(const float* h2, const float* wo, const float* lin, const 
                       int64_t R, int mean, bool relu_mask, float* logit, float* g, float* dh2, void* ws, double* loss,
                       float* dbias, float* dwo, void* stream);
 
+// The QuerySoftMax gradient stage (csrc/gbdt_rank.hip), arguments as rsx_gbdt_grad_query_softmax after its
+// checks; the workspace bytes it needs, or -1 unless 1 <= R < 2^31 and 1 <= G <= R.
+int64_t gbdt_query_softmax_workspace(int64_t R, int64_t G);
+void gbdt_query_softmax_launch(const float* F, const float* y, const int* row_group, const int* goff, int64_t R, int G,
+                               void* ws, int* qg, int* qh, hipStream_t st);
+
 }  // namespace rsx
 
 #define RSX_ARG(cond, msg)                                   \

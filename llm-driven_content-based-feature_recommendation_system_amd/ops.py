@@ -4194,12 +4194,119 @@ class GBDTScratch:
         self.key = (R, F, depth, torch.device(device))
 
 
-def gbdt_tree(bins, y, Fx, is_cat, n_bins, depth, lr, l2, splits, leaf_values, scratch):
+class GBDTGroupPlan:
+    """The group layout the QuerySoftMax kernels read, built once per set of rows from group_id [R] (int32 /
+    int64 ids >= 0, the rows of a group anywhere) with torch on the device and one host read (the number of
+    groups, with the smallest id in the same copy; ValueError for a negative id): order int64 [R] = the
+    stable sort of the rows by id (rows in group order = rows[order]), row_group int32 [R] = the dense
+    group index of each row in that order, goff int32 [G + 1] = the groups' offsets, G, R, ws = the
+    kernels' workspace."""
+
+    def __init__(self, group_id, device=None):
+        g = torch.as_tensor(group_id)
+        if g.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"GBDTGroupPlan: group_id must be int32 or int64 (got {g.dtype})")
+        if device is None:
+            device = g.device if g.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        g = g.detach().to(device).reshape(-1).to(torch.int64)
+        N.ensure_device(g)
+        R = g.numel()
+        if not 1 <= R < 2 ** 31:
+            raise ValueError(f"GBDTGroupPlan: need 1 <= R < 2^31 rows (got {R})")
+        ids, order = torch.sort(g, stable=True)
+        head = torch.ones(R, device=g.device, dtype=torch.bool)
+        head[1:] = ids[1:] != ids[:-1]
+        dense = torch.cumsum(head, 0) - 1
+        G, lowest = (int(v) for v in torch.stack([dense[-1] + 1, ids[0]]).tolist())     # the one host read
+        if lowest < 0:
+            raise ValueError(f"GBDTGroupPlan: group ids must be >= 0 (got {lowest})")
+        sizes = torch.zeros(G + 1, device=g.device, dtype=torch.int64)
+        sizes.scatter_add_(0, dense + 1, torch.ones_like(dense))      # an integer sum: the same bits every run
+        self.order, self.row_group = order, _c(dense.to(torch.int32))
+        self.goff = _c(torch.cumsum(sizes, 0).to(torch.int32))
+        self.G, self.R, self.device = G, R, g.device
+        nws = int(N.lib().rsx_gbdt_grad_query_softmax_workspace_bytes(R, G))
+        if nws < 0:
+            N.check(1, "gbdt_grad_query_softmax_workspace_bytes")
+        self.ws = torch.empty(nws, device=g.device, dtype=torch.uint8)
+
+
+def _gbdt_plan(fn, plan, R, ref):
+    if not isinstance(plan, GBDTGroupPlan):
+        raise TypeError(f"{fn}: groups must be a GBDTGroupPlan, got {type(plan).__name__}")
+    if plan.R != R or plan.device != ref.device:
+        raise ValueError(f"{fn}: the plan was built for {plan.R} rows on {plan.device}, not {R} on {ref.device}")
+
+
+def gbdt_grad_query_softmax(F, y, plan, out=None):
+    """(qg, qh) int32 [R] of the approximant F [R] and the labels y [R] (fp32, device, both in the group
+    order of plan: rows[plan.order]) under the QuerySoftMax objective (include/recsys_amd.h): per group the
+    exact maximum, Z = the int64 sum of llrint(exp(a - m) 2^32) and S = the positives, then g = t - p, h =
+    p (1 - p) in fp32, quantised as gbdt_grad's (rsx_gbdt_grad_query_softmax). The rows of a group without
+    a positive get 0. The result does not depend on the order of the rows. out: (qg, qh) to write into."""
+    N.ensure_device(F)
+    _f32("gbdt_grad_query_softmax", "F", F)
+    R = F.numel()
+    _gbdt_plan("gbdt_grad_query_softmax", plan, R, F)
+    _gbdt_rows("gbdt_grad_query_softmax", "F", F, torch.float32, R, F)
+    _gbdt_rows("gbdt_grad_query_softmax", "y", y, torch.float32, R, F)
+    qg, qh = out if out is not None else (torch.empty(R, device=F.device, dtype=torch.int32) for _ in range(2))
+    _gbdt_rows("gbdt_grad_query_softmax", "qg", qg, torch.int32, R, F)
+    _gbdt_rows("gbdt_grad_query_softmax", "qh", qh, torch.int32, R, F)
+    with timed("gbdt/grad_query_softmax"):
+        N.check(N.lib().rsx_gbdt_grad_query_softmax(N.ptr(F), N.ptr(y), N.ptr(plan.row_group), N.ptr(plan.goff), R, plan.G,
+                                                    N.ptr(plan.ws), plan.ws.numel(), N.ptr(qg), N.ptr(qh), N.stream()),
+                "gbdt_grad_query_softmax")
+    return qg, qh
+
+
+class QuerySoftMaxEval:
+    """What query_softmax_eval returns. The outputs stay on the device until result(): loss_sum (float64)
+    and live_groups (int64) are views of one 16-byte allocation, fetched by one copy."""
+
+    def __init__(self, buf):
+        self._buf = buf
+        self.loss_sum, self.live_groups = buf[:1].view(torch.float64), buf[1:2]
+
+    def result(self):
+        """The one host read: {"loss": loss_sum / live_groups (NaN when no group holds a positive),
+        "live_groups"}."""
+        return self._result(self._buf.cpu())
+
+    @staticmethod
+    def _result(host):
+        live = int(host[1])
+        loss = float(host[:1].view(torch.float64)[0])
+        return {"loss": loss / live if live else float("nan"), "live_groups": live}
+
+
+def query_softmax_eval(F, y, plan):
+    """The QuerySoftMax metric of the scores F [R] against the labels y [R] (fp32, device, in the group order
+    of plan): the mean over the groups with a positive of L_q = -(1 / S_q) sum_{y_i = 1} log softmax(a)_i, its
+    sum formed in fp64 in a fixed order (rsx_query_softmax_eval: the same bits every run), without a host
+    synchronisation. Returns a QuerySoftMaxEval; its result() does the one host read."""
+    N.ensure_device(F)
+    _f32("query_softmax_eval", "F", F)
+    R = F.numel()
+    _gbdt_plan("query_softmax_eval", plan, R, F)
+    _gbdt_rows("query_softmax_eval", "F", F, torch.float32, R, F)
+    _gbdt_rows("query_softmax_eval", "y", y, torch.float32, R, F)
+    out = QuerySoftMaxEval(torch.empty(2, device=F.device, dtype=torch.int64))
+    with timed("query_softmax_eval"):
+        N.check(N.lib().rsx_query_softmax_eval(N.ptr(F), N.ptr(y), N.ptr(plan.row_group), N.ptr(plan.goff), R, plan.G,
+                                               N.ptr(plan.ws), plan.ws.numel(), N.ptr(out._buf), N.stream()),
+                "query_softmax_eval")
+    return out
+
+
+def gbdt_tree(bins, y, Fx, is_cat, n_bins, depth, lr, l2, splits, leaf_values, scratch, groups=None):
     """One whole tree on the approximant Fx [R] (updated in place), enqueued by one native call
     (rsx_gbdt_tree: gradients, then per level histogram, split search and leaf update, the last level with the
     leaf values and the update of Fx; 2 + 4 depth kernels and 1 + depth fills, no host synchronisation).
     Writes splits int32 [>= depth, 2] and leaf_values fp32 [>= 2^depth] (a tree's rows of a GBDTModel).
-    scratch: a GBDTScratch(R, F, depth, device); its flag collects range errors (the caller watches it)."""
+    scratch: a GBDTScratch(R, F, depth, device); its flag collects range errors (the caller watches it).
+    groups: a GBDTGroupPlan of the rows (given in its group order) selects the QuerySoftMax gradients
+    (rsx_gbdt_tree_grouped: three kernels and a fill in place of the Logloss gradient kernel)."""
     F, R = _gbdt_bins("gbdt_tree", bins)
     if not 1 <= depth <= GBDT_MAX_DEPTH:
         raise ValueError(f"gbdt_tree: need 1 <= depth <= {GBDT_MAX_DEPTH} (got {depth})")
@@ -4215,6 +4322,16 @@ def gbdt_tree(bins, y, Fx, is_cat, n_bins, depth, lr, l2, splits, leaf_values, s
             or leaf_values.device != bins.device):
         raise ValueError(f"gbdt_tree: leaf_values must be a contiguous fp32 [>= {1 << depth}] tensor on {bins.device}")
     s = scratch
+    if groups is not None:
+        _gbdt_plan("gbdt_tree", groups, R, bins)
+        g = groups
+        with timed("gbdt/tree_grouped"):
+            N.check(N.lib().rsx_gbdt_tree_grouped(N.ptr(bins), N.ptr(y), N.ptr(g.row_group), N.ptr(g.goff), R, g.G, F,
+                                                  N.ptr(is_cat), N.ptr(n_bins), int(depth), float(lr), float(l2), N.ptr(Fx),
+                                                  N.ptr(s.qg), N.ptr(s.qh), N.ptr(s.leaf), N.ptr(s.hist), N.ptr(s.ws),
+                                                  N.ptr(g.ws), g.ws.numel(), N.ptr(splits), N.ptr(s.sums),
+                                                  N.ptr(leaf_values), N.ptr(s.flag), N.stream()), "gbdt_tree_grouped")
+        return
     with timed("gbdt/tree"):
         N.check(N.lib().rsx_gbdt_tree(N.ptr(bins), N.ptr(y), R, F, N.ptr(is_cat), N.ptr(n_bins), int(depth), float(lr),
                                       float(l2), N.ptr(Fx), N.ptr(s.qg), N.ptr(s.qh), N.ptr(s.leaf), N.ptr(s.hist),

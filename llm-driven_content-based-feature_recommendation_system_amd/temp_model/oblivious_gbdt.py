@@ -14,6 +14,11 @@ Compute: ops.gbdt_bin (borders -> bins), ops.gbdt_tree (one native call per tree
 rsx_gbdt_histogram, rsx_gbdt_best_split, rsx_gbdt_apply_split), ops.gbdt_predict; the metrics on
 ops.binary_eval / ops.group_eval. Every sum is an integer sum, so two fits of the same data give the same
 model bit for bit.
+
+`ObliviousBoostingRanker` is the same model trained on the listwise QuerySoftMax objective over the
+reference's per-customer groups (utils/monitor/log_importer.py: X_user, X_item, y, groups): ops.GBDTGroupPlan,
+ops.gbdt_tree(groups=...) (rsx_gbdt_tree_grouped: rsx_gbdt_grad_query_softmax in place of rsx_gbdt_grad),
+ops.query_softmax_eval; restated by tests/gbdt_rank_ref.py. The two classes share everything but fit.
 """
 from __future__ import annotations
 
@@ -58,18 +63,11 @@ def _is_frame(X):
     return hasattr(X, "columns") and hasattr(X, "iloc")
 
 
-class ObliviousBoostingClassifier:
-    """Binary classifier of `iterations` oblivious trees of `depth` <= 6 levels boosted on Logloss.
+class _ObliviousBoosting:
+    """What the classifier and the ranker share: the hyper-parameters, columns -> borders, vocabularies and
+    bins, the raw scores and the model file. A subclass names its loss_function and brings fit."""
 
-    X is a dict or DataFrame of columns (those named in cat_features are categorical: any hashable
-    values, coded by a vocabulary built from the training rows, code 0 = unseen; at most 255 distinct
-    values; the others numeric), or a pair (numeric [R, Fn] float, categorical [R, Fc] integer) of tensors
-    or arrays, either may be None; there the categorical values are codes already, in [0, 255] (a value
-    outside it predicts as 0). Internally the numeric columns come first, then the categorical ones: that
-    is the order in which ties between equally good splits are broken.
-
-    After fit: tree_count_, feature_names_, and with an eval_set evals_result_, best_iteration_ (the
-    0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
+    loss_function = None
 
     def __init__(self, iterations=1000, learning_rate=0.05, depth=6, l2_leaf_reg=3.0, border_count=254,
                  cat_features=None, early_stopping_rounds=None, metric_period=1, device=None):
@@ -150,25 +148,11 @@ class ObliviousBoostingClassifier:
         return torch.from_numpy(host).to(self.device)
 
     # ---- training ----------------------------------------------------------------------------------
-    @torch.no_grad()
-    def fit(self, X, y, eval_set=None, eval_metric="AUC", use_best_model=None, eval_group_id=None,
-            record_approximants=()):
-        """Boost `iterations` trees on X / y [R] in {0, 1}. Nothing synchronises with the host inside a tree
-        and the splits stay on the device; a plain fit reads the host once (the label counts, with the largest
-        code of tensor-given categorical columns in the same copy).
-
-        eval_set=(X_val, y_val) adds the reference's validation (:98-108, :123-135) with the semantics
-        DeepFM.fit documents: after every metric_period-th tree (and the last) the validation scores are
-        advanced by the new trees and evaluated on the device (ops.binary_eval; with eval_group_id also
-        ops.group_eval), one host read per evaluation that also carries the training Logloss after that tree.
-        eval_metric "AUC", "Logloss", "NDCG", "NDCG:top=K" or "QueryAUC" picks the best evaluation (only a
-        strictly better one replaces it), early_stopping_rounds (the constructor's) stops after that many
-        evaluations without an improvement, and use_best_model (default True with an eval_set) truncates the
-        model to best_iteration_ + 1 trees. record_approximants: tree counts t after which the training
-        approximant is kept (approximants_[t], a device tensor), for tests."""
-        esr = self.early_stopping_rounds if eval_set is not None else None
-        use_best_model = _fit_args(eval_set, eval_metric, esr, use_best_model, None, eval_group_id)
-        metric, top = _parse_eval_metric(eval_metric)
+    def _fit_columns(self, X, y, check_labels):
+        """The start of a fit: the columns of X split, the vocabularies, borders and n_bins_ built and the
+        training rows binned. One host read (the label counts, with the largest code of tensor-given
+        categorical columns in the same copy); check_labels(n_pos, n_neg) raises for labels the objective
+        cannot train on. Returns (bins uint8 [F, R], y fp32 [R], is_cat uint8 [F], n_pos)."""
         dev = self.device
         self.model_, self._fitted_names = None, None
         num, cat, nums, cats = self._split_columns(X)
@@ -202,8 +186,7 @@ class ObliviousBoostingClassifier:
         n_pos, n_neg = host[:2]
         if n_pos + n_neg != R:
             raise ValueError("labels must be 0 or 1")
-        if n_pos == 0 or n_neg == 0:
-            raise ValueError("the training labels hold a single class")
+        check_labels(n_pos, n_neg)
         if Fc and torch.is_tensor(cat):
             if host[2] > _MAX_CODES or host[3] < 0:
                 raise ValueError(f"categorical codes must be in [0, {_MAX_CODES}] (got {host[3]} .. {host[2]}): at most "
@@ -217,17 +200,118 @@ class ObliviousBoostingClassifier:
             self.borders_, self.n_borders_ = None, None
         is_cat = torch.tensor([0] * Fn + [1] * Fc, dtype=torch.uint8, device=dev)
         self.n_bins_ = torch.tensor(n_bins, dtype=torch.int32, device=dev)
-        f0 = float(np.float32(math.log(n_pos / R / (1.0 - n_pos / R))))
-        T = self.iterations
-        model = ops.GBDTModel(torch.zeros(T, ops.GBDT_MAX_DEPTH, 2, device=dev, dtype=torch.int32),
-                              torch.zeros(T, ops.GBDT_LEAF_STRIDE, device=dev, dtype=torch.float32), is_cat, self.depth,
-                              f0, 0)
-        self.model_ = model
         bins = torch.empty(F, R, device=dev, dtype=torch.uint8)
         if Fn:
             ops.gbdt_bin(num, self.borders_, self.n_borders_, out=bins)
         if Fc:
             bins[Fn:] = self._codes(cat, R)
+        return bins, y, is_cat, n_pos
+
+    def _new_model(self, is_cat, f0):
+        """The empty GBDTModel of `iterations` trees a fit fills (model_)."""
+        T, dev = self.iterations, self.device
+        self.model_ = ops.GBDTModel(torch.zeros(T, ops.GBDT_MAX_DEPTH, 2, device=dev, dtype=torch.int32),
+                                    torch.zeros(T, ops.GBDT_LEAF_STRIDE, device=dev, dtype=torch.float32), is_cat,
+                                    self.depth, f0, 0)
+        return self.model_
+
+    # ---- prediction ----------------------------------------------------------------------------------
+    def _fitted(self):
+        if self.model_ is None:
+            raise RuntimeError("the model is not fitted")
+        return self.model_
+
+    @torch.no_grad()
+    def predict_logits(self, X, ntree_end=None):
+        """The raw scores [R] (fp32 device tensor) of X after the first ntree_end trees (default: tree_count_):
+        bit-identical to the training approximant after as many trees."""
+        model = self._fitted()
+        if ntree_end is not None and not 0 <= ntree_end <= model.splits.shape[0]:
+            raise ValueError(f"ntree_end must be in [0, {model.splits.shape[0]}] (got {ntree_end})")
+        return ops.gbdt_predict(self._bins(X), model, ntree_end=ntree_end)
+
+    # ---- persistence -----------------------------------------------------------------------------------
+    def save_model(self, path):
+        """torch.save of the trees in use, the borders and the vocabularies, under the class's loss_function."""
+        m = self._fitted()
+        n = m.n_trees
+        cpu = lambda t: None if t is None else t.detach().cpu()   # noqa: E731
+        torch.save({"format": "oblivious_gbdt/1", "loss_function": self.loss_function, "splits": cpu(m.splits[:n]), "leaf_values": cpu(m.leaf_values[:n]),
+                    "is_cat": cpu(m.is_cat), "depth": m.depth, "f0": m.f0, "borders": cpu(self.borders_),
+                    "n_borders": cpu(self.n_borders_), "n_bins": cpu(self.n_bins_), "vocab": self.vocab_,
+                    "names": self._fitted_names,
+                    "params": {"iterations": self.iterations, "learning_rate": self.learning_rate, "depth": self.depth,
+                               "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
+                               "cat_features": self.cat_features},
+                    "best_iteration": self.best_iteration_, "best_score": self.best_score_,
+                    "evals_result": self.evals_result_}, path)
+
+    def load_model(self, path):
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        if sd.get("format") != "oblivious_gbdt/1":
+            raise ValueError(f"{path} is not an ObliviousBoostingClassifier model")
+        loss = sd.get("loss_function", "Logloss")      # files written before the ranker existed carry no key
+        if loss != self.loss_function:
+            raise ValueError(f"{path} holds a {loss} model: {type(self).__name__} loads {self.loss_function} models")
+        dev = self.device
+        to = lambda t: None if t is None else t.to(dev).contiguous()   # noqa: E731
+        for k, v in sd["params"].items():
+            setattr(self, k, v)
+        self.model_ = ops.GBDTModel(to(sd["splits"]), to(sd["leaf_values"]), to(sd["is_cat"]), sd["depth"], sd["f0"],
+                                    sd["splits"].shape[0])
+        self.borders_, self.n_borders_, self.n_bins_ = to(sd["borders"]), to(sd["n_borders"]), to(sd["n_bins"])
+        self.vocab_, self._fitted_names = sd["vocab"], tuple(sd["names"])
+        self.feature_names_ = list(self._fitted_names[0]) + list(self._fitted_names[1])
+        self.best_iteration_, self.best_score_, self.evals_result_ = sd["best_iteration"], sd["best_score"], sd["evals_result"]
+        self.tree_count_ = self.model_.n_trees
+        return self
+
+
+class ObliviousBoostingClassifier(_ObliviousBoosting):
+    """Binary classifier of `iterations` oblivious trees of `depth` <= 6 levels boosted on Logloss.
+
+    X is a dict or DataFrame of columns (those named in cat_features are categorical: any hashable
+    values, coded by a vocabulary built from the training rows, code 0 = unseen; at most 255 distinct
+    values; the others numeric), or a pair (numeric [R, Fn] float, categorical [R, Fc] integer) of tensors
+    or arrays, either may be None; there the categorical values are codes already, in [0, 255] (a value
+    outside it predicts as 0). Internally the numeric columns come first, then the categorical ones: that
+    is the order in which ties between equally good splits are broken.
+
+    After fit: tree_count_, feature_names_, and with an eval_set evals_result_, best_iteration_ (the
+    0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
+
+    loss_function = "Logloss"
+
+    @torch.no_grad()
+    def fit(self, X, y, eval_set=None, eval_metric="AUC", use_best_model=None, eval_group_id=None,
+            record_approximants=()):
+        """Boost `iterations` trees on X / y [R] in {0, 1}. Nothing synchronises with the host inside a tree
+        and the splits stay on the device; a plain fit reads the host once (the label counts, with the largest
+        code of tensor-given categorical columns in the same copy).
+
+        eval_set=(X_val, y_val) adds the reference's validation (:98-108, :123-135) with the semantics
+        DeepFM.fit documents: after every metric_period-th tree (and the last) the validation scores are
+        advanced by the new trees and evaluated on the device (ops.binary_eval; with eval_group_id also
+        ops.group_eval), one host read per evaluation that also carries the training Logloss after that tree.
+        eval_metric "AUC", "Logloss", "NDCG", "NDCG:top=K" or "QueryAUC" picks the best evaluation (only a
+        strictly better one replaces it), early_stopping_rounds (the constructor's) stops after that many
+        evaluations without an improvement, and use_best_model (default True with an eval_set) truncates the
+        model to best_iteration_ + 1 trees. record_approximants: tree counts t after which the training
+        approximant is kept (approximants_[t], a device tensor), for tests."""
+        esr = self.early_stopping_rounds if eval_set is not None else None
+        use_best_model = _fit_args(eval_set, eval_metric, esr, use_best_model, None, eval_group_id)
+        metric, top = _parse_eval_metric(eval_metric)
+        dev = self.device
+
+        def two_classes(n_pos, n_neg):
+            if n_pos == 0 or n_neg == 0:
+                raise ValueError("the training labels hold a single class")
+
+        bins, y, is_cat, n_pos = self._fit_columns(X, y, two_classes)
+        F, R = bins.shape
+        f0 = float(np.float32(math.log(n_pos / R / (1.0 - n_pos / R))))
+        T = self.iterations
+        model = self._new_model(is_cat, f0)
 
         validate = eval_set is not None
         if validate:
@@ -285,55 +369,139 @@ class ObliviousBoostingClassifier:
         self.tree_count_ = model.n_trees
         return self
 
-    # ---- prediction ----------------------------------------------------------------------------------
-    def _fitted(self):
-        if self.model_ is None:
-            raise RuntimeError("the model is not fitted")
-        return self.model_
-
-    @torch.no_grad()
-    def predict_logits(self, X, ntree_end=None):
-        """The raw scores [R] (fp32 device tensor) of X after the first ntree_end trees (default: tree_count_):
-        bit-identical to the training approximant after as many trees."""
-        model = self._fitted()
-        if ntree_end is not None and not 0 <= ntree_end <= model.splits.shape[0]:
-            raise ValueError(f"ntree_end must be in [0, {model.splits.shape[0]}] (got {ntree_end})")
-        return ops.gbdt_predict(self._bins(X), model, ntree_end=ntree_end)
-
     def predict_proba(self, X) -> np.ndarray:
         """CatBoost's shape: [R, 2] = (1 - p, p) with p = sigmoid(raw score), a host array."""
         p = torch.sigmoid(self.predict_logits(X))
         return torch.stack([1.0 - p, p], dim=1).cpu().numpy()
 
-    # ---- persistence -----------------------------------------------------------------------------------
-    def save_model(self, path):
-        """torch.save of the trees in use, the borders and the vocabularies."""
-        m = self._fitted()
-        n = m.n_trees
-        cpu = lambda t: None if t is None else t.detach().cpu()   # noqa: E731
-        torch.save({"format": "oblivious_gbdt/1", "splits": cpu(m.splits[:n]), "leaf_values": cpu(m.leaf_values[:n]),
-                    "is_cat": cpu(m.is_cat), "depth": m.depth, "f0": m.f0, "borders": cpu(self.borders_),
-                    "n_borders": cpu(self.n_borders_), "n_bins": cpu(self.n_bins_), "vocab": self.vocab_,
-                    "names": self._fitted_names,
-                    "params": {"iterations": self.iterations, "learning_rate": self.learning_rate, "depth": self.depth,
-                               "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
-                               "cat_features": self.cat_features},
-                    "best_iteration": self.best_iteration_, "best_score": self.best_score_,
-                    "evals_result": self.evals_result_}, path)
 
-    def load_model(self, path):
-        sd = torch.load(path, map_location="cpu", weights_only=False)
-        if sd.get("format") != "oblivious_gbdt/1":
-            raise ValueError(f"{path} is not an ObliviousBoostingClassifier model")
+def _parse_rank_metric(eval_metric):
+    """A ranker's eval_metric -> (the key of evals_result_["validation"] it selects, the NDCG cut-off):
+    "QuerySoftMax" (smaller is better), "NDCG", "NDCG:top=K" or "QueryAUC"."""
+    if eval_metric == "QuerySoftMax":
+        return "QuerySoftMax", 10
+    if eval_metric in ("AUC", "Logloss"):
+        raise ValueError(f'a ranker\'s eval_metric must be "QuerySoftMax", "NDCG", "NDCG:top=K" or "QueryAUC" '
+                         f"(got {eval_metric!r})")
+    return _parse_eval_metric(eval_metric)
+
+
+class ObliviousBoostingRanker(_ObliviousBoosting):
+    """Ranker of `iterations` oblivious trees boosted on QuerySoftMax, the group-normalised softmax loss
+    (include/recsys_amd.h, "QuerySoftMax"; restated by tests/gbdt_rank_ref.py): the rows carry y in {0, 1}
+    and a group id (the reference's per-customer ranker rows, utils/monitor/log_importer.py), and every
+    group with a positive weighs the same. X as ObliviousBoostingClassifier's; the base score is 0. The
+    trees, the histograms and the prediction are the classifier's: only the gradient stage differs
+    (ops.gbdt_tree(groups=...)). Every sum is an integer sum and every group reduction is order-free: two
+    fits give the same model bit for bit, and so does a fit on the same rows in another order."""
+
+    loss_function = "QuerySoftMax"
+
+    @torch.no_grad()
+    def fit(self, X, y, group_id, eval_set=None, eval_group_id=None, eval_metric="NDCG:top=10", use_best_model=None,
+            record_approximants=()):
+        """Boost `iterations` trees on X / y [R] in {0, 1} / group_id [R] (int32 or int64 ids >= 0, the rows of a
+        group anywhere). The bins and labels are permuted into group order once (ops.GBDTGroupPlan); nothing
+        synchronises with the host inside a tree. A plain fit reads the host twice (the plan's number of
+        groups, the label counts). ValueError when no group holds a positive.
+
+        eval_set=(X_val, y_val) with eval_group_id [validation rows] validates as the classifier does: after
+        every metric_period-th tree (and the last) the validation scores are advanced by the new trees and
+        evaluated on the device, one host read per evaluation: evals_result_["learn"]["QuerySoftMax"] (the
+        training loss after that tree) and evals_result_["validation"]["QuerySoftMax" | "NDCG" | "QueryAUC"]
+        (ops.query_softmax_eval, ops.group_eval). eval_metric "QuerySoftMax" (smaller is better), "NDCG",
+        "NDCG:top=K" or "QueryAUC" picks the best evaluation; early_stopping_rounds, best_iteration_,
+        best_score_ and use_best_model as ObliviousBoostingClassifier.fit. record_approximants: tree counts t
+        after which the training approximant is kept (approximants_[t], in group order: the rows
+        [group_plan_.order]), for tests."""
+        metric, top = _parse_rank_metric(eval_metric)
+        validate = eval_set is not None
+        if not validate:
+            if eval_group_id is not None:
+                raise ValueError("eval_group_id needs an eval_set")
+            if use_best_model:
+                raise ValueError("use_best_model needs an eval_set")
+            use_best_model = False
+        else:
+            if eval_group_id is None:
+                raise ValueError("a ranker's eval_set needs eval_group_id")
+            if self.early_stopping_rounds is not None and self.early_stopping_rounds < 1:
+                raise ValueError("early_stopping_rounds must be >= 1")
+            use_best_model = True if use_best_model is None else use_best_model
+        esr = self.early_stopping_rounds if validate else None
         dev = self.device
-        to = lambda t: None if t is None else t.to(dev).contiguous()   # noqa: E731
-        for k, v in sd["params"].items():
-            setattr(self, k, v)
-        self.model_ = ops.GBDTModel(to(sd["splits"]), to(sd["leaf_values"]), to(sd["is_cat"]), sd["depth"], sd["f0"],
-                                    sd["splits"].shape[0])
-        self.borders_, self.n_borders_, self.n_bins_ = to(sd["borders"]), to(sd["n_borders"]), to(sd["n_bins"])
-        self.vocab_, self._fitted_names = sd["vocab"], tuple(sd["names"])
-        self.feature_names_ = list(self._fitted_names[0]) + list(self._fitted_names[1])
-        self.best_iteration_, self.best_score_, self.evals_result_ = sd["best_iteration"], sd["best_score"], sd["evals_result"]
-        self.tree_count_ = self.model_.n_trees
+
+        def a_positive(n_pos, n_neg):
+            if n_pos == 0:
+                raise ValueError("no group holds a positive: QuerySoftMax has nothing to train on")
+
+        bins, y, is_cat, _ = self._fit_columns(X, y, a_positive)
+        F, R = bins.shape
+        if len(group_id) != R:
+            raise ValueError(f"group_id has {len(group_id)} ids for {R} rows")
+        plan = self.group_plan_ = ops.GBDTGroupPlan(group_id, dev)
+        bins = bins.index_select(1, plan.order).contiguous()      # group order, once
+        y = y.index_select(0, plan.order).contiguous()
+        T = self.iterations
+        model = self._new_model(is_cat, 0.0)
+
+        if validate:
+            Xv, yv = eval_set
+            yv = torch.as_tensor(np.asarray(yv) if not torch.is_tensor(yv) else yv).to(dev, torch.float32).reshape(-1)
+            yv = yv.contiguous()
+            _fit_eval_labels(yv, eval_metric)
+            gv = _fit_eval_groups(yv, eval_group_id, "NDCG" if metric == "QuerySoftMax" else eval_metric)
+            bins_v = self._bins(Xv)
+            if bins_v.shape[1] != yv.numel():
+                raise ValueError(f"eval_set has {bins_v.shape[1]} rows for {yv.numel()} labels")
+            plan_v = ops.GBDTGroupPlan(gv, dev)
+            yv_grouped = yv.index_select(0, plan_v.order).contiguous()
+            Fv = torch.zeros(yv.numel(), device=dev, dtype=torch.float32)
+            self.evals_result_ = {"learn": {"QuerySoftMax": []},
+                                  "validation": {"QuerySoftMax": [], "NDCG": [], "QueryAUC": []}}
+            self.best_iteration_, self.best_score_ = None, None
+        best, since, scored = None, 0, 0
+
+        Fx = torch.zeros(R, device=dev, dtype=torch.float32)
+        scratch = ops.GBDTScratch(R, F, self.depth, dev)
+        keep = set(int(t) for t in record_approximants)
+        self.approximants_ = {}
+        built = 0
+        for t in range(T):
+            ops.gbdt_tree(bins, y, Fx, is_cat, self.n_bins_, self.depth, self.learning_rate, self.l2_leaf_reg,
+                          model.splits[t], model.leaf_values[t], scratch, groups=plan)
+            built = t + 1
+            if built in keep:
+                self.approximants_[built] = Fx.clone()
+            if not validate or (built % self.metric_period != 0 and built != T):
+                continue
+            ops.gbdt_predict(bins_v, model, ntree_begin=scored, ntree_end=built, init=Fv, out=Fv)
+            scored = built
+            learn = ops.query_softmax_eval(Fx, y, plan)
+            val = ops.query_softmax_eval(Fv.index_select(0, plan_v.order), yv_grouped, plan_v)
+            grp = ops.group_eval(Fv, yv, gv, top=top)
+            host = torch.cat([learn._buf, val._buf, grp._buf]).cpu()      # the one host read
+            grp = grp._result(host[4:10])
+            now = {"QuerySoftMax": val._result(host[2:4])["loss"], "NDCG": grp["ndcg"], "QueryAUC": grp["query_auc"]}
+            ev = self.evals_result_
+            ev["learn"]["QuerySoftMax"].append(learn._result(host[:2])["loss"])
+            for name, value in now.items():
+                ev["validation"][name].append(value)
+            score = -now["QuerySoftMax"] if metric == "QuerySoftMax" else now[metric]
+            if best is None or score > best:
+                best, since = score, 0
+                self.best_iteration_ = t
+                self.best_score_ = {"validation": now}
+            else:
+                since += 1
+            if esr is not None and since >= esr:
+                break
+        ops._GBDT_GUARD.watch(scratch.flag)      # a range error is reported by the next gbdt call, or by check()
+        model.n_trees = self.best_iteration_ + 1 if (validate and use_best_model) else built
+        self.tree_count_ = model.n_trees
         return self
+
+    def predict(self, X, ntree_end=None):
+        """The raw scores [R] (fp32 device tensor, the rows in X's order) after the first ntree_end trees
+        (default: tree_count_): what orders the rows of a group. predict_logits under CatBoost's name."""
+        return self.predict_logits(X, ntree_end)

@@ -17,7 +17,9 @@ ops.group_eval (rsx_group_eval: per-query NDCG@top and QueryAUC; evaluate(group_
 fit(eval_group_id=..., eval_metric="NDCG" | "NDCG:top=K" | "QueryAUC")); retrieval
 (user_vec @ item_vectors.T -> topk, :193-196) = rsx_retrieve_topk (see ops.retrieve_topk). The
 boosted-tree ranker itself (RecommendationRanker, :95-149) runs on the device as backend "native":
-oblivious_gbdt.ObliviousBoostingClassifier (rsx_gbdt_*), served in batches through rsx_rerank_tabular.
+oblivious_gbdt.ObliviousBoostingClassifier (rsx_gbdt_*), served in batches through rsx_rerank_tabular; with
+loss_function "QuerySoftMax" it is oblivious_gbdt.ObliviousBoostingRanker, trained on the rows' group ids
+(rsx_gbdt_tree_grouped) and served by its raw score.
 """
 from __future__ import annotations
 
@@ -489,24 +491,35 @@ class RecommendationRanker:
     use_best_model). backend "catboost": CatBoostClassifier, as the reference (constructing it needs
     catboost); "native": ObliviousBoostingClassifier (oblivious_gbdt.py: trained and served on the device,
     a model of its own, not CatBoost's trees); "auto": catboost where it imports, so nothing changes where
-    the class worked before, else native."""
+    the class worked before, else native. loss_function "QuerySoftMax" (backend "native" only; the default
+    stays "Logloss") builds the listwise ObliviousBoostingRanker instead: its rows carry the reference's
+    per-customer group id (utils/monitor/log_importer.py) as "group_id", it validates on NDCG@10, and
+    its scores are raw scores that order the candidates of a query, not probabilities."""
 
-    def __init__(self, model_path: str = None, backend: str = "auto"):
+    def __init__(self, model_path: str = None, backend: str = "auto", loss_function: str = "Logloss"):
         if backend not in ("auto", "catboost", "native"):
             raise ValueError(f'backend must be "auto", "catboost" or "native" (got {backend!r})')
+        if loss_function not in ("Logloss", "QuerySoftMax"):
+            raise ValueError(f'loss_function must be "Logloss" or "QuerySoftMax" (got {loss_function!r})')
+        if loss_function == "QuerySoftMax" and backend != "native":
+            raise ValueError('loss_function "QuerySoftMax" needs backend="native"')
         if backend == "auto":
             try:
                 import catboost  # noqa: F401
                 backend = "catboost"
             except ImportError:
                 backend = "native"
-        self.backend = backend
+        self.backend, self.loss_function = backend, loss_function
         self.engineer = FeatureEngineer()
         if backend == "catboost":
             from catboost import CatBoostClassifier
             self.model = CatBoostClassifier(iterations=1000, learning_rate=0.05, depth=6, loss_function="Logloss",
                                             eval_metric="AUC", verbose=100, early_stopping_rounds=50,
                                             cat_features=self.engineer.cat_features, random_seed=42)
+        elif loss_function == "QuerySoftMax":
+            from .oblivious_gbdt import ObliviousBoostingRanker
+            self.model = ObliviousBoostingRanker(iterations=1000, learning_rate=0.05, depth=6, early_stopping_rounds=50,
+                                                 cat_features=self.engineer.cat_features)
         else:
             from .oblivious_gbdt import ObliviousBoostingClassifier
             self.model = ObliviousBoostingClassifier(iterations=1000, learning_rate=0.05, depth=6,
@@ -519,14 +532,21 @@ class RecommendationRanker:
     def train(self, train_data: List[Dict], val_data: List[Dict] = None):
         """Reference :114-137: train_data / val_data are FeatureEngineer.prepare_batch rows with a "label"
         (1 = bought). With val_data the model is validated on it (AUC), stops early and keeps its best
-        iteration."""
+        iteration. With loss_function "QuerySoftMax" every row also carries its "group_id" (an integer >= 0;
+        ValueError when one is missing) and the validation metric is NDCG@10."""
         df = self.engineer.prepare_batch(train_data)
         X, y = df.drop(columns=["target"]), df["target"]
         eval_set = None
         if val_data:
             dv = self.engineer.prepare_batch(val_data)
             eval_set = (dv.drop(columns=["target"]), dv["target"])
-        if self.backend == "catboost":
+        if self.loss_function == "QuerySoftMax":
+            groups = [_row_group_ids(rows, name) for rows, name in ((train_data, "train_data"), (val_data, "val_data"))]
+            self.model.fit(X, y.to_numpy(), groups[0],
+                           eval_set=None if eval_set is None else (eval_set[0], eval_set[1].to_numpy()),
+                           eval_group_id=groups[1], eval_metric="NDCG:top=10",
+                           use_best_model=True if eval_set is not None else None)
+        elif self.backend == "catboost":
             self.model.fit(X, y, eval_set=eval_set, use_best_model=True)
         else:
             self.model.fit(X, y.to_numpy(), eval_set=None if eval_set is None else (eval_set[0], eval_set[1].to_numpy()),
@@ -541,7 +561,27 @@ class RecommendationRanker:
         self.is_fitted = True
 
     def predict_proba(self, X) -> np.ndarray:
+        if self.loss_function == "QuerySoftMax":
+            raise TypeError("a QuerySoftMax ranker scores, it has no probabilities: use predict")
         return self.model.predict_proba(X)[:, 1]
+
+    def predict(self, X) -> np.ndarray:
+        """The scores that order the rows X (a host array): the raw scores of a QuerySoftMax ranker, else the
+        probabilities of class 1."""
+        if self.loss_function == "QuerySoftMax":
+            return self.model.predict(X).cpu().numpy()
+        return self.predict_proba(X)
+
+
+def _row_group_ids(rows, name):
+    """The "group_id" of every row of train_data / val_data as an int64 tensor (None for no rows)."""
+    if not rows:
+        return None
+    missing = sum(1 for d in rows if "group_id" not in d)
+    if missing:
+        raise ValueError(f'{name}: {missing} of {len(rows)} rows carry no "group_id" (loss_function "QuerySoftMax" '
+                         "ranks within groups)")
+    return torch.tensor([int(d["group_id"]) for d in rows], dtype=torch.int64)
 
 
 _HASH_ITEM, _HASH_USER, _HASH_FIELD = 0x9E3779B1, 0x85EBCA77, 0xC2B2AE35
@@ -590,7 +630,9 @@ class ReRankingSystem:
                      "two_tower_score": float(s), "user_vector": uv[0].cpu().numpy(),
                      "item_vector": self.item_vectors[int(i)].cpu().numpy()}
                     for s, i in zip(top_scores[0].tolist(), idx.tolist())]
-            probs = self.ranker.predict_proba(self.ranker.engineer.prepare_batch(rows))
+            frame = self.ranker.engineer.prepare_batch(rows)
+            listwise = getattr(self.ranker, "loss_function", "Logloss") == "QuerySoftMax"
+            probs = self.ranker.predict(frame) if listwise else self.ranker.predict_proba(frame)
         order = np.argsort(probs)[::-1][:final_k]
         idx_cpu = idx.cpu().numpy()
         sc_cpu = top_scores[0].cpu().numpy()
@@ -612,7 +654,8 @@ class ReRankingSystem:
         ops.rerank_tabular (the numeric FeatureEngineer columns of every candidate from the item
         vectors and the per-item / per-user price tensors) -> ops.gbdt_bin with the model's borders,
         the categorical codes gathered from per-item code tables built once from item_db_metadata ->
-        ops.gbdt_predict -> torch.topk. user_buckets and features are not used."""
+        ops.gbdt_predict -> torch.topk. user_buckets and features are not used. A QuerySoftMax ranker orders by
+        its raw score and returns it as the final score (no sigmoid)."""
         if _is_native_ranker(self.ranker):
             if user_vectors is None:
                 raise ValueError("rerank_batch with the native tree ranker needs user_vectors [Q, d]")
@@ -712,7 +755,8 @@ class ReRankingSystem:
                 row.copy_(per_user.repeat_interleave(K))
             else:
                 row.zero_()
-        prob = torch.sigmoid(ops.gbdt_predict(bins, clf.model_)).view(Q, K)
+        raw = ops.gbdt_predict(bins, clf.model_).view(Q, K)
+        prob = raw if clf.loss_function == "QuerySoftMax" else torch.sigmoid(raw)      # a ranker's score is its raw score
         top_p, top_j = torch.topk(prob, final_k, dim=1)
         return torch.gather(cand_ids, 1, top_j), torch.gather(cand_scores, 1, top_j), top_p
 

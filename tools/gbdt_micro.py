@@ -11,6 +11,10 @@ min over indices, prediction by gathers; integer sums, so it builds the same tre
            search and the leaf update (device events, median).
   predict  ops.gbdt_predict at --predict-rows rows (4096 queries x 100 candidates) under the fitted model.
 
+--loss QuerySoftMax --group-size N times the listwise objective instead (rank_main): the grouped gradient
+stage against its PyTorch restatement and one grouped tree against a Logloss tree, at --fit-rows rows in
+groups of N; it writes profiles/gbdt_rank_micro_gN.json.
+
 Before timing, the two forms' first trees are compared (the splits exactly, the leaf values to fp32
 rounding) and their predictions within fp32 summation error. Writes --out (profiles/gbdt_micro.json)."""
 import argparse
@@ -25,7 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import recsys_amd  # noqa: E402,F401
 from recsys_amd import ops  # noqa: E402
-from recsys_amd.temp_model.oblivious_gbdt import ObliviousBoostingClassifier  # noqa: E402
+from recsys_amd.temp_model.oblivious_gbdt import ObliviousBoostingClassifier, ObliviousBoostingRanker  # noqa: E402
 
 CARDS = (4, 3, 40, 12, 5)
 INV = 1.0 / ops.GBDT_SCALE
@@ -121,8 +125,70 @@ def wall_ms(fn):
     return (time.perf_counter() - t0) * 1e3, out
 
 
+def torch_grad_query_softmax(Fx, y, row_group, G):
+    """The QuerySoftMax gradients in PyTorch ops, no host read: scatter_reduce(amax), exp, index_add_ (a
+    float64 sum where the kernel has an int64 one). Returns (qg, qh) int32."""
+    rg = row_group.long()
+    m = torch.full((G,), float("-inf"), device=Fx.device).scatter_reduce(0, rg, Fx, "amax")
+    e = torch.exp(Fx.double() - m[rg].double())
+    Z = torch.zeros(G, device=Fx.device, dtype=torch.float64).index_add_(0, rg, e)
+    S = torch.zeros(G, device=Fx.device).index_add_(0, rg, y)
+    p = (e / Z[rg]).float()
+    live = S[rg] > 0
+    t = torch.where(y == 1, (1.0 / S.clamp(min=1.0))[rg], torch.zeros_like(y))
+    g = torch.where(live, t - p, torch.zeros_like(p))
+    h = torch.where(live, p * (1.0 - p), torch.zeros_like(p))
+    return (torch.round(g.double() * ops.GBDT_SCALE).int(), torch.round(h.double() * ops.GBDT_SCALE).int())
+
+
+def rank_main(a):
+    """--loss QuerySoftMax: the gradient stage (native against the PyTorch restatement) and one grouped tree
+    (against a Logloss tree of the same build) at --fit-rows rows in groups of --group-size, the two forms
+    alternating --repeats times (device events, the median of --iters calls each time)."""
+    dev = torch.device("cuda", 0)
+    R, F, depth, lr, l2 = a.fit_rows, 12, 6, 0.05, 3.0
+    num, cat, y = make_rows(R, 1, dev)
+    gid = (torch.randperm(R, device=dev, generator=torch.Generator(device=dev).manual_seed(5)) // a.group_size)
+    rk = ObliviousBoostingRanker(iterations=a.check_trees, device=dev).fit((num, cat), y, gid)
+    plan, model = rk.group_plan_, rk.model_
+    bins = rk._bins((num, cat)).index_select(1, plan.order).contiguous()
+    yg = y.index_select(0, plan.order).contiguous()
+    Fx = ops.gbdt_predict(bins, model)
+    qg, qh = ops.gbdt_grad_query_softmax(Fx, yg, plan)
+    tg, th = torch_grad_query_softmax(Fx, yg, plan.row_group, plan.G)
+    err = max(int((qg - tg).abs().max()), int((qh - th).abs().max())) / ops.GBDT_SCALE
+    assert err <= 2e-6, err
+    result = {"device": torch.cuda.get_device_name(0), "fit_rows": R, "columns": F, "depth": depth, "group_size": a.group_size,
+              "groups": plan.G, "iters": a.iters, "repeats": a.repeats, "max_abs_difference_to_torch": err,
+              "kernels_per_grouped_tree": 4 + 4 * depth, "fills_per_grouped_tree": 2 + depth}
+    scratch = ops.GBDTScratch(R, F, depth, dev)
+    sp, lv = model.splits[0].clone(), model.leaf_values[0].clone()
+    forms = {
+        "grad_native": lambda: ops.gbdt_grad_query_softmax(Fx, yg, plan, out=(qg, qh)),
+        "grad_torch": lambda: torch_grad_query_softmax(Fx, yg, plan.row_group, plan.G),
+        "grad_logloss": lambda: ops.gbdt_grad(Fx, yg, out=(qg, qh)),
+        "tree_grouped": lambda: ops.gbdt_tree(bins, yg, Fx.clone(), model.is_cat, rk.n_bins_, depth, lr, l2, sp, lv, scratch,
+                                              groups=plan),
+        "tree_logloss": lambda: ops.gbdt_tree(bins, yg, Fx.clone(), model.is_cat, rk.n_bins_, depth, lr, l2, sp, lv, scratch),
+    }
+    runs = {name: [] for name in forms}
+    for _ in range(a.repeats):
+        for name, fn in forms.items():
+            runs[name].append(events_ms(fn, 3, a.iters)[0])
+    ops._GBDT_GUARD.check()
+    result["ms_all"] = runs
+    result["ms"] = {name: statistics.median(v) for name, v in runs.items()}
+    result["torch_over_native_grad"] = result["ms"]["grad_torch"] / result["ms"]["grad_native"]
+    print("QuerySoftMax:", result, flush=True)
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as fh:
+        json.dump(result, fh, indent=1, sort_keys=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--loss", choices=("Logloss", "QuerySoftMax"), default="Logloss")
+    ap.add_argument("--group-size", type=int, default=6)
     ap.add_argument("--fit-rows", type=int, default=600_000)
     ap.add_argument("--predict-rows", type=int, default=409_600)
     ap.add_argument("--trees", type=int, default=1000)
@@ -130,8 +196,12 @@ def main():
     ap.add_argument("--check-trees", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join("profiles", "gbdt_micro.json"))
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.loss == "QuerySoftMax":
+        a.out = a.out or os.path.join("profiles", f"gbdt_rank_micro_g{a.group_size}.json")
+        return rank_main(a)
+    a.out = a.out or os.path.join("profiles", "gbdt_micro.json")
     dev = torch.device("cuda", 0)
     num, cat, y = make_rows(a.fit_rows, 1, dev)
     R, F, depth, lr, l2 = a.fit_rows, 12, 6, 0.05, 3.0
