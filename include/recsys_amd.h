@@ -1167,6 +1167,45 @@ int rsx_rerank_tabular(const int64_t* cand, const float* score, const float* U, 
                        const float* user_avg_price, int64_t Q, int64_t K, int64_t N, int64_t d, float* feats,
                        int64_t* ids, int* flag, void* stream);
 
+/* ---- A18 ranker training rows: purchase logs -> rows -> columns, csrc/ranker_rows.hip -----------------
+ * The reference builds the ranker's rows on the host: HMLogImporter (utils/monitor/log_importer.py:36-87)
+ * emits, per purchase, the positive and negative_ratio items drawn uniformly among those the customer has
+ * not bought (a rejection loop over Python's random), and FeatureEngineer.prepare_batch turns each row into
+ * columns with numpy. Here both run on the device.
+ *   sampling: the valid positives in order are pos_user, pos_item int32 [Pv] (user < C, item < N); customer
+ *          c's distinct bought items are bought[bought_off[c] .. bought_off[c + 1]) = s_0 < s_1 < ... (int32,
+ *          ascending and distinct; bought_off int64 [C + 1]), D_c of them, and M = N - D_c items are left.
+ *          With K = negative_ratio >= 0 the rows are row_user, row_item int32 and y fp32 [Pv (K + 1)]: row
+ *          p (K + 1) is positive p with y = 1 and rows p (K + 1) + 1 + k, k < K, its negatives with y = 0
+ *          (the reference's order, :59-84). Negative (p, k): h = hash_u32(seed, p K + k) (csrc/rsx_common.h),
+ *          r = ((uint64)h M) >> 32 in [0, M), item = r + #{j : s_j - j <= r}: the r-th item not in s, found
+ *          by one binary search over the non-decreasing s_j - j. For a uniform h this is the reference's
+ *          distribution (its rejection loop is uniform over the non-bought items too) up to the bias of the
+ *          multiply-shift map: an item's probability differs from 1 / M by less than 2^-32, a relative
+ *          bias of at most M / 2^32. The draw always terminates, is a function of (seed, p, k) alone and so
+ *          does not depend on the launch shape; Python's random stream is not reproduced.
+ *          flag (int32, OR-ed): bit 0 = a customer with M <= 0 (the reference would loop forever; the row's
+ *          item is 0), bit 1 = a pos_user outside [0, C) or a pos_item outside [0, N) (0 is used), or a bought
+ *          list that is not ascending and distinct within [0, N) (the item is clamped to N - 1). Offsets are
+ *          clamped to [0, n_bought]: no access leaves its array. One thread per row; no thread walks a list.
+ *   columns: rsx_pair_tabular gives the rows row_user, row_item int32 [R] the columns rsx_rerank_tabular
+ *          gives candidates: U [C, d], V [N, d], item_price [N], user_avg_price [C] -> feats fp32 [7, R].
+ *          Columns 1..6 come from the one device function both kernels call (csrc/rsx_pair_cols.h) and so
+ *          have the same bits for the same pair. Column 0 is score[r], or with score NULL the fp32 dot
+ *          product u . v of the same wave reduction (mean = dot / d). With y_out not NULL, y_out[r] = 1 where
+ *          row_item[r] is among truth[truth_off[u] .. truth_off[u + 1]) (int32 ascending and distinct,
+ *          truth_off int64 [C + 1], n_truth entries; a binary search), else 0. A user outside [0, C) or an
+ *          item outside [0, N) is replaced by 0 and sets flag bit 0. One wave per row, 1 <= d <= 65536.
+ * The only atomics are the integer ORs into flag: the same inputs give the same bits every run. Every loop
+ * is bounded by its array length or by 32 halvings. */
+int rsx_ranker_rows_sample(const int* pos_user, const int* pos_item, int64_t Pv, const int64_t* bought_off,
+                           const int* bought, int64_t n_bought, int64_t C, int64_t N, int64_t K, uint64_t seed,
+                           int* row_user, int* row_item, float* y, int* flag, void* stream);
+int rsx_pair_tabular(const int* row_user, const int* row_item, const float* score, const float* U, const float* V,
+                     const float* item_price, const float* user_avg_price, int64_t R, int64_t C, int64_t N, int64_t d,
+                     const int64_t* truth_off, const int* truth, int64_t n_truth, float* feats, float* y_out, int* flag,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

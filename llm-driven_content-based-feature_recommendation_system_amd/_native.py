@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 16 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 17 # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -228,6 +228,9 @@ _SIGS = {
                                     c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "rsx_gbdt_predict": (c_i,[c_p, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
     "rsx_rerank_tabular": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p]),
+    "rsx_ranker_rows_sample": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_pair_tabular": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p,
+                               c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

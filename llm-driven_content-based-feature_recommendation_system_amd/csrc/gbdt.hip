@@ -21,6 +21,7 @@
 // rsx_gbdt_tree_grouped runs the same levels on the QuerySoftMax gradients of gbdt_rank.hip.
 #include "rsx_block.h"
 #include "rsx_common.h"
+#include "rsx_pair_cols.h"
 
 namespace {
 
@@ -263,32 +264,9 @@ __global__ __launch_bounds__(kThreads) void rerank_k(const int64_t* __restrict__
     if (lane == 0) atomicOr(flag, 1);
     id = 0;
   }
-  const float* u = U + q * d;
-  const float* v = V + id * d;
-  float sum = 0.0f, mx = -__builtin_huge_valf();
-  for (int i = lane; i < d; i += 64) {
-    const float p = u[i] * v[i];
-    sum += p;
-    mx = rsx::fmax_nan(mx, p);
-  }
-  sum = rsx::wave_sum_width(sum, 64);
-  for (int o = 32; o > 0; o >>= 1) mx = rsx::fmax_nan(mx, __shfl_xor(mx, o, 64));
-  const float mean = sum / (float)d;
-  float ss = 0.0f;
-  for (int i = lane; i < d; i += 64) {
-    const float t = u[i] * v[i] - mean;
-    ss += t * t;
-  }
-  ss = rsx::wave_sum_width(ss, 64);
+  rsx::pair_columns(U + q * d, V + id * d, d, lane, price + id, avg + q, feats, R, c);   // columns 1..6
   if (lane != 0) return;
-  const float pr = price[id], a = avg[q];
   feats[c] = score[c];
-  feats[R + c] = mean;
-  feats[2 * R + c] = mx;
-  feats[3 * R + c] = sqrtf(ss / (float)d);
-  feats[4 * R + c] = pr;
-  feats[5 * R + c] = a;
-  feats[6 * R + c] = a > 0.0f ? (pr - a) / a : 0.0f;
   ids[c] = id;
 }
 

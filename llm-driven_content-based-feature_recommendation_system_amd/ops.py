@@ -4413,6 +4413,121 @@ def rerank_tabular(cand_ids, cand_scores, user_vectors, item_vectors, item_price
 
 
 # ----------------------------------------------------------------------------------------
+# A18 the ranker's training rows (csrc/ranker_rows.hip; include/recsys_amd.h, "ranker training rows")
+_RANKER_ROWS_GUARD = IdRangeGuard("ranker_sample_rows: a positive's user or item, a bought list, or a customer who "
+                                  "bought every item (nothing to draw a negative from)")
+_PAIR_GUARD = IdRangeGuard("pair_tabular row users or items")
+
+
+def _i32_rows(fn, name, t, ref=None, n=None):
+    """t is a 1-D int32 tensor (on ref's device, of n elements); returned contiguous."""
+    if t.dtype != torch.int32:
+        raise TypeError(f"{fn}: {name} must be int32, got {t.dtype}")
+    if ref is not None and t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+    if t.dim() != 1 or (n is not None and t.numel() != n):
+        want = "" if n is None else f" of {n} elements"
+        raise ValueError(f"{fn}: {name} must be a vector{want}, got shape {tuple(t.shape)}")
+    return _c(t)
+
+
+def ranker_sample_rows(pos_user, pos_item, bought_off, bought, n_items, negative_ratio, seed):
+    """HMLogImporter's rows (utils/monitor/log_importer.py:59-84) on rsx_ranker_rows_sample: for the valid
+    positives pos_user, pos_item int32 [Pv] in order, (row_user int32, row_item int32, y fp32), each
+    [Pv (K + 1)] with K = negative_ratio >= 0: positive p with y = 1, then its K negatives with y = 0, each
+    drawn uniformly (bias <= M / 2^32) among the M = n_items - D items customer pos_user[p] has not bought.
+    The customers' distinct bought items are the CSR of first_hit: bought_off int64 [C + 1], bought int32
+    ascending and distinct per customer. Negative (p, k) is a function of (seed, p K + k) alone (no rejection
+    loop: the specification is in include/recsys_amd.h). A customer with M <= 0, a positive outside [0, C) x
+    [0, n_items) or a malformed bought list raises IndexError at a later call (_RANKER_ROWS_GUARD.check())."""
+    fn = "ranker_sample_rows"
+    N.ensure_device(pos_user)
+    pos_user = _i32_rows(fn, "pos_user", pos_user)
+    Pv = pos_user.numel()
+    pos_item = _i32_rows(fn, "pos_item", pos_item, pos_user, Pv)
+    K, n_items, seed = int(negative_ratio), int(n_items), int(seed)
+    if K < 0:
+        raise ValueError(f"{fn}: negative_ratio must be >= 0 (got {K})")
+    if not 1 <= n_items < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= n_items < 2^31 (got {n_items})")
+    if Pv < 1 or Pv * (K + 1) >= 2 ** 31:
+        raise ValueError(f"{fn}: need Pv >= 1 and Pv (negative_ratio + 1) < 2^31 (got {Pv}, {K})")
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"{fn}: seed must be in [0, 2^64) (got {seed})")
+    if bought_off.dim() != 1 or bought_off.numel() < 2:
+        raise ValueError(f"{fn}: bought_off must hold C + 1 >= 2 offsets, got shape {tuple(bought_off.shape)}")
+    C = bought_off.numel() - 1
+    bought_off, bought = _truth_csr(fn, bought_off, bought, C, pos_user)
+    if bought.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: bought holds {bought.numel()} >= 2^31 entries")
+    R = Pv * (K + 1)
+    dev = pos_user.device
+    row_user = torch.empty(R, device=dev, dtype=torch.int32)
+    row_item = torch.empty(R, device=dev, dtype=torch.int32)
+    y = torch.empty(R, device=dev, dtype=torch.float32)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("gbdt/ranker_sample_rows"):
+        N.check(N.lib().rsx_ranker_rows_sample(N.ptr(pos_user), N.ptr(pos_item), Pv, N.ptr(bought_off), N.ptr(bought),
+                                               bought.numel(), C, n_items, K, seed, N.ptr(row_user), N.ptr(row_item),
+                                               N.ptr(y), N.ptr(flag), N.stream()), fn)
+    _RANKER_ROWS_GUARD.watch(flag)
+    return row_user, row_item, y
+
+
+def pair_tabular(row_user, row_item, score, user_vectors, item_vectors, item_price, user_avg_price, truth_off=None,
+                 truth=None):
+    """The FeatureEngineer numeric columns of the rows (row_user[r], row_item[r]), int32 [R]: feats fp32 [7, R]
+    in the order RERANK_TABULAR_COLUMNS on rsx_pair_tabular, one wave per row. user_vectors [C, d],
+    item_vectors [N, d], item_price [N], user_avg_price [C], all fp32 on the device. Columns 1..6 have the bits
+    rerank_tabular gives the same pair (one device function); column 0 is score [R] fp32, or with score None
+    the fp32 dot product of the pair's vectors. With truth_off int64 [C + 1] and truth int32 (the CSR of
+    first_hit) the result is (feats, y): y fp32 [R] = 1 where the row's item is in its user's truth set. A
+    user outside [0, C) or an item outside [0, N) reads row 0 and raises IndexError at a later call."""
+    fn = "pair_tabular"
+    N.ensure_device(row_user)
+    row_user = _i32_rows(fn, "row_user", row_user)
+    R = row_user.numel()
+    row_item = _i32_rows(fn, "row_item", row_item, row_user, R)
+    if not 1 <= R < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= R < 2^31 rows (got {R})")
+    if score is not None:
+        _f32(fn, "score", score, row_user)
+        if score.dim() != 1 or score.numel() != R:
+            raise ValueError(f"{fn}: score must be a vector of {R} elements, got shape {tuple(score.shape)}")
+    d = _rows2(fn, "user_vectors", user_vectors)
+    if _rows2(fn, "item_vectors", item_vectors) != d:
+        raise ValueError(f"{fn}: need user_vectors [C, d] and item_vectors [N, d] (got {tuple(user_vectors.shape)} and "
+                         f"{tuple(item_vectors.shape)})")
+    C, n_items = user_vectors.shape[0], item_vectors.shape[0]
+    if C < 1 or n_items < 1 or not 1 <= d <= 65536:
+        raise ValueError(f"{fn}: need C, N >= 1 and 1 <= d <= 65536 (got {C}, {n_items}, {d})")
+    for name, t in (("user_vectors", user_vectors), ("item_vectors", item_vectors)):
+        if t.device != row_user.device:
+            raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {row_user.device}")
+    if item_price is None or user_avg_price is None:
+        raise ValueError(f"{fn}: item_price and user_avg_price are needed")
+    _f32_vec(fn, "item_price", item_price, n_items, row_user)
+    _f32_vec(fn, "user_avg_price", user_avg_price, C, row_user)
+    if (truth_off is None) != (truth is None):
+        raise ValueError(f"{fn}: truth_off and truth come together")
+    y = None
+    if truth is not None:
+        truth_off, truth = _truth_csr(fn, truth_off, truth, C, row_user)
+        if truth.numel() >= 2 ** 31:
+            raise ValueError(f"{fn}: truth holds {truth.numel()} >= 2^31 entries")
+        y = torch.empty(R, device=row_user.device, dtype=torch.float32)
+    feats = torch.empty(len(RERANK_TABULAR_COLUMNS), R, device=row_user.device, dtype=torch.float32)
+    flag = torch.zeros(1, device=row_user.device, dtype=torch.int32)
+    with timed("gbdt/pair_tabular"):
+        N.check(N.lib().rsx_pair_tabular(N.ptr(row_user), N.ptr(row_item), N.ptr(_c(score)), N.ptr(_c(user_vectors)),
+                                         N.ptr(_c(item_vectors)), N.ptr(_c(item_price)), N.ptr(_c(user_avg_price)), R, C,
+                                         n_items, d, N.ptr(truth_off), N.ptr(truth), 0 if truth is None else truth.numel(),
+                                         N.ptr(feats), N.ptr(y), N.ptr(flag), N.stream()), fn)
+    _PAIR_GUARD.watch(flag)
+    return feats if y is None else (feats, y)
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 

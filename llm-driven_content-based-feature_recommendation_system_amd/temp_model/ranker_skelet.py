@@ -19,7 +19,9 @@ fit(eval_group_id=..., eval_metric="NDCG" | "NDCG:top=K" | "QueryAUC")); retriev
 boosted-tree ranker itself (RecommendationRanker, :95-149) runs on the device as backend "native":
 oblivious_gbdt.ObliviousBoostingClassifier (rsx_gbdt_*), served in batches through rsx_rerank_tabular; with
 loss_function "QuerySoftMax" it is oblivious_gbdt.ObliviousBoostingRanker, trained on the rows' group ids
-(rsx_gbdt_tree_grouped) and served by its raw score.
+(rsx_gbdt_tree_grouped) and served by its raw score. RecommendationRanker.train_rows fits either from rows that
+stay on the device (utils/monitor/log_importer.py: HMLogImporter.load_rows; ReRankingSystem.training_rows), with
+the columns of rsx_pair_tabular, whose arithmetic is rsx_rerank_tabular's.
 """
 from __future__ import annotations
 
@@ -553,6 +555,64 @@ class RecommendationRanker:
                            eval_metric="AUC", use_best_model=True if eval_set is not None else None)
         self.is_fitted = True
 
+    # the FeatureEngineer categorical columns train_rows builds, in the model's order: column -> (whose meta, its key)
+    _ROW_CATS = (("season", "user", "season"), ("gender", "user", "gender"), ("item_category", "item", "category"),
+                 ("item_material", "item", "material"), ("item_fit", "item", "fit"))
+
+    @torch.no_grad()
+    def train_rows(self, rows, item_vectors, user_vectors, item_metadata, user_meta=None, val_rows=None):
+        """train without the host rows: rows / val_rows are RankerRows (utils/monitor/log_importer.py:
+        HMLogImporter.load_rows, ReRankingSystem.training_rows): row_user, row_item int32 [R] into
+        user_vectors [C, d] and item_vectors [N, d], y, group_id and the retrieval score or None, all on the
+        device. Backend "native" only (TypeError otherwise). The numeric columns are ops.pair_tabular's (the
+        arithmetic of the serving path, ops.rerank_tabular: columns 1..6 of a pair have the same bits in both;
+        with score None the two-tower score is the pair's dot product), in the order ops.RERANK_TABULAR_COLUMNS.
+        The categorical columns season, gender, item_category, item_material, item_fit are gathered from
+        per-user and per-item code tables whose vocabularies are built once from the metadata dicts
+        (item_metadata: {item row: dict}, user_meta: C dicts, default {}; a missing key reads "unknown"), in
+        the order of first occurrence over the tables. No per-row Python: the host loops run over the N items
+        and the C users. The model is fitted through fit((numeric, codes), y[, group_id]) and then carries the
+        FeatureEngineer column names and these vocabularies, so ReRankingSystem.rerank_batch /
+        recommend_batch serve it and save_model / load_model round-trip it. With val_rows the model validates
+        as train does (AUC, or NDCG@10 for QuerySoftMax), stops early and keeps its best iteration."""
+        if self.backend != "native":
+            raise TypeError(f'train_rows needs backend="native" (this ranker\'s is {self.backend!r})')
+        dev = rows.row_user.device
+        n, C = item_vectors.shape[0], user_vectors.shape[0]
+        user_meta = [{}] * C if user_meta is None else list(user_meta)
+        if len(user_meta) != C:
+            raise ValueError(f"user_meta holds {len(user_meta)} dicts for {C} user vectors")
+        metas = {"item": [item_metadata.get(i, {}) for i in range(n)], "user": user_meta}
+        price = torch.tensor([float(m.get("price", 0)) for m in metas["item"]], dtype=torch.float32, device=dev)
+        avg = torch.tensor([float(m.get("avg_price", 0.0)) for m in metas["user"]], dtype=torch.float32, device=dev)
+        vocabs, tables = [], []
+        for name, side, key in self._ROW_CATS:
+            vocab = {}
+            codes = np.fromiter((vocab.setdefault(m.get(key, "unknown"), len(vocab) + 1) for m in metas[side]), np.int64,
+                                len(metas[side]))
+            if len(vocab) > 255:
+                raise ValueError(f"categorical column {name!r} has {len(vocab)} distinct values: at most 255 are supported")
+            vocabs.append(vocab)
+            tables.append((side, torch.from_numpy(codes).to(dev)))
+
+        def columns(r):
+            feats = ops.pair_tabular(r.row_user, r.row_item, r.score, user_vectors, item_vectors, price, avg)
+            idx = {"user": r.row_user.long(), "item": r.row_item.long()}
+            return feats.t(), torch.stack([t.index_select(0, idx[side]) for side, t in tables], dim=1)
+
+        X = columns(rows)
+        have_val = val_rows is not None and len(val_rows) > 0
+        eval_set = (columns(val_rows), val_rows.y) if have_val else None
+        if self.loss_function == "QuerySoftMax":
+            self.model.fit(X, rows.y, rows.group_id, eval_set=eval_set,
+                           eval_group_id=val_rows.group_id if have_val else None, eval_metric="NDCG:top=10",
+                           use_best_model=True if have_val else None)
+        else:
+            self.model.fit(X, rows.y, eval_set=eval_set, eval_metric="AUC", use_best_model=True if have_val else None)
+        names = (list(ops.RERANK_TABULAR_COLUMNS), [name for name, _, _ in self._ROW_CATS])
+        self.model._fitted_names, self.model.feature_names_, self.model.vocab_ = names, names[0] + names[1], vocabs
+        self.is_fitted = True
+
     def save_model(self, path: str):
         self.model.save_model(path)
 
@@ -692,6 +752,28 @@ class ReRankingSystem:
             user_buckets = torch.arange(Q, device=self.device, dtype=torch.int64) % 1000
         sc, idx = ops.retrieve_topk(uv, self.item_vectors, top_k_retrieval)
         return self.rerank_batch(idx, sc, user_buckets, final_k)
+
+    @torch.no_grad()
+    def training_rows(self, user_vectors: torch.Tensor, truth_off: torch.Tensor, truth: torch.Tensor,
+                      top_k_retrieval: int = 100):
+        """The rows the reranker will see, as a RankerRows for RecommendationRanker.train_rows: the
+        top_k_retrieval <= N retrieved candidates of every user vector [Q, d] (ops.retrieve_topk, as
+        recommend_batch) with their retrieval scores, group = query, row_user = query, and y = 1 where the
+        candidate is in the query's truth set (the CSR of ops.first_hit: truth_off int64 [Q + 1], truth int32
+        ascending and distinct per query), labelled by rsx_pair_tabular's y_out. Everything stays on the
+        device; nothing is read back."""
+        from ..utils.monitor.log_importer import RankerRows
+        uv = user_vectors.to(self.device, torch.float32)
+        Q, n = uv.shape[0], self.item_vectors.shape[0]
+        k = int(top_k_retrieval)
+        if not 1 <= k <= n:
+            raise ValueError(f"top_k_retrieval must be in [1, {n}] (got {top_k_retrieval})")
+        sc, idx = ops.retrieve_topk(uv, self.item_vectors, k)
+        query = torch.arange(Q, device=self.device, dtype=torch.int32).repeat_interleave(k)
+        row_item = idx.reshape(-1).to(torch.int32)
+        zeros = torch.zeros(max(n, Q), device=self.device, dtype=torch.float32)      # the labels need no prices
+        _, y = ops.pair_tabular(query, row_item, None, uv, self.item_vectors, zeros[:n], zeros[:Q], truth_off, truth)
+        return RankerRows(query, row_item, y, query.clone(), sc.reshape(-1).to(torch.float32).contiguous())
 
 
     # the FeatureEngineer columns the meta dicts feed: column -> (whose meta, its key)
