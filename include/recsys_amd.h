@@ -1206,6 +1206,44 @@ int rsx_pair_tabular(const int* row_user, const int* row_item, const float* scor
                      const int64_t* truth_off, const int* truth, int64_t n_truth, float* feats, float* y_out, int* flag,
                      void* stream);
 
+/* ---- A19 ordered target statistics: wide categorical columns of the oblivious-tree model, csrc/gbdt_ts.hip ----
+ * The reference hands CatBoost six cat_features (temp_model/ranker_skelet.py:20-27, 106) and CatBoost encodes
+ * them by ordered target statistics. Here a categorical column with more known values than one_hot_max_size
+ * becomes one numeric column: one permutation, one prior; CatBoost's several permutations, feature combinations
+ * and counter statistics are not reproduced. For TS column k (its index among the TS columns of the call) with
+ * the codes c_i in [0, V_k] (0 = unknown / unseen, V_k <= GBDT_TS_MAX_CODES = 2^22), the labels y_i in {0, 1}
+ * and R < 2^31 rows in the caller's row order, the prior (p, a), a > 0, and ap = a * p formed once on the host in
+ * float64:
+ *   order:  k_i = hash_u32(ts_seed + k, i) (csrc/rsx_common.h). Row j precedes row i iff (k_j, j) < (k_i, i): a
+ *          total order, so nothing depends on a sort's tie-breaking.
+ *   training value: n_i = #{j precedes i, c_j = c_i}, s_i = #{such j with y_j = 1},
+ *          ts_i = (float)(((double)s_i + ap) / ((double)n_i + a)): two additions and one division in fp64,
+ *          nothing to contract, then one rounding to fp32. A row that is first of its code gets the prior value
+ *          (float)(ap / a), which is (float)p wherever a * p / a rounds back to p (the default (0.5, 1) does).
+ *   table:  N_c, S_c = the totals over all training rows of code c; table[c] = (float)((S_c + ap) / (N_c + a)),
+ *          the prior value for a code nobody had. Validation and serving rows read table[c]; a code outside
+ *          [0, V_k] reads table[0].
+ *   downstream: a TS column is a numeric column from there on: its borders are those of the ordered training
+ *          values, its bins rsx_gbdt_bin's, its is_cat entry 0. The model's internal column order is numeric,
+ *          then TS, then one-hot: that is the order in which ties between equally good splits are broken. At the
+ *          end of the fit each TS column keeps the byte table bins(table) uint8 [V_k + 1]: serving it is a
+ *          one-byte gather. Training rows see the ordered value and served rows the table's, so the prediction
+ *          on the training rows no longer equals the training approximant of a model with TS columns.
+ * rsx_gbdt_ts_keys writes keys int64 [Fts, R] = c_i << 32 | k_i; a stable ascending sort of each row of keys is
+ * order int64 [Fts, R] (ties fall to the row index: the order above inside every code). rsx_gbdt_ordered_ts walks
+ * that order on fixed 256-row tiles, one row per thread: a segmented exclusive scan of (1, y) over the runs of
+ * equal code inside the tile, one scan over the tiles' aggregates per column, and a second tile pass that adds
+ * the carry and scatters. No thread walks a run, no workgroup waits on another, every slot has one writer and all
+ * sums are integers: the same bits every run. codes int32 [Fts, R], y fp32 [R], V int32 [Fts] (device), Vmax >=
+ * every V_k the row stride - 1 of totals int32 [Fts, Vmax + 1, 2] = (N_c, S_c) and table fp32 [Fts, Vmax + 1]
+ * (both written whole), ts fp32 [Fts, R] in the caller's row order, ws 16 Fts ceil(R / 256) bytes, 16-byte
+ * aligned. flag (int32, OR-ed) bit 0: an order entry outside [0, R) (skipped) or a code outside [0, V_k] (its
+ * row gets the prior value and counts nowhere); no access leaves its array. */
+int rsx_gbdt_ts_keys(const int* codes, int64_t R, int Fts, uint64_t seed, int64_t* keys, void* stream);
+int rsx_gbdt_ordered_ts(const int* codes, const int64_t* order, const float* y, const int* V, int64_t R, int Fts,
+                        int64_t Vmax, double ap, double a, void* ws, int64_t ws_bytes, float* ts, int* totals,
+                        float* table, int* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

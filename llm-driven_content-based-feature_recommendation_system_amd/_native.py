@@ -231,6 +231,8 @@ _SIGS = {
     "rsx_ranker_rows_sample": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_u64, c_p, c_p, c_p, c_p, c_p]),
     "rsx_pair_tabular": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p,
                                c_p, c_p]),
+    "rsx_gbdt_ts_keys": (c_i, [c_p, c_i64, c_i, c_u64, c_p, c_p]),
+    "rsx_gbdt_ordered_ts": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i64, c_d, c_d, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -24,26 +24,13 @@
 
 namespace {
 
-using rsx::at, rsx::block_scan_excl, rsx::ordered_key, rsx::ordered_key_inv;
+using rsx::at, rsx::block_scan_excl, rsx::ordered_key, rsx::ordered_key_inv, rsx::Seg, rsx::SegOp;
 
 constexpr int kThreads = 256;      // rows per tile: one row per thread
 constexpr int kLossSlots = 1024;   // workgroups of qs_loss_k (each one partial)
 constexpr double kTwo32 = 4294967296.0;
 
-// ---- the segmented scan ---------------------------------------------------------------------------------
-// A value with "a segment starts here". op(earlier, later) keeps the later one when it starts a segment,
-// else combines: associative, so block_scan_excl scans every segment of the tile on its own.
-template <class V>
-struct Seg {
-  V v;
-  int head;
-};
-template <class V, class Op>
-struct SegOp {
-  __device__ __forceinline__ Seg<V> operator()(Seg<V> a, Seg<V> b) const {
-    return b.head ? b : Seg<V>{Op()(a.v, b.v), a.head};
-  }
-};
+// ---- the segmented scan (rsx_block.h: Seg, SegOp) over these values ---------------------------------------
 struct MaxU {
   __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const { return a > b ? a : b; }
 };

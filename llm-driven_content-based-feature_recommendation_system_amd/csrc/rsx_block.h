@@ -74,6 +74,21 @@ __device__ __forceinline__ T block_scan_excl(T x, Op op, T ident, T* sm, T& tota
   return op(pre, e);
 }
 
+// The segmented scan: a value with "a segment starts here". op(earlier, later) keeps the later one when it
+// starts a segment, else combines: associative, so block_scan_excl scans every segment of the tile on its
+// own, and the total is the tile's trailing piece with head = a segment starts somewhere in the tile.
+template <class V>
+struct Seg {
+  V v;
+  int head;
+};
+template <class V, class Op>
+struct SegOp {
+  __device__ __forceinline__ Seg<V> operator()(Seg<V> a, Seg<V> b) const {
+    return b.head ? b : Seg<V>{Op()(a.v, b.v), a.head};
+  }
+};
+
 // One step of a descending 8-bit radix select, called by every lane of ONE wave: count(bin) is the
 // number of keys in bin 0..255. Lane l takes the bins 255 - 4l ... 252 - 4l and a scan over the lanes
 // counts the keys above them. Returns true in exactly one lane, the owner of the bin where the running

@@ -4413,6 +4413,78 @@ def rerank_tabular(cand_ids, cand_scores, user_vectors, item_vectors, item_price
 
 
 # ----------------------------------------------------------------------------------------
+# A19 ordered target statistics of wide categorical columns (csrc/gbdt_ts.hip; include/recsys_amd.h, "ordered
+# target statistics")
+GBDT_TS_MAX_CODES = 1 << 22
+_GBDT_TS_TILE = 256
+_GBDT_TS_GUARD = IdRangeGuard("gbdt_ordered_ts: a code outside [0, V] or an order entry outside [0, R)")
+
+
+def _gbdt_ts_codes(fn, codes):
+    """codes is a contiguous int32 [Fts, R] device matrix, Fts <= 32, 1 <= R < 2^31; returns (Fts, R)."""
+    N.ensure_device(codes)
+    if codes.dtype != torch.int32:
+        raise TypeError(f"{fn}: codes must be int32, got {codes.dtype}")
+    if codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError(f"{fn}: codes must be a contiguous [Fts, R] matrix, got shape {tuple(codes.shape)}")
+    Fts, R = codes.shape
+    if not (1 <= Fts <= GBDT_MAX_FEATURES and 1 <= R < 2 ** 31):
+        raise ValueError(f"{fn}: need 1 <= Fts <= {GBDT_MAX_FEATURES} and 1 <= R < 2^31 (got Fts {Fts}, R {R})")
+    return Fts, R
+
+
+def gbdt_ts_plan(codes, seed=0):
+    """The order the ordered target statistics of codes int32 [Fts, R] run along: order int64 [Fts, R], per
+    column the rows by code and inside a code by (hash_u32(seed + column, row), row). rsx_gbdt_ts_keys writes the
+    keys code << 32 | hash and a stable torch.sort gives the order (ties fall to the row index). No host read."""
+    Fts, R = _gbdt_ts_codes("gbdt_ts_plan", codes)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64 - GBDT_MAX_FEATURES:
+        raise ValueError(f"gbdt_ts_plan: seed must be in [0, 2^64 - {GBDT_MAX_FEATURES}) (got {seed})")
+    keys = torch.empty(Fts, R, device=codes.device, dtype=torch.int64)
+    with timed("gbdt/ts_keys"):
+        N.check(N.lib().rsx_gbdt_ts_keys(N.ptr(codes), R, Fts, seed, N.ptr(keys), N.stream()), "gbdt_ts_keys")
+    return torch.sort(keys, dim=1, stable=True).indices
+
+
+def gbdt_ordered_ts(codes, order, y, V, prior=(0.5, 1.0)):
+    """Ordered target statistics (rsx_gbdt_ordered_ts) of the TS columns codes int32 [Fts, R] with the labels y
+    fp32 [R] in {0, 1} along order int64 [Fts, R] (gbdt_ts_plan): (ts fp32 [Fts, R] in the caller's row order,
+    totals int32 [Fts, Vmax + 1, 2] = (N_c, S_c), table fp32 [Fts, Vmax + 1]), Vmax = max(V). V: the largest
+    code of each column (host ints, <= GBDT_TS_MAX_CODES); prior = (p, a): ts_i = (s_i + a p) / (n_i + a) over
+    the rows of the same code that precede row i, table[c] = (S_c + a p) / (N_c + a). Integer sums: the same
+    bits every call. A code outside [0, V] or an order entry outside [0, R) gives the prior value, no access
+    leaves its array, and IndexError is raised at a later call (_GBDT_TS_GUARD.check())."""
+    fn = "gbdt_ordered_ts"
+    Fts, R = _gbdt_ts_codes(fn, codes)
+    if order.dtype != torch.int64 or tuple(order.shape) != (Fts, R) or not order.is_contiguous() or order.device != codes.device:
+        raise ValueError(f"{fn}: order must be a contiguous int64 [{Fts}, {R}] matrix on {codes.device}")
+    _gbdt_rows(fn, "y", y, torch.float32, R, codes)
+    V = [int(v) for v in V]
+    if len(V) != Fts or min(V) < 0:
+        raise ValueError(f"{fn}: V must hold {Fts} largest codes >= 0 (got {V})")
+    Vmax = max(V)
+    if Vmax > GBDT_TS_MAX_CODES:
+        raise ValueError(f"{fn}: a target-statistic column has at most {GBDT_TS_MAX_CODES} known values (got {Vmax})")
+    p, a = float(prior[0]), float(prior[1])
+    if not (a > 0 and math.isfinite(a) and 0.0 <= p <= 1.0):
+        raise ValueError(f"{fn}: prior must be (p in [0, 1], a > 0) (got {prior})")
+    dev = codes.device
+    Vd = torch.tensor(V, dtype=torch.int32, device=dev)
+    ts = torch.empty(Fts, R, device=dev, dtype=torch.float32)
+    totals = torch.empty(Fts, Vmax + 1, 2, device=dev, dtype=torch.int32)
+    table = torch.empty(Fts, Vmax + 1, device=dev, dtype=torch.float32)
+    ws = torch.empty(16 * Fts * ((R + _GBDT_TS_TILE - 1) // _GBDT_TS_TILE), device=dev, dtype=torch.uint8)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("gbdt/ordered_ts"):
+        N.check(N.lib().rsx_gbdt_ordered_ts(N.ptr(codes), N.ptr(order), N.ptr(y), N.ptr(Vd), R, Fts, Vmax, a * p, a,
+                                            N.ptr(ws), ws.numel(), N.ptr(ts), N.ptr(totals), N.ptr(table), N.ptr(flag),
+                                            N.stream()), fn)
+    _GBDT_TS_GUARD.watch(flag)
+    return ts, totals, table
+
+
+# ----------------------------------------------------------------------------------------
 # A18 the ranker's training rows (csrc/ranker_rows.hip; include/recsys_amd.h, "ranker training rows")
 _RANKER_ROWS_GUARD = IdRangeGuard("ranker_sample_rows: a positive's user or item, a bought list, or a customer who "
                                   "bought every item (nothing to draw a negative from)")

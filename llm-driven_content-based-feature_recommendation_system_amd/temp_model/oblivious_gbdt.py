@@ -7,8 +7,11 @@ use_best_model) over the FeatureEngineer columns. CatBoost's GPU trainer is CUDA
 save_model / load_model, best_iteration_, evals_result_). It is a model of its own, specified in
 include/recsys_amd.h ("oblivious-tree boosting") and restated by tests/gbdt_ref.py: plain (not ordered)
 boosting, quantile-free borders at the midpoints of the distinct values, categorical columns as one-hot
-candidates over host-built codes (no target statistics), no feature combinations. Parity with CatBoost's
-own trees is not claimed.
+candidates over host-built codes, no feature combinations. With one_hot_max_size (CatBoost's name) a
+categorical column with more known values than that is encoded by ordered target statistics instead
+(include/recsys_amd.h, "ordered target statistics"; ops.gbdt_ts_plan, ops.gbdt_ordered_ts; restated by
+tests/gbdt_ts_ref.py): one permutation and one prior, and the column is numeric from there on. Parity with
+CatBoost's own trees is not claimed.
 
 Compute: ops.gbdt_bin (borders -> bins), ops.gbdt_tree (one native call per tree: rsx_gbdt_grad,
 rsx_gbdt_histogram, rsx_gbdt_best_split, rsx_gbdt_apply_split), ops.gbdt_predict; the metrics on
@@ -70,7 +73,8 @@ class _ObliviousBoosting:
     loss_function = None
 
     def __init__(self, iterations=1000, learning_rate=0.05, depth=6, l2_leaf_reg=3.0, border_count=254,
-                 cat_features=None, early_stopping_rounds=None, metric_period=1, device=None):
+                 cat_features=None, early_stopping_rounds=None, metric_period=1, device=None, one_hot_max_size=None,
+                 ts_prior=(0.5, 1.0), ts_seed=0):
         if iterations < 1:
             raise ValueError("iterations must be >= 1")
         if not 1 <= depth <= ops.GBDT_MAX_DEPTH:
@@ -81,14 +85,31 @@ class _ObliviousBoosting:
             raise ValueError(f"border_count must be in [1, {ops.GBDT_MAX_BORDERS}] (got {border_count})")
         if metric_period < 1:
             raise ValueError("metric_period must be >= 1")
+        if one_hot_max_size is not None and not 1 <= one_hot_max_size <= _MAX_CODES:
+            raise ValueError(f"one_hot_max_size must be None or in [1, {_MAX_CODES}] (got {one_hot_max_size})")
+        p, a = (float(v) for v in ts_prior)
+        if not (0.0 <= p <= 1.0 and a > 0 and math.isfinite(a)):
+            raise ValueError(f"ts_prior must be (p in [0, 1], a > 0) (got {ts_prior})")
+        if not 0 <= ts_seed < 2 ** 63:
+            raise ValueError(f"ts_seed must be in [0, 2^63) (got {ts_seed})")
+        self.one_hot_max_size = None if one_hot_max_size is None else int(one_hot_max_size)
+        self.ts_prior, self.ts_seed = (p, a), int(ts_seed)
         self.iterations, self.learning_rate, self.depth = int(iterations), float(learning_rate), int(depth)
         self.l2_leaf_reg, self.border_count = float(l2_leaf_reg), int(border_count)
         self.cat_features = list(cat_features) if cat_features is not None else []
         self.early_stopping_rounds, self.metric_period = early_stopping_rounds, int(metric_period)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model_, self._fitted_names = None, None
+        self._no_ts()
         self.tree_count_ = 0
         self.evals_result_, self.best_iteration_, self.best_score_ = None, None, None
+
+    def _no_ts(self):
+        """The state of a model without target-statistic columns. ts_cols_: the positions, among the categorical
+        columns, of the TS columns; per TS column ts_table_ fp32 [V + 1], ts_totals_ int32 [V + 1, 2] = (N_c,
+        S_c) and ts_bins_ uint8 [V + 1] = the table's bins under ts_borders_ / ts_n_borders_."""
+        self.ts_cols_, self.ts_table_, self.ts_totals_, self.ts_bins_ = [], [], [], []
+        self.ts_borders_, self.ts_n_borders_ = None, None
 
     # ---- columns -> bins ---------------------------------------------------------------------------
     def _split_columns(self, X):
@@ -135,9 +156,44 @@ class _ObliviousBoosting:
         bins = torch.empty(Fn + Fc, R, device=self.device, dtype=torch.uint8)
         if Fn:
             ops.gbdt_bin(num, self.borders_, self.n_borders_, out=bins)
-        if Fc:
+        if Fc and not self.ts_cols_:
             bins[Fn:] = self._codes(cat, R)
+        elif Fc:
+            self._cat_bins(self._wide_codes(cat, R), bins, Fn)
         return bins
+
+    def _cat_rows(self, Fn, Fc):
+        """The row of bins each categorical column has: the numeric columns, then the TS columns, then the
+        one-hot ones, each kind in the caller's order."""
+        oh = [k for k in range(Fc) if k not in self.ts_cols_]
+        rows = {k: Fn + j for j, k in enumerate(self.ts_cols_)}
+        rows.update({k: Fn + len(self.ts_cols_) + j for j, k in enumerate(oh)})
+        return [rows[k] for k in range(Fc)]
+
+    def _cat_bins(self, codes, bins, Fn):
+        """bins rows Fn.. of served rows from codes int64 [Fc, R]: a TS column gathers its byte table (a code
+        outside [0, V] reads entry 0), a one-hot column is its code (outside [0, 255]: 0)."""
+        for k, row in enumerate(self._cat_rows(Fn, codes.shape[0])):
+            c = codes[k]
+            if k in self.ts_cols_:
+                bins[row] = self._ts_bins_of(k, c)
+            else:
+                bins[row] = torch.where((c < 0) | (c > _MAX_CODES), torch.zeros_like(c), c).to(torch.uint8)
+
+    def _ts_bins_of(self, k, c):
+        """The bins uint8 of the codes c (int64, any shape) of categorical column k, a TS column: one gather of
+        its byte table."""
+        table = self.ts_bins_[self.ts_cols_.index(k)]
+        return table[torch.where((c < 0) | (c >= table.numel()), torch.zeros_like(c), c)]
+
+    def _wide_codes(self, cat, R):
+        """The codes int64 [Fc, R] on the device: the tensor's own, or the vocabularies' (0 = unseen)."""
+        if torch.is_tensor(cat):
+            return cat
+        host = np.empty((len(cat), R), np.int64)
+        for k, (vals, vocab) in enumerate(zip(cat, self.vocab_)):
+            host[k] = [vocab.get(v, 0) for v in vals]
+        return torch.from_numpy(host).to(self.device)
 
     def _codes(self, cat, R):
         if torch.is_tensor(cat):
@@ -163,8 +219,9 @@ class _ObliviousBoosting:
         y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(dev, torch.float32).reshape(-1).contiguous()
         R = y.numel()
         stats = [(y == 1).sum(), (y == 0).sum()]
-        n_bins = [self.border_count + 1] * Fn
         self.vocab_ = []
+        self._no_ts()
+        ohm, known = self.one_hot_max_size, []      # known: the known values of every categorical column
         if Fc and torch.is_tensor(cat):
             stats += [cat.max(), cat.min()] + list(cat.max(dim=1).values)
         elif Fc:
@@ -173,11 +230,11 @@ class _ObliviousBoosting:
                 for v in vals:
                     if v not in vocab:
                         vocab[v] = len(vocab) + 1
-                if len(vocab) > _MAX_CODES:
+                if ohm is None and len(vocab) > _MAX_CODES:
                     raise ValueError(f"categorical column {name!r} has {len(vocab)} distinct values: at most "
                                      f"{_MAX_CODES} are supported (no target-statistic encoding)")
                 self.vocab_.append(vocab)
-                n_bins.append(len(vocab) + 1)
+                known.append(len(vocab))
         for name, block in (("numeric", num), ("categorical", cat)):
             n = None if block is None else (block.shape[1] if torch.is_tensor(block) else len(block[0]))
             if n is not None and n != R:
@@ -188,24 +245,54 @@ class _ObliviousBoosting:
             raise ValueError("labels must be 0 or 1")
         check_labels(n_pos, n_neg)
         if Fc and torch.is_tensor(cat):
-            if host[2] > _MAX_CODES or host[3] < 0:
+            if ohm is None and (host[2] > _MAX_CODES or host[3] < 0):
                 raise ValueError(f"categorical codes must be in [0, {_MAX_CODES}] (got {host[3]} .. {host[2]}): at most "
                                  f"{_MAX_CODES} known values besides 0 = unknown")
-            n_bins += [m + 1 for m in host[4:]]
+            if host[3] < 0:
+                raise ValueError(f"categorical codes must be >= 0 (got {host[3]})")
+            known = host[4:]
+        if ohm is not None:
+            self.ts_cols_ = [k for k, n in enumerate(known) if n > ohm]
+            for k in self.ts_cols_:
+                if known[k] > ops.GBDT_TS_MAX_CODES:
+                    raise ValueError(f"categorical column {cats[k]!r} has {known[k]} known values: a target-statistic "
+                                     f"column takes up to {ops.GBDT_TS_MAX_CODES}")
+        Fts = len(self.ts_cols_)
+        one_hot = [k for k in range(Fc) if k not in self.ts_cols_]
+        n_bins = [self.border_count + 1] * (Fn + Fts) + [known[k] + 1 for k in one_hot]
         self._fitted_names = (nums, cats)
         self.feature_names_ = nums + cats
         if Fn:
             self.borders_, self.n_borders_ = build_borders(num, self.border_count)
         else:
             self.borders_, self.n_borders_ = None, None
-        is_cat = torch.tensor([0] * Fn + [1] * Fc, dtype=torch.uint8, device=dev)
+        is_cat = torch.tensor([0] * (Fn + Fts) + [1] * len(one_hot), dtype=torch.uint8, device=dev)
         self.n_bins_ = torch.tensor(n_bins, dtype=torch.int32, device=dev)
         bins = torch.empty(F, R, device=dev, dtype=torch.uint8)
         if Fn:
             ops.gbdt_bin(num, self.borders_, self.n_borders_, out=bins)
-        if Fc:
+        if Fc and not Fts:
             bins[Fn:] = self._codes(cat, R)
+        elif Fc:
+            codes = self._wide_codes(cat, R)
+            self._fit_ts(codes, y, [known[k] for k in self.ts_cols_], bins[Fn:])
+            if one_hot:
+                bins[Fn + Fts:] = codes[one_hot].to(torch.uint8)      # in [0, one_hot_max_size]: checked above
         return bins, y, is_cat, n_pos
+
+    def _fit_ts(self, codes, y, V, out):
+        """The TS columns of a fit: codes int64 [Fc, R] -> the ordered training values (ops.gbdt_ts_plan,
+        ops.gbdt_ordered_ts), their borders and bins (rows 0..Fts-1 of out), and per column the table, the
+        totals and the byte table the served rows gather. V: the columns' known values. No host read."""
+        ts_codes = codes[self.ts_cols_].to(torch.int32).contiguous()
+        order = ops.gbdt_ts_plan(ts_codes, self.ts_seed)
+        ts, totals, table = ops.gbdt_ordered_ts(ts_codes, order, y, V, self.ts_prior)
+        self.ts_borders_, self.ts_n_borders_ = build_borders(ts, self.border_count)
+        ops.gbdt_bin(ts, self.ts_borders_, self.ts_n_borders_, out=out)
+        table_bins = ops.gbdt_bin(table, self.ts_borders_, self.ts_n_borders_)
+        self.ts_table_ = [table[j, :v + 1].clone() for j, v in enumerate(V)]
+        self.ts_totals_ = [totals[j, :v + 1].clone() for j, v in enumerate(V)]
+        self.ts_bins_ = [table_bins[j, :v + 1].clone() for j, v in enumerate(V)]
 
     def _new_model(self, is_cat, f0):
         """The empty GBDTModel of `iterations` trees a fit fills (model_)."""
@@ -224,7 +311,9 @@ class _ObliviousBoosting:
     @torch.no_grad()
     def predict_logits(self, X, ntree_end=None):
         """The raw scores [R] (fp32 device tensor) of X after the first ntree_end trees (default: tree_count_):
-        bit-identical to the training approximant after as many trees."""
+        bit-identical to the training approximant after as many trees for a model without TS columns. With TS
+        columns the training rows saw their ordered values and the rows given here read the table's, so on the
+        training rows the two differ."""
         model = self._fitted()
         if ntree_end is not None and not 0 <= ntree_end <= model.splits.shape[0]:
             raise ValueError(f"ntree_end must be in [0, {model.splits.shape[0]}] (got {ntree_end})")
@@ -232,23 +321,32 @@ class _ObliviousBoosting:
 
     # ---- persistence -----------------------------------------------------------------------------------
     def save_model(self, path):
-        """torch.save of the trees in use, the borders and the vocabularies, under the class's loss_function."""
+        """torch.save of the trees in use, the borders and the vocabularies, under the class's loss_function:
+        format "oblivious_gbdt/1", or with TS columns "oblivious_gbdt/2", which adds their positions, tables,
+        totals, borders and byte tables and the three TS parameters."""
         m = self._fitted()
         n = m.n_trees
         cpu = lambda t: None if t is None else t.detach().cpu()   # noqa: E731
-        torch.save({"format": "oblivious_gbdt/1", "loss_function": self.loss_function, "splits": cpu(m.splits[:n]), "leaf_values": cpu(m.leaf_values[:n]),
-                    "is_cat": cpu(m.is_cat), "depth": m.depth, "f0": m.f0, "borders": cpu(self.borders_),
-                    "n_borders": cpu(self.n_borders_), "n_bins": cpu(self.n_bins_), "vocab": self.vocab_,
-                    "names": self._fitted_names,
-                    "params": {"iterations": self.iterations, "learning_rate": self.learning_rate, "depth": self.depth,
-                               "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
-                               "cat_features": self.cat_features},
-                    "best_iteration": self.best_iteration_, "best_score": self.best_score_,
-                    "evals_result": self.evals_result_}, path)
+        sd = {"format": "oblivious_gbdt/1", "loss_function": self.loss_function, "splits": cpu(m.splits[:n]), "leaf_values": cpu(m.leaf_values[:n]),
+              "is_cat": cpu(m.is_cat), "depth": m.depth, "f0": m.f0, "borders": cpu(self.borders_),
+              "n_borders": cpu(self.n_borders_), "n_bins": cpu(self.n_bins_), "vocab": self.vocab_,
+              "names": self._fitted_names,
+              "params": {"iterations": self.iterations, "learning_rate": self.learning_rate, "depth": self.depth,
+                         "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
+                         "cat_features": self.cat_features},
+              "best_iteration": self.best_iteration_, "best_score": self.best_score_,
+              "evals_result": self.evals_result_}
+        if self.ts_cols_:
+            sd["format"] = "oblivious_gbdt/2"
+            sd["params"].update(one_hot_max_size=self.one_hot_max_size, ts_prior=self.ts_prior, ts_seed=self.ts_seed)
+            sd["ts"] = {"cols": list(self.ts_cols_), "table": [cpu(t) for t in self.ts_table_],
+                        "totals": [cpu(t) for t in self.ts_totals_], "bins": [cpu(t) for t in self.ts_bins_],
+                        "borders": cpu(self.ts_borders_), "n_borders": cpu(self.ts_n_borders_)}
+        torch.save(sd, path)
 
     def load_model(self, path):
         sd = torch.load(path, map_location="cpu", weights_only=False)
-        if sd.get("format") != "oblivious_gbdt/1":
+        if sd.get("format") not in ("oblivious_gbdt/1", "oblivious_gbdt/2"):
             raise ValueError(f"{path} is not an ObliviousBoostingClassifier model")
         loss = sd.get("loss_function", "Logloss")      # files written before the ranker existed carry no key
         if loss != self.loss_function:
@@ -261,6 +359,12 @@ class _ObliviousBoosting:
                                     sd["splits"].shape[0])
         self.borders_, self.n_borders_, self.n_bins_ = to(sd["borders"]), to(sd["n_borders"]), to(sd["n_bins"])
         self.vocab_, self._fitted_names = sd["vocab"], tuple(sd["names"])
+        self._no_ts()
+        if sd["format"] == "oblivious_gbdt/2":
+            ts = sd["ts"]
+            self.ts_cols_ = list(ts["cols"])
+            self.ts_table_, self.ts_totals_, self.ts_bins_ = ([to(t) for t in ts[k]] for k in ("table", "totals", "bins"))
+            self.ts_borders_, self.ts_n_borders_ = to(ts["borders"]), to(ts["n_borders"])
         self.feature_names_ = list(self._fitted_names[0]) + list(self._fitted_names[1])
         self.best_iteration_, self.best_score_, self.evals_result_ = sd["best_iteration"], sd["best_score"], sd["evals_result"]
         self.tree_count_ = self.model_.n_trees
@@ -276,6 +380,16 @@ class ObliviousBoostingClassifier(_ObliviousBoosting):
     or arrays, either may be None; there the categorical values are codes already, in [0, 255] (a value
     outside it predicts as 0). Internally the numeric columns come first, then the categorical ones: that
     is the order in which ties between equally good splits are broken.
+
+    one_hot_max_size=n in [1, 255] (default None: every categorical column one-hot, as above) makes a
+    categorical column with more than n known values (the vocabulary's size, or the largest code of a tensor
+    column) a target-statistic column of up to ops.GBDT_TS_MAX_CODES known values: its training rows carry the
+    ordered statistic (s_i + a p) / (n_i + a) over the rows of the same code that precede them in the order
+    hash_u32(ts_seed + TS column index, row), ts_prior = (p, a); validation and served rows read the table of
+    the totals, through a byte table per column (ts_bins_), and a code outside [0, V] reads entry 0. Such a
+    column is numeric from there on (borders of the ordered values, is_cat 0). The internal order is then
+    numeric, TS, one-hot columns, each kind in the caller's order: the tie-break order. predict_logits on the
+    training rows no longer equals the training approximant of such a model.
 
     After fit: tree_count_, feature_names_, and with an eval_set evals_result_, best_iteration_ (the
     0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
@@ -393,7 +507,9 @@ class ObliviousBoostingRanker(_ObliviousBoosting):
     group with a positive weighs the same. X as ObliviousBoostingClassifier's; the base score is 0. The
     trees, the histograms and the prediction are the classifier's: only the gradient stage differs
     (ops.gbdt_tree(groups=...)). Every sum is an integer sum and every group reduction is order-free: two
-    fits give the same model bit for bit, and so does a fit on the same rows in another order."""
+    fits give the same model bit for bit, and so does a fit on the same rows in another order. With TS columns
+    (one_hot_max_size) the statistics are computed on the caller's row order, before the permutation into
+    group order, and depend on it: the second property then holds only for a model without TS columns."""
 
     loss_function = "QuerySoftMax"
 

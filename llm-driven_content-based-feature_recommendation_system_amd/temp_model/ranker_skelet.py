@@ -496,9 +496,13 @@ class RecommendationRanker:
     the class worked before, else native. loss_function "QuerySoftMax" (backend "native" only; the default
     stays "Logloss") builds the listwise ObliviousBoostingRanker instead: its rows carry the reference's
     per-customer group id (utils/monitor/log_importer.py) as "group_id", it validates on NDCG@10, and
-    its scores are raw scores that order the candidates of a query, not probabilities."""
+    its scores are raw scores that order the candidates of a query, not probabilities. one_hot_max_size
+    (default None: every categorical column one-hot, at most 255 values each) goes to the native model: a
+    categorical column with more known values is encoded by ordered target statistics
+    (oblivious_gbdt.py); backend "catboost" ignores it (CatBoost has its own)."""
 
-    def __init__(self, model_path: str = None, backend: str = "auto", loss_function: str = "Logloss"):
+    def __init__(self, model_path: str = None, backend: str = "auto", loss_function: str = "Logloss",
+                 one_hot_max_size: int = None):
         if backend not in ("auto", "catboost", "native"):
             raise ValueError(f'backend must be "auto", "catboost" or "native" (got {backend!r})')
         if loss_function not in ("Logloss", "QuerySoftMax"):
@@ -521,12 +525,14 @@ class RecommendationRanker:
         elif loss_function == "QuerySoftMax":
             from .oblivious_gbdt import ObliviousBoostingRanker
             self.model = ObliviousBoostingRanker(iterations=1000, learning_rate=0.05, depth=6, early_stopping_rounds=50,
-                                                 cat_features=self.engineer.cat_features)
+                                                 cat_features=self.engineer.cat_features,
+                                                 one_hot_max_size=one_hot_max_size)
         else:
             from .oblivious_gbdt import ObliviousBoostingClassifier
             self.model = ObliviousBoostingClassifier(iterations=1000, learning_rate=0.05, depth=6,
                                                      early_stopping_rounds=50,
-                                                     cat_features=self.engineer.cat_features)
+                                                     cat_features=self.engineer.cat_features,
+                                                     one_hot_max_size=one_hot_max_size)
         self.is_fitted = False
         if model_path:
             self.load_model(model_path)
@@ -574,7 +580,9 @@ class RecommendationRanker:
         and the C users. The model is fitted through fit((numeric, codes), y[, group_id]) and then carries the
         FeatureEngineer column names and these vocabularies, so ReRankingSystem.rerank_batch /
         recommend_batch serve it and save_model / load_model round-trip it. With val_rows the model validates
-        as train does (AUC, or NDCG@10 for QuerySoftMax), stops early and keeps its best iteration."""
+        as train does (AUC, or NDCG@10 for QuerySoftMax), stops early and keeps its best iteration. A column
+        with more than 255 values raises ValueError unless the ranker was built with one_hot_max_size: then the
+        columns with more values than that are target-statistic columns of the fit."""
         if self.backend != "native":
             raise TypeError(f'train_rows needs backend="native" (this ranker\'s is {self.backend!r})')
         dev = rows.row_user.device
@@ -590,7 +598,7 @@ class RecommendationRanker:
             vocab = {}
             codes = np.fromiter((vocab.setdefault(m.get(key, "unknown"), len(vocab) + 1) for m in metas[side]), np.int64,
                                 len(metas[side]))
-            if len(vocab) > 255:
+            if len(vocab) > 255 and self.model.one_hot_max_size is None:      # else fit decides: a TS column
                 raise ValueError(f"categorical column {name!r} has {len(vocab)} distinct values: at most 255 are supported")
             vocabs.append(vocab)
             tables.append((side, torch.from_numpy(codes).to(dev)))
@@ -713,7 +721,8 @@ class ReRankingSystem:
         [Q, d] and user_meta (a list of Q dicts as recommend's user_meta_raw; default {}) ->
         ops.rerank_tabular (the numeric FeatureEngineer columns of every candidate from the item
         vectors and the per-item / per-user price tensors) -> ops.gbdt_bin with the model's borders,
-        the categorical codes gathered from per-item code tables built once from item_db_metadata ->
+        the categorical codes gathered from per-item code tables built once from item_db_metadata (a
+        target-statistic column of the model: the bins of its table, an unseen value as code 0) ->
         ops.gbdt_predict -> torch.topk. user_buckets and features are not used. A QuerySoftMax ranker orders by
         its raw score and returns it as the final score (no sigmoid)."""
         if _is_native_ranker(self.ranker):
@@ -784,7 +793,8 @@ class ReRankingSystem:
     def _tabular_tables(self, clf):
         """Per-item tensors of the native rerank path, built once per fitted model from item_db_metadata
         (item i = row i of the item vectors): price fp32 [N] and, per categorical item column of the model,
-        its codes uint8 [N] under the model's vocabulary."""
+        its codes uint8 [N] under the model's vocabulary; for a target-statistic column the item's bin, its code
+        looked up in the model's byte table (ts_bins_), so serving either kind is one one-byte gather."""
         cached = self.__dict__.get("_tabular")
         if cached is not None and cached["model"] is clf.model_:
             return cached
@@ -795,9 +805,12 @@ class ReRankingSystem:
         if unknown or not clf.vocab_ and cats:
             raise ValueError(f"the native ranker was not fitted on FeatureEngineer rows (columns {unknown or cats})")
         codes = {}
-        for name, vocab in zip(cats, clf.vocab_):
+        for k, (name, vocab) in enumerate(zip(cats, clf.vocab_)):
             side, key = self._TABULAR_CATS.get(name, (None, None))
-            if side == "item":
+            if side == "item" and k in clf.ts_cols_:       # a TS column: the item's bin, through the model's byte table
+                host = np.fromiter((vocab.get(m.get(key, "unknown"), 0) for m in metas), np.int64, n)
+                codes[name] = clf._ts_bins_of(k, torch.from_numpy(host).to(self.device))
+            elif side == "item":
                 host = np.fromiter((vocab.get(m.get(key, "unknown"), 0) for m in metas), np.uint8, n)
                 codes[name] = torch.from_numpy(host).to(self.device)
         price = torch.tensor([float(m.get("price", 0)) for m in metas], dtype=torch.float32, device=self.device)
@@ -826,11 +839,16 @@ class ReRankingSystem:
         if nums:
             x = feats if tab["rows"] is None else feats.index_select(0, tab["rows"])
             ops.gbdt_bin(x, clf.borders_, clf.n_borders_, out=bins)
+        rows = clf._cat_rows(len(nums), len(cats))      # numeric, then TS, then one-hot columns
         for k, (name, vocab) in enumerate(zip(cats, clf.vocab_)):
             side, key = self._TABULAR_CATS.get(name, (None, None))
-            row = bins[len(nums) + k]
+            row = bins[rows[k]]
             if side == "item":
                 row.copy_(tab["codes"][name].index_select(0, ids))
+            elif side == "user" and k in clf.ts_cols_:
+                per_user = torch.tensor([vocab.get(m.get(key, "unknown"), 0) for m in user_meta], dtype=torch.int64,
+                                        device=self.device)
+                row.copy_(clf._ts_bins_of(k, per_user).repeat_interleave(K))
             elif side == "user":
                 per_user = torch.tensor([vocab.get(m.get(key, "unknown"), 0) for m in user_meta], dtype=torch.uint8,
                                         device=self.device)
