@@ -259,6 +259,15 @@ int rsx_nce_grouped_fwd_grad(const float* A, const float* B, const float* bias, 
                              const int* row_col, const int* row_beg, const int* row_end, const int* exc_cols,
                              int64_t N, int64_t D, int64_t lda, int64_t ldb, float tau, int precision, int nsplit,
                              float* ws, float* out2, float* ga, void* stream);
+/* The fused forward's grid for (N, D, nsplit) on a device of cus compute units (cus <= 0: the current
+ * device's), computed on the host without a launch (no reference counterpart: tests and tools read it).
+ * With nsplit 1 or 2 the library lays the grid out in whole rounds of 2 x cus co-resident workgroups:
+ * the leading rb1 row blocks (128 rows each) run ns1 column splits, the rest ns2, nslots partial slots
+ * per row. sched[7] = {rb1, ns1, span1, ns2, span2, nslots, blocks} (span: columns per split);
+ * block_map (nullable) receives {row block, split, first column, end column} of blocks
+ * 0 .. min(blocks, max_blocks) - 1, exactly as the kernels derive them from their block index. */
+int rsx_nce_fwdg_schedule(int64_t N, int64_t D, int nsplit, int cus, int64_t* sched, int64_t* block_map,
+                          int64_t max_blocks);
 /* Measurement hooks (no reference counterpart; bench.py's roofline): while enabled,
  * rsx_nce_grouped_fwd_grad brackets the fused forward kernel's own launch (not the B split or the
  * merge) with two HIP events on its stream; rsx_kernel_events_read waits for them and writes up to

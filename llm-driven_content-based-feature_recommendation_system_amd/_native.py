@@ -70,6 +70,7 @@ _SIGS = {
     "rsx_nce_grouped_workspace_floats": (c_i64, [c_i64, c_i64, c_i, c_i, c_i]),
     "rsx_nce_grouped_fwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_f, c_i, c_i,
                                   c_p, c_p, c_p]),
+    "rsx_nce_fwdg_schedule": (c_i, [c_i64, c_i64, c_i, c_i, c_p, c_p, c_i64]),
     "rsx_kernel_events": (c_i, [c_i]),
     "rsx_kernel_events_read": (c_i, [c_p, c_i]),
     "rsx_gather_events": (c_i, [c_i]),

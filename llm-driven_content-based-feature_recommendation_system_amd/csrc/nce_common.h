@@ -48,7 +48,7 @@ struct FwdArgs {
 // split's streamed operand is re-read from that XCD's L2. Speed only, never correctness.
 // I: the block index type (int, or int64_t where the caller's row-block arithmetic is 64-bit).
 template <typename I>
-__device__ __forceinline__ void remap_block(I b, int nsplit, int& split, I& rb) {
+__host__ __device__ __forceinline__ void remap_block(I b, int nsplit, int& split, I& rb) {
   const int xcd = (int)(b & 7);
   const I q = b >> 3;
   if (nsplit >= 8) {  // multiple of 8: each split on one XCD group
@@ -212,8 +212,8 @@ struct GArgs {
   const __bf16* alo;
   const __bf16* bhi;
   const __bf16* blo;
-  // fused forward, tail-split geometry (fwdg_geometry): row blocks [0, rb1) run nsplit splits of
-  // span columns, the rest nsplit2 splits of span2; partial slots per row: nslots
+  // fused forward, two-region geometry (fwdg_schedule / fwdg_block): row blocks [0, rb1) run nsplit
+  // splits of span columns, the rest nsplit2 splits of span2; partial slots per row: nslots
   int64_t rb1, span2;
   int nsplit2, nslots;
   int split_major;       // grouped backward: split-major block order (nce_grouped_bwd_x3_k)
@@ -227,35 +227,86 @@ __device__ __forceinline__ int lower_bound_i(const int* a, int lo, int hi, int64
   return lo;
 }
 
-// Block geometry of the fused forward (nce_grouped_fwdg_x3p_k). Row blocks [0, rb1)
-// run a.nsplit column splits, the rest a.nsplit2 (finer: their workgroups are shorter and are
-// dispatched last, so the final round of the grid is filled by short workgroups instead of a
-// third of the chip running long ones). Each region keeps the XCD-aware remap of remap_block.
-__device__ __forceinline__ void fwdg_geometry(const GArgs& a, int& split, int64_t& rb, int64_t& j_begin,
-                                              int64_t& j_end) {
-  const int64_t b = blockIdx.x, n1 = a.rb1 * a.nsplit;
-  int64_t span;
+// Block geometry of the fused forwards (nce_grouped_fwdg_x3p_k, nce_grouped_fwdg_h_k): the one place
+// that turns a block index into (row block, split, column range). Row blocks [0, rb1) run nsplit
+// column splits of span columns, the rest nsplit2 splits of span2 (their workgroups are shorter
+// and are dispatched last, so the final round of the grid is filled by short workgroups instead of
+// part of the chip running long ones). Both counts are 1, 2, 4 or a multiple of 8, and each region
+// keeps the XCD-aware remap of remap_block: rb1 * nsplit is a multiple of 8 (fwdg_schedule), so in
+// the tail region b & 7 still names the XCD group.
+__host__ __device__ __forceinline__ void fwdg_block(int64_t b, int nsplit, int64_t span, int64_t rb1, int nsplit2,
+                                                    int64_t span2, int64_t M, int& split, int64_t& rb,
+                                                    int64_t& j_begin, int64_t& j_end) {
+  const int64_t n1 = rb1 * nsplit;
   if (b < n1) {
-    remap_block<int64_t>(b, a.nsplit, split, rb);
-    span = a.span;
-  } else {  // n1 is a multiple of 8 (host), so b & 7 still names the XCD group
-    const int64_t b2 = b - n1;
-    const int xcd = (int)(b2 & 7);
-    const int64_t q = b2 >> 3;
-    const int nsub = a.nsplit2 >> 3;  // nsplit2 in {8, 16, ...}
-    split = xcd + 8 * (int)(q % nsub);
-    rb = a.rb1 + q / nsub;
-    span = a.span2;
+    remap_block<int64_t>(b, nsplit, split, rb);
+  } else {
+    remap_block<int64_t>(b - n1, nsplit2, split, rb);
+    rb += rb1;
+    span = span2;
   }
   j_begin = (int64_t)split * span;
   j_end = j_begin + span;
-  if (j_end > a.M) j_end = a.M;
+  if (j_end > M) j_end = M;
+}
+__device__ __forceinline__ void fwdg_geometry(const GArgs& a, int& split, int64_t& rb, int64_t& j_begin,
+                                              int64_t& j_end) {
+  fwdg_block(blockIdx.x, a.nsplit, a.span, a.rb1, a.nsplit2, a.span2, a.M, split, rb, j_begin, j_end);
 }
 
 // streamed rows (or columns) per split: whole tiles, at least one
 inline int64_t split_span(int64_t n_str, int nsplit) {
   const int64_t s = round_up((n_str + nsplit - 1) / nsplit, kTile);
   return s < kTile ? kTile : s;
+}
+
+// Grid of the fused forward for the caller's slot count nsplit, over slots = 2 x CUs co-resident
+// workgroups (two 256-VGPR workgroups per CU). A pure function of (N, D, slots): no atomics, no
+// work claiming, so a step is bit-reproducible.
+//   nsplit 4: every row block runs 4 splits; nsplit 8: the leading row blocks, as many as fill
+//     whole rounds, run 4 splits and the rest 8 (the plain-family view's geometry).
+//   nsplit 1, 2 (rounds model; slots rounded down to whole XCD groups of 8): the first
+//     rb1 = floor(rbs / slots) * slots row blocks run as
+//     whole-row workgroups (one split over all D columns, one partial slot: whole rounds of equal
+//     workgroups have no tail), the remaining t < slots row blocks run ns2 splits, ns2 in
+//     {1, 2, 4, 8} minimising the tail's makespan ceil(t ns2 / slots) / ns2 row sweeps (ties: the
+//     smaller ns2, less partial traffic). With 2 splits everywhere the makespan was
+//     ceil(2 rbs / slots) / 2 sweeps; ns2 = 2 is a candidate, so the model never gets worse.
+//     Batch 8192 (rbs 1,197, slots 512): 1,024 whole-row blocks, then 173 x 8: 2 + 3/8 = 2.375
+//     sweeps against 2.5; batch 4096 (601): 512, then 89 x 4: 1.25 against 1.5.
+// nslots: partial slots per row (the stride of part and of the row-gradient partials).
+struct FwdgSchedule {
+  int64_t rb1;   // leading row blocks
+  int ns1, ns2;  // splits of the leading / tail row blocks
+  int nslots;
+  int64_t span1, span2, blocks;
+};
+inline FwdgSchedule fwdg_schedule(int64_t N, int64_t D, int nsplit, int64_t slots) {
+  const int64_t rbs = (N + kOwnRows - 1) / kOwnRows;
+  FwdgSchedule s;
+  if (slots < 8) slots = 8;
+  if (nsplit == 4) {
+    s.rb1 = rbs; s.ns1 = 4; s.ns2 = 8; s.nslots = 4;
+  } else if (nsplit == 8) {
+    s.ns1 = 4; s.ns2 = 8; s.nslots = 8;
+    s.rb1 = (4 * rbs / slots) * slots / 4;  // whole rounds of the 4-split blocks
+  } else {
+    s.ns1 = 1;
+    slots -= slots % 8;  // whole XCD groups: the tail region starts where b & 7 == 0
+    s.rb1 = rbs / slots * slots;
+    const int64_t t = rbs - s.rb1;
+    s.ns2 = 1;
+    int64_t best = (t + slots - 1) / slots;  // rounds / ns2, compared as fractions
+    for (int c = 2; c <= 8; c *= 2) {
+      const int64_t r = (t * c + slots - 1) / slots;
+      if (r * s.ns2 < best * c) { best = r; s.ns2 = c; }
+    }
+    s.nslots = t > 0 ? s.ns2 : 1;
+  }
+  s.span1 = split_span(D, s.ns1);
+  s.span2 = split_span(D, s.ns2);
+  s.blocks = s.rb1 * s.ns1 + (rbs - s.rb1) * s.ns2;
+  return s;
 }
 
 // split count of one pass of the plain bf16x3 kernels: the smallest power of two (<= 64) that gives
@@ -302,8 +353,15 @@ struct PlainX3Layout : StatsLayout {
 // grouped: the plain fp32 layout over (N, D), then (bf16x3, f16: 64-float aligned) img | 64. The
 // fused forward's per-slot row gradients (nslots x N x 128) and the column pass's up to 32 splits
 // also live in dpart: both are checked against dpart_cap where they are chosen.
+// The fused forward called with 1 or 2 slots gives its tail rows up to 8 (fwdg_schedule), more than
+// the stats region's part [4][nf][N] holds, and the totals are fixed (callers size their buffers
+// with them): its partial stats [4][nslots][N] (<= 32 N floats) go to the head of A's image region
+// (fwd_part = img, N x 128 floats), which is idle between the calls: the forward streams B's
+// images and reads A itself, and A's images are written by the backward's column pass, after the
+// merge has consumed the partials. lse / row_loss / row_valid stay where StatsLayout puts them.
 struct GroupedLayout : PlainLayout {
   int64_t img, total;
+  int64_t fwd_part(int nsplit_fwd) const { return nsplit_fwd <= 2 ? img : part; }
   GroupedLayout(int64_t N, int64_t D, int nsplit_fwd, int precision, int nsplit_bwd = kNsplitBwdGrouped)
       : PlainLayout(N, D, nsplit_fwd, nsplit_bwd), img(round_up(PlainLayout::total, 64)),
         total(img + (precision != RSX_NCE_FP32 ? (N + D) * kD + 64 : 0)) {}

@@ -1252,26 +1252,26 @@ int grouped_forward(const float* A, const float* B, const float* bias, const flo
     hipLaunchKernelGGL(nce_grouped_merge_k, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, A, B, bias, row_col, N,
                        lda, ldb, g.inv_tau, nsplit, g.part, ws + L.lse, ws + L.row_loss, ws + L.row_valid);
   } else {
+    // the grid (fwdg_schedule): whole rounds of equal workgroups on the leading row blocks, the
+    // remaining row blocks on more, shorter splits dispatched last, so the grid's final round is
+    // short and full. nsplit 1 and 2 (the grouped loss): whole-row workgroups, then up to 8 splits
+    // (batch 8192: 1,024 row blocks x 1 = 2 rounds of 512, then 173 x 8 eighth-length workgroups);
+    // 8 (the plain view): 4 splits, then 8. The rows' partial slots follow their region's count.
+    const FwdgSchedule sc = fwdg_schedule(N, D, nsplit, 2 * (int64_t)rsx::cu_count());
+    const int ns1 = sc.ns1;
+    const int64_t rb1 = sc.rb1;
     // the per-slot row gradients [nslots][N][128] go into the backward's split-partial region
-    RSX_ARG((int64_t)nsplit * N * kD <= L.dpart_cap, "fused forward partials exceed the split-partial region");
-    // nsplit = 8 (the partial slots per row): the leading row blocks run 4 column splits, as many
-    // as fill whole rounds of the grid at two workgroups per CU; the remaining row blocks run 8
-    // half-length splits, dispatched last, so the grid's final round is short and full
-    // (batch 8192: 1,152 row blocks x 4 = 9 rounds of 512, then 45 x 8 half-length workgroups)
-    const int ns1 = nsplit == 8 ? 4 : nsplit;
-    int64_t rb1 = rbs;
-    if (nsplit == 8) {
-      const int64_t slots = 2 * (int64_t)rsx::cu_count();
-      rb1 = (ns1 * rbs / slots) * slots / ns1;  // whole rounds of the 4-split blocks
-    }
+    RSX_ARG((int64_t)sc.nslots * N * kD <= L.dpart_cap, "fused forward partials exceed the split-partial region");
+    RSX_ARG(sc.blocks < (1ll << 31), "too many workgroups");
     g.nsplit = ns1;
-    g.span = split_span(D, ns1);
+    g.span = sc.span1;
     g.rb1 = rb1;
-    g.nsplit2 = 8;
-    g.span2 = split_span(D, 8);
-    g.nslots = nsplit;
+    g.nsplit2 = sc.ns2;
+    g.span2 = sc.span2;
+    g.nslots = sc.nslots;
+    g.part = ws + L.fwd_part(nsplit);
     g.dout = ws + L.dpart;
-    const int blocks = (int)(rb1 * ns1 + (rbs - rb1) * (nsplit == 8 ? 8 : 0));
+    const int blocks = (int)sc.blocks;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     if (events) {
       KernelEvents& k = kernel_events();
@@ -1292,11 +1292,11 @@ int grouped_forward(const float* A, const float* B, const float* bias, const flo
       RSX_LAUNCHED();
       hipLaunchKernelGGL(nce_grouped_merge_g_k<true>, mgrid, dim3(256), 0, st, A, B, bias, row_col, N, lda, ldb,
                          g.inv_tau, ns1, g.part, g.dout, ws + L.lse, ws + L.row_loss, ws + L.row_valid, ga,
-                         rb1 * kOwnRows, 8, nsplit, 0, pos->cnt, pos->ps, pos->P);
+                         rb1 * kOwnRows, sc.ns2, sc.nslots, 0, pos->cnt, pos->ps, pos->P);
     } else {
       hipLaunchKernelGGL(nce_grouped_merge_g_k<false>, mgrid, dim3(256), 0, st, A, B, bias, row_col, N, lda, ldb,
                          g.inv_tau, ns1, g.part, g.dout, ws + L.lse, ws + L.row_loss, ws + L.row_valid, ga,
-                         rb1 * kOwnRows, 8, nsplit, h16 ? 1 : 0, nullptr, nullptr, nullptr);
+                         rb1 * kOwnRows, sc.ns2, sc.nslots, h16 ? 1 : 0, nullptr, nullptr, nullptr);
     }
   }
   RSX_LAUNCHED();
@@ -1330,6 +1330,25 @@ RSX_API int rsx_nce_grouped_fwd(const float* A, const float* B, const float* bia
   NCE_REQUIRE(operand_error(A, B, lda, ldb));
   return grouped_forward(A, B, bias, colcnt, row_col, row_beg, row_end, exc_cols, N, D, lda, ldb, tau, precision,
                          nsplit, ws, out2, nullptr, (hipStream_t)stream);
+}
+
+RSX_API int rsx_nce_fwdg_schedule(int64_t N, int64_t D, int nsplit, int cus, int64_t* sched, int64_t* block_map,
+                                  int64_t max_blocks) {
+  RSX_ARG(sched != nullptr, "null sched");
+  RSX_ARG(N >= 0 && D >= 0, "N and D must be >= 0");
+  RSX_ARG(nsplit == 1 || nsplit == 2 || nsplit == 4 || nsplit == 8, "nsplit must be 1, 2, 4 or 8");
+  const FwdgSchedule sc = fwdg_schedule(N, D, nsplit, 2 * (int64_t)(cus > 0 ? cus : rsx::cu_count()));
+  const int64_t v[7] = {sc.rb1, sc.ns1, sc.span1, sc.ns2, sc.span2, sc.nslots, sc.blocks};
+  for (int k = 0; k < 7; ++k) sched[k] = v[k];
+  if (block_map) {
+    for (int64_t b = 0; b < sc.blocks && b < max_blocks; ++b) {
+      int split;
+      int64_t rb, j0, j1;
+      fwdg_block(b, sc.ns1, sc.span1, sc.rb1, sc.ns2, sc.span2, D, split, rb, j0, j1);
+      block_map[4 * b] = rb; block_map[4 * b + 1] = split; block_map[4 * b + 2] = j0; block_map[4 * b + 3] = j1;
+    }
+  }
+  return 0;
 }
 
 RSX_API int rsx_kernel_events(int on) {

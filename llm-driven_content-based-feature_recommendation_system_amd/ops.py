@@ -21,8 +21,10 @@ NCE_SUPCON = 9
 NCE_MASK_ITEM_POS = 18  # NCE_MASK_ITEM with the label logit left without its bias (plain kernels only)
 
 _NSPLIT_FWD = 8
-# partial slots of the grouped forward; the fused forward (rsx_nce_grouped_fwd_grad) accepts 1/2/4/8 and
-# runs 4 splits on the leading row blocks, 8 on the tail
+# partial slots of the grouped forward; the fused forward (rsx_nce_grouped_fwd_grad) accepts 1/2/4/8. With 1 or
+# 2 the library lays its grid out itself from the row count and the device's CU count: whole-row workgroups
+# on the row blocks that fill whole rounds of the chip, up to 8 splits on the rest (csrc/nce_common.h,
+# fwdg_schedule); 4 runs 4 splits everywhere, 8 runs 4 on the leading row blocks and 8 on the tail
 _NSPLIT_FWD_GROUPED = int(os.environ.get("RSX_NCE_NSPLIT_FWD", "2"))
 if _NSPLIT_FWD_GROUPED not in (1, 2, 4, 8):
     raise ValueError("RSX_NCE_NSPLIT_FWD must be 1, 2, 4 or 8 (the fused forward's supported partial-slot counts)")

@@ -6,6 +6,10 @@ the grouped fwd + both backward passes. Prints per-kernel average ms. Meant to b
 rocprofv3 (kernel trace / PMC passes) so a profile isolates these kernels.
 
   python tools/nce_micro.py --iters 20 --precision bf16x3
+
+--row-blocks K keeps the first K x 128 rows of the batch and all of its columns (the distinct targets
+of the whole batch): the fused forward's grid at a chosen number of row blocks, e.g. exact rounds of
+the chip's co-resident workgroups (the rounds model).
 """
 from __future__ import annotations
 
@@ -33,6 +37,8 @@ def main():
     ap.add_argument("--global-batch", type=int, default=0,
                     help="emulate one rank of a DP run: rows of the first --batch users, columns = the "
                          "distinct targets of a global batch of this many users")
+    ap.add_argument("--row-blocks", type=int, default=0,
+                    help="keep the first K x 128 rows only; the columns stay those of the whole batch")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     items = synth.make_items(seed=args.seed)
@@ -43,11 +49,16 @@ def main():
     valid = valid[:args.batch]
     t = b["target_ids"][:args.batch][valid].to(dev)
     users = torch.arange(args.batch).unsqueeze(1).expand_as(valid)[valid].to(dev)
+    cut = args.row_blocks > 0
+    if cut:
+        if args.row_blocks * 128 > t.numel():
+            raise SystemExit(f"--row-blocks {args.row_blocks}: the batch has only {t.numel()} rows")
+        t, users = t[:args.row_blocks * 128], users[:args.row_blocks * 128]
     n = t.numel()
     g = torch.Generator(device="cpu").manual_seed(args.seed)
     U = F.normalize(torch.randn(n, 128, generator=g), dim=1).to(dev).requires_grad_()
     W = items.pretrained.to(dev)
-    grp = ops.TargetGroups(t, users, t_cols=t_all) if gb > args.batch else ops.TargetGroups(t, users)
+    grp = ops.TargetGroups(t, users, t_cols=t_all) if gb > args.batch or cut else ops.TargetGroups(t, users)
     B = W[grp.uniq].contiguous().requires_grad_()
     bias = items.log_q.to(dev)[grp.uniq].contiguous()
     for i in range(3):
@@ -70,7 +81,8 @@ def main():
     N.lib().rsx_kernel_events(0)
     kms = [float(kev[i]) for i in range(max(nk, 0))]
     flops = 4.0 * n * int(grp.uniq.numel()) * 128
-    out = {"rows": n, "distinct_targets": int(grp.uniq.numel()), "precision": args.precision,
+    out = {"lib_hash": N.build_info()["lib_hash"], "rows": n, "distinct_targets": int(grp.uniq.numel()),
+           "precision": args.precision,
            "loss_sum": float(s.item()),
            "grad_u_abs_sum": float(U.grad.abs().sum().item()) / args.iters,
            "grad_b_abs_sum": float(B.grad.abs().sum().item()) / args.iters,
