@@ -364,6 +364,13 @@ int64_t rsx_gemm_x3_split_floats(int64_t M, int N, int K);
 int rsx_gemm_x3_ws(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M, int N,
                    int K, int epi, float* aux, int64_t ldaux, float p_drop, uint64_t seed, float* C, int64_t ldc,
                    float* ws, int64_t ws_floats, void* stream);
+/* The kernel form rsx_gemm_x3_ws takes for a shape with ws_floats of workspace (0: rsx_gemm_x3, or a null ws):
+ * 0 weight-stationary (K 128 / 256 / 384; C, and aux when given, must then be 16-byte aligned with row strides
+ * that are multiples of 4), 1 LDS-staged two-stage stream, 2 four stages in flight at 32 of K per stage,
+ * 3 four stages at 16 of K per stage, 4 split-K (split count = rsx_gemm_x3_split_floats / (M * N));
+ * -1 for a shape the entry refuses. epi 0..3 as rsx_gemm_x3, 4 = rsx_gemm_x3_relu_train's epilogue. The
+ * dispatcher switches on this function; it launches nothing and needs no device (256 CUs are assumed then). */
+int rsx_gemm_x3_form(int64_t M, int N, int K, int epi, int64_t ws_floats);
 /* The ReLU feed-forward's first GEMM with gradients (nn.TransformerEncoderLayer's default activation:
  * dropout(relu(linear1(x))) of HybridUserTower's encoder, tower_code/mined_inference.py:635-638, in
  * training): z = A . B^T + bias, C = dropout_p(max(z, 0)) with keep-mask hash(seed, m*N + n) as epi 1,

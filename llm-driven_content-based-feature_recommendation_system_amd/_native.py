@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 17 # rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 18# rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -105,6 +105,7 @@ _SIGS = {
     "rsx_linear_wgrad_x3": (c_i, [c_p, c_i64, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_p, c_i, c_p, c_i64, c_p]),
     "rsx_gemm_x3": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64, c_p]),
     "rsx_gemm_x3_split_floats": (c_i64, [c_i64, c_i, c_i]),
+    "rsx_gemm_x3_form": (c_i, [c_i64, c_i, c_i, c_i, c_i64]),
     "rsx_gemm_x3_ws": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64, c_p,
                              c_i64, c_p]),
     "rsx_gemm_x3_relu_train": (c_i, [c_p, c_i64, c_p, c_i64, c_p, c_i64, c_i, c_i, c_p, c_i64, c_f, c_u64, c_p, c_i64,

@@ -692,12 +692,43 @@ int split_plan(int64_t M, int N, int K) {
     if (K % (S * 32) == 0 && K / S >= 256 && tiles * S <= 4LL * cus) return S;
   return 1;
 }
+
+// The kernel form gemm_x3_impl launches for (M, N, K, internal epi) with ws_floats of split-K workspace
+// (0 = none); -1 for a shape it refuses. rsx_gemm_x3_form publishes it.
+constexpr int kFormWs = 0, kFormTwoStage = 1, kFormFour32 = 2, kFormFour16 = 3, kFormSplitK = 4;
+int gemm_form(int64_t M, int N, int K, int epi, int64_t ws_floats) {
+  if (M < 0 || N <= 0 || K <= 0 || N % kBN || K % kBK) return -1;
+  if (M * (int64_t)N >= (1LL << 32)) return -1;
+  const int64_t tiles = ((M + kBM - 1) / kBM) * (N / kBN);
+  if (tiles >= (1LL << 30)) return -1;
+  if (ws_enabled() && (K == 128 || K == 256 || K == 384)) return kFormWs;
+  const int S = split_plan(M, N, K);
+  if (S > 1 && ws_floats >= (int64_t)S * M * N) return kFormSplitK;
+  // tiles per workgroup: enough workgroups for two per CU, each a continuous stage stream
+  const int per = (int)((tiles + RSX_GEMM_BLOCKS - 1) / RSX_GEMM_BLOCKS);
+  const int64_t blocks = per > 0 ? (tiles + per - 1) / per : 0;
+  // few tiles for the chip (one workgroup per CU at most) and a long K: four stages in flight per workgroup
+  // (EPI_DGELU_DROP keeps the two-stage kernel: Q = 4 spills there)
+  if (per == 1 && blocks <= num_cus() && a_nk_long(K) && epi != EPI_DGELU_DROP)
+    return few_bk(K) == 32 ? kFormFour32 : kFormFour16;
+  return kFormTwoStage;
+}
 }  // namespace
 
 RSX_API int64_t rsx_gemm_x3_split_floats(int64_t M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   const int S = split_plan(M, N, K);
   return S > 1 ? (int64_t)S * M * N : 0;
+}
+
+// Which kernel form rsx_gemm_x3_ws (ws_floats = 0: rsx_gemm_x3) takes for this shape: 0 weight-stationary,
+// 1 streamed two-stage, 2 four-stage BK 32, 3 four-stage BK 16, 4 split-K (split count =
+// rsx_gemm_x3_split_floats / (M * N)); -1 for a shape the entry refuses. epi 0..3 as rsx_gemm_x3, 4 = the
+// epilogue of rsx_gemm_x3_relu_train. Host only: launches nothing.
+RSX_API int rsx_gemm_x3_form(int64_t M, int N, int K, int epi, int64_t ws_floats) {
+  if (epi < 0 || epi > 4) return -1;
+  const int internal = epi == kPublicRelu ? EPI_RELU : epi == 4 ? EPI_RELU_DROP : epi;
+  return gemm_form(M, N, K, internal, ws_floats);
 }
 
 static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias, int64_t M,
@@ -723,68 +754,75 @@ static int gemm_x3_impl(const float* A, int64_t lda, const float* B, int64_t ldb
   }
   RSX_ARG(p_drop >= 0.0f && p_drop < 1.0f, "p_drop must be in [0, 1)");
   RSX_ARG(M * (int64_t)N < (1LL << 32), "M * N must be < 2^32 (dropout element index)");
+  const int64_t tiles = ((M + kBM - 1) / kBM) * (N / kBN);
+  RSX_ARG(tiles < (1LL << 30), "too many tiles");
+  const int form = gemm_form(M, N, K, epi, ws ? ws_floats : 0);
+  if (form == kFormWs) {  // the weight-stationary kernel stores (and reads aux as) float4s
+    RSX_ARG(ldc % 4 == 0 && ((uintptr_t)C % 16) == 0,
+            "C must be 16-byte aligned, row stride a multiple of 4 (K 128, 256 or 384)");
+    RSX_ARG(!aux || (ldaux % 4 == 0 && ((uintptr_t)aux % 16) == 0),
+            "aux must be 16-byte aligned, row stride a multiple of 4 (K 128, 256 or 384)");
+  }
   if (M == 0) return 0;
   GArgs g = {};
   g.A = A; g.B = B; g.bias = bias; g.C = C; g.aux = aux; g.ridx = nullptr;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldaux = ldaux; g.M = M;
   g.N = N; g.K = K; g.epi = epi;
   g.tiles_n = N / kBN;
-  const int64_t tiles = ((M + kBM - 1) / kBM) * g.tiles_n;
-  RSX_ARG(tiles < (1LL << 30), "too many tiles");
   g.tiles = (int)tiles;
   g.drop = rsx::make_dropout(epi == EPI_BIAS ? 0.0f : p_drop, seed);
   hipStream_t st = (hipStream_t)stream;
-  if (ws_enabled() && ldb % 4 == 0) {
-    if (K == 128) { launch_ws<1, 128>(g, st); RSX_LAUNCHED(); return 0; }
-    if (K == 256) { launch_ws<2, 128>(g, st); RSX_LAUNCHED(); return 0; }
-    if (K == 384) { launch_ws<3, 64>(g, st); RSX_LAUNCHED(); return 0; }
-  }
-  const int S = split_plan(M, N, K);
-  if (S > 1 && ws && ws_floats >= (int64_t)S * M * N && ldc >= N) {
-    // split-K: (split, tile) workgroups write raw partial sums, then one pass adds them in split order
-    // and applies the epilogue (the epilogue form is not instantiated in the partial kernel)
-    g.per = 1;
-    g.ksplit = S;
-    g.kspan = K / S;
-    g.part = ws;
-    const int64_t blocks = tiles * S;
-    const int grid = (int)((blocks + 7) / 8 * 8);
-    if (few_bk(g.kspan) == 32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4, 32>), dim3(grid), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4>), dim3(grid), dim3(256), 0, st, g);
-    RSX_LAUNCHED();
-    const unsigned rb = (unsigned)((M * (int64_t)N + 255) / 256);
-    if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_BIAS>, dim3(rb), dim3(256), 0, st, g);
-    else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_GELU_DROP>, dim3(rb), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU>, dim3(rb), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU_DROP)
-      hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU_DROP>, dim3(rb), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_DGELU_DROP>, dim3(rb), dim3(256), 0, st, g);
-    RSX_LAUNCHED();
-    return 0;
-  }
-  // tiles per workgroup: enough workgroups for two per CU, each a continuous stage stream
+  // tiles per workgroup of the streamed forms: each a continuous stage stream
   g.per = (int)((tiles + RSX_GEMM_BLOCKS - 1) / RSX_GEMM_BLOCKS);
-  const int64_t blocks = (tiles + g.per - 1) / g.per;
-  const int grid = (int)((blocks + 7) / 8 * 8);
-  // few tiles for the chip (one workgroup per CU at most) and a long K: four stages in flight per workgroup
-  if (g.per == 1 && blocks <= num_cus() && a_nk_long(K)) {
-    const bool b32 = few_bk(K) == 32;
-    if (epi == EPI_BIAS && b32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4, 32>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_BIAS) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_GELU_DROP && b32)
-      hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU && b32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4, 32>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU_DROP && b32)
-      hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
-    else if (epi == EPI_RELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);  // Q = 4 spills here
-  } else if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_BIAS>, dim3(grid), dim3(256), 0, st, g);
-  else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_GELU_DROP>, dim3(grid), dim3(256), 0, st, g);
-  else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU>, dim3(grid), dim3(256), 0, st, g);
-  else if (epi == EPI_RELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU_DROP>, dim3(grid), dim3(256), 0, st, g);
-  else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);
+  const int grid = (int)(((tiles + g.per - 1) / g.per + 7) / 8 * 8);
+  switch (form) {
+    case kFormWs:
+      if (K == 128) launch_ws<1, 128>(g, st);
+      else if (K == 256) launch_ws<2, 128>(g, st);
+      else launch_ws<3, 64>(g, st);
+      break;
+    case kFormSplitK: {
+      // split-K: (split, tile) workgroups write raw partial sums, then one pass adds them in split order
+      // and applies the epilogue (the epilogue form is not instantiated in the partial kernel)
+      const int S = split_plan(M, N, K);
+      g.per = 1;
+      g.ksplit = S;
+      g.kspan = K / S;
+      g.part = ws;
+      const int sgrid = (int)((tiles * S + 7) / 8 * 8);
+      if (few_bk(g.kspan) == 32) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4, 32>), dim3(sgrid), dim3(256), 0, st, g);
+      else hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4>), dim3(sgrid), dim3(256), 0, st, g);
+      RSX_LAUNCHED();
+      const unsigned rb = (unsigned)((M * (int64_t)N + 255) / 256);
+      if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_BIAS>, dim3(rb), dim3(256), 0, st, g);
+      else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_GELU_DROP>, dim3(rb), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU>, dim3(rb), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU_DROP)
+        hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_RELU_DROP>, dim3(rb), dim3(256), 0, st, g);
+      else hipLaunchKernelGGL(gemm_splitk_reduce_k<EPI_DGELU_DROP>, dim3(rb), dim3(256), 0, st, g);
+      break;
+    }
+    case kFormFour32:
+      if (epi == EPI_BIAS) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_GELU_DROP)
+        hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+      else hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4, 32>), dim3(grid), dim3(256), 0, st, g);
+      break;
+    case kFormFour16:
+      if (epi == EPI_BIAS) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_BIAS, 4>), dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_GELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU) hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU, 4>), dim3(grid), dim3(256), 0, st, g);
+      else hipLaunchKernelGGL((gemm_x3_nt_k<EPI_RELU_DROP, 4>), dim3(grid), dim3(256), 0, st, g);
+      break;
+    default:  // kFormTwoStage
+      if (epi == EPI_BIAS) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_BIAS>, dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_GELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_GELU_DROP>, dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU>, dim3(grid), dim3(256), 0, st, g);
+      else if (epi == EPI_RELU_DROP) hipLaunchKernelGGL(gemm_x3_nt_k<EPI_RELU_DROP>, dim3(grid), dim3(256), 0, st, g);
+      else hipLaunchKernelGGL(gemm_x3_nt_k<EPI_DGELU_DROP>, dim3(grid), dim3(256), 0, st, g);
+      break;
+  }
   RSX_LAUNCHED();
   return 0;
 }

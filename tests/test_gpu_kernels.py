@@ -620,9 +620,10 @@ def _absprod(a, b):
                                    (1000, 256, 1024), (130, 128, 2048), (3000, 768, 3072), (3000, 2304, 768)])
 def test_gemm_x3_against_float64(gpu, M, N, K):
     """rsx_gemm_x3 (bf16x3 products, fp32 accumulate) vs float64: |C - ref| <= 2e-5 * sum_k
-    |a_mk b_nk| + 1e-6 per element (each bf16x3 product is within 2^-17 of exact). The last four shapes
-    have fewer output tiles than CUs and a long K: split-K through ops.gemm_x3's workspace (S = 4, 8, 4)
-    and the four-stage prefetch (3000 x 2304)."""
+    |a_mk b_nk| + 1e-6 per element (each bf16x3 product is within 2^-17 of exact). (1000, 256, 1024),
+    (130, 128, 2048) and (3000, 768, 3072) have fewer output tiles than CUs and a long K: split-K through
+    ops.gemm_x3's workspace (S = 4, 8, 4). 3000 x 2304 x 768 has 432 tiles, more than the chip has CUs, and
+    takes the two-stage kernel; the four-stage forms are covered by tests/test_gpu_gemm_forms.py."""
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn(M, K, generator=g)
     b = torch.randn(N, K, generator=g)
