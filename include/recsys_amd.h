@@ -1260,6 +1260,105 @@ int rsx_gbdt_ordered_ts(const int* codes, const int64_t* order, const float* y, 
                         int64_t Vmax, double ap, double a, void* ws, int64_t ws_bytes, float* ts, int* totals,
                         float* table, int* flag, void* stream);
 
+/* ---- A20 transaction features: the towers' frames from the purchase log, csrc/tx_features.hip --------------
+ * The reference builds features_user_w_meta, features_item and features_sequence with pandas groupbys and a
+ * pandarallel apply per customer (staticstics/preprosess_agg_parallel.py). Here the log is a table sorted by
+ * (customer, day), same-day ties in file order (the reference's sort_values leaves them open; file order is this
+ * project's definition and decides last_price and the order of same-day sequence entries): item, day int32 [T],
+ * price fp32 [T], channel uint8 [T], T < 2^31 rows, and cust_off int64 [C + 1]. Every per-segment quantity is a
+ * segmented scan on fixed 256-row tiles: a tile pass, one scan over the tiles' aggregates, a second tile pass.
+ * No thread walks a segment, no workgroup waits on another, every slot has one writer and the order in which
+ * floating-point values combine is fixed: the same bits every run. Integer results are exact. ws is
+ * rsx_tx_workspace_bytes(T) bytes, 16-byte aligned; flag is int32, OR-ed, and no access leaves its array
+ * whatever the inputs hold.
+ *   calendar: day = days since 1970-01-01 in [0, 2^31): weekend = ((day + 3) mod 7 >= 5) (Monday = 0), month =
+ *          12 year + month - 1 by the civil-from-days integer algorithm, week = floor((day + 3) / 7) (weeks start
+ *          on Monday). A negative day is taken as 0 and sets flag bit 0.
+ *   segment rows: row_seg[t] = the s with seg_off[s] <= t < seg_off[s + 1], -1 for a row in no segment.
+ *          Offsets are clamped to [0, T]; an offset outside it, a decreasing pair, seg_off[0] != 0 or
+ *          seg_off[S] != T set flag bit 0. The entries below take row_seg: non-decreasing over the rows (this
+ *          entry's output, or a sorted column such as the item of a by-item order); a value outside [0, S) is a
+ *          row of no segment; a value >= S or a value below its predecessor's sets flag bit 0 (equal values
+ *          must be contiguous: each run would write the slot again).
+ *   segment stats: with perm NULL the rows are the table's, else sorted position t is table row perm[t] (an
+ *          entry outside [0, T) is skipped, flag bit 0). Per segment: count, sum = the fp64 sum of the fp32
+ *          prices, m2 = sum (price - mean)^2 in fp64 with mean = sum / count (a second pass), last = the last
+ *          row's price, dmin / dmax = the smallest / largest day, chan = the sum of channel, wkend = the
+ *          number of rows with weekend != 0. A segment without rows has zeros everywhere.
+ *   segment distinct: val int32 [T] non-decreasing inside every segment -> the number of distinct values per
+ *          segment (the rows whose value differs from their predecessor's, and the first). A decreasing pair
+ *          inside a segment sets flag bit 1.
+ *   weekly sales: weeks int32 [W] ascending and distinct, the weeks with at least one row -> weekly int32 [N, W],
+ *          weekly[i, j] = #{t : item[t] = i, week[t] = weeks[j]}: the reference's groupby([article_id,
+ *          week_start]).size().unstack(fill_value=0).sort_index(axis=1); a week nobody bought in has no column.
+ *          Integer atomics. An item outside [0, N) or a week not in weeks is skipped and sets flag bit 0.
+ *   item features (:171-237): out fp32 [8, N] = raw_probability = n / T; pop_1w_log = log1p(last column);
+ *          pop_1m_log = log1p(sum of the last four columns that exist); velocity_1w = clip((cur - prev) / (prev +
+ *          1), -1, 5) over the last two columns, velocity_1m the same over the last four and the columns [-8:-4]
+ *          that exist (prev = 0 where none does); steady_score_log = log1p(mean / (std + 1e-9)) over the last
+ *          min(12, W) columns, std with ddof = 1 from the two-pass sum of squares, 0 when W = 1 (the NaN the
+ *          frame's fillna(0) removes); avg_item_price_log = log1p(sum / n); days_since_release_log = log1p(max_day
+ *          - dmin). Then for an item with max_day - dmin < cold_days (14) rows 1..4 are replaced by the row's
+ *          mean over all items taken before any replacement: the fixed-order fp64 sum of the fp32 values, / N. The
+ *          sum has two levels: per chunk of 4096 values thread j of 256 adds the elements j, j + 256, ... in order
+ *          and the 256 partial sums meet in a fixed tree; the chunk sums are summed the same way. col_sum:
+ *          col_sum_doubles >= 4 + 4 ceil(N / 4096) doubles, the four sums first.
+ *          Every value is evaluated in fp64 and rounded once.
+ *   user features (:329-351, :549-570): from the per-customer stats, uniq (distinct items) and months (distinct
+ *          months): f64 double [3, C] = user_avg_price = sum / n, total_cnt, recency_days = max_day - dmax (what
+ *          the buckets are cut from); cols fp32 [11, C] = price_std = sqrt(m2 / (n - 1)) (0 for n = 1),
+ *          last_price_diff = last - mean, repurchase_ratio = 1 - uniq / n, weekend_ratio = wkend / n, then
+ *          their four standardised forms (x - mean) / (std + 1e-9), then the reranker frame's user_avg_price_log
+ *          = log1p(mean), total_cnt_log = log1p(n), recency_log = log1p(recency_days). x is the fp32 column as
+ *          stored for the first three and the fp64 ratio for weekend_ratio (the reference's dtypes); mean and std
+ *          (ddof = 1) come from the two-pass fixed-order fp64 sums above over all C customers; C = 1 gives 0.
+ *          channel int8 = 2 where chan / n > 1.5, else 1; active_months int16 = months. ws: (4 C + 8 + 4 ceil(C /
+ *          4096)) * 8 bytes.
+ *   quantile buckets: pd.qcut(x, q, labels=False, duplicates='drop') + 1 for x double [n] with its ascending
+ *          copy s. Edge k = 0..q interpolates s at h = (n - 1) k / q, formed in float64 in the steps pandas'
+ *          quantile takes (numpy.percentile of linspace(0, 1, q + 1), method 'linear'): p = k * (1 / q), 1 for k =
+ *          q; p = (p * 100) / 100; h = (n - 1) * p; lo = floor(h), t = h - lo; e_k = s[lo] + (s[lo + 1] - s[lo]) t,
+ *          or s[lo + 1] - (s[lo + 1] - s[lo]) (1 - t) where t >= 0.5 (numpy's _lerp; a product and a sum, not
+ *          contracted), s[n - 1] where lo >= n - 1. These are the bits pandas 2 / numpy 2 give: h is not the
+ *          exact fraction (at n = 701, q = 10, k = 7 it is 489.99999999999994 and the edge lies just below
+ *          s[490]). Equal edges are dropped: edges double [q + 1] holds the n_edges (int32) that remain. bucket
+ *          int8 = #{edges < x}, at least 1: the lowest edge is in bucket 1 and a constant column is 1 everywhere
+ *          (the reference raises there on its int8 cast of NaN). q <= 126.
+ *   sequences: valid uint8 [N] marks the items kept. rsx_tx_sequence_ranks: rank[t] = the number of valid rows
+ *          behind row t in its customer (a reversed segmented scan), -1 for a row whose item is not valid (an item
+ *          outside [0, N): flag bit 0); n_valid [C] = the customer's valid rows, last_day [C] = the day of the last
+ *          one. The caller forms seq_off int64 [C + 1] = the running sum of min(n_valid, max_len), n_out its last
+ *          entry. rsx_tx_sequences: a row with 0 <= rank < max_len goes to slot seq_off[c + 1] - 1 - rank:
+ *          seq_item = its item, seq_delta = last_day[c] - day. One writer per slot; a slot outside its
+ *          customer's range (offsets that are not those of n_valid) is skipped and sets flag bit 0. */
+int64_t rsx_tx_workspace_bytes(int64_t T);
+int rsx_tx_calendar(const int* day, int64_t T, uint8_t* weekend, int* month, int* week, int* flag, void* stream);
+int rsx_tx_segment_rows(const int64_t* seg_off, int64_t S, int64_t T, void* ws, int64_t ws_bytes, int* row_seg,
+                        int* flag, void* stream);
+int rsx_tx_segment_stats(const int* row_seg, int64_t S, int64_t T, const int64_t* perm, const float* price,
+                         const int* day, const uint8_t* channel, const uint8_t* weekend, void* ws, int64_t ws_bytes,
+                         int* count, double* sum, double* m2, float* last, int* dmin, int* dmax, int64_t* chan,
+                         int* wkend, int* flag, void* stream);
+int rsx_tx_segment_distinct(const int* row_seg, int64_t S, int64_t T, const int* val, void* ws, int64_t ws_bytes,
+                            int* distinct, int* flag, void* stream);
+int rsx_tx_weekly_sales(const int* item, const int* week, int64_t T, const int* weeks, int64_t W, int64_t N,
+                        int* weekly, int* flag, void* stream);
+int rsx_tx_item_features(const int* weekly, int64_t N, int64_t W, const int* count, const double* sum,
+                         const int* dmin, int64_t T, int max_day, int cold_days, double* col_sum, int64_t col_sum_doubles,
+                         float* out, void* stream);
+int rsx_tx_user_features(const int* count, const double* sum, const double* m2, const float* last, const int* dmax,
+                         const int64_t* chan, const int* wkend, const int* uniq, const int* months, int64_t C,
+                         int max_day, void* ws, int64_t ws_bytes, double* f64, float* cols, int8_t* channel,
+                         int16_t* active_months, void* stream);
+int rsx_quantile_bucket(const double* x, const double* sorted, int64_t n, int q, double* edges, int* n_edges,
+                        int8_t* bucket, void* stream);
+int rsx_tx_sequence_ranks(const int* row_seg, int64_t C, int64_t T, const int* item, const int* day,
+                          const uint8_t* valid, int64_t N, void* ws, int64_t ws_bytes, int* rank, int* n_valid,
+                          int* last_day, int* flag, void* stream);
+int rsx_tx_sequences(const int* row_seg, int64_t C, int64_t T, const int* item, const int* day, const int* rank,
+                     const int* last_day, const int64_t* seq_off, int max_len, int64_t n_out, int* seq_item,
+                     int* seq_delta, int* flag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

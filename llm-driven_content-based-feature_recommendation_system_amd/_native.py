@@ -25,7 +25,7 @@ c_f = ctypes.c_float
 c_d = ctypes.c_double
 c_u64 = ctypes.c_uint64
 
-ABI_VERSION = 18# rsx_abi_version() of the library these signatures describe
+ABI_VERSION = 19  # rsx_abi_version() of the library these signatures describe
 
 # name -> (restype, argtypes)
 _SIGS = {
@@ -235,6 +235,19 @@ _SIGS = {
                                c_p, c_p]),
     "rsx_gbdt_ts_keys": (c_i, [c_p, c_i64, c_i, c_u64, c_p, c_p]),
     "rsx_gbdt_ordered_ts": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i64, c_d, c_d, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_tx_workspace_bytes": (c_i64, [c_i64]),
+    "rsx_tx_calendar": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_tx_segment_rows": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_tx_segment_stats": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p,
+                                   c_p, c_p, c_p, c_p]),
+    "rsx_tx_segment_distinct": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "rsx_tx_weekly_sales": (c_i, [c_p, c_p, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    "rsx_tx_item_features": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_i, c_i, c_p, c_i64, c_p, c_p]),
+    "rsx_tx_user_features": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_i64, c_p, c_p, c_p,
+                                   c_p, c_p]),
+    "rsx_quantile_bucket": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p]),
+    "rsx_tx_sequence_ranks": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_tx_sequences": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -4602,6 +4602,279 @@ def pair_tabular(row_user, row_item, score, user_vectors, item_vectors, item_pri
 
 
 # ----------------------------------------------------------------------------------------
+# A20 the towers' feature frames from the transaction log (csrc/tx_features.hip; include/recsys_amd.h, "transaction
+# features"). The table is sorted by (customer, day): item, day int32 [T], price fp32 [T], channel uint8 [T].
+TX_ITEM_COLUMNS = ("raw_probability", "pop_1w_log", "pop_1m_log", "velocity_1w", "velocity_1m", "steady_score_log",
+                   "avg_item_price_log", "days_since_release_log")
+TX_USER_COLUMNS = ("price_std", "last_price_diff", "repurchase_ratio", "weekend_ratio", "price_std_scaled",
+                   "last_price_diff_scaled", "repurchase_ratio_scaled", "weekend_ratio_scaled", "user_avg_price_log",
+                   "total_cnt_log", "recency_log")
+TX_USER_F64 = ("user_avg_price", "total_cnt", "recency_days")
+TX_COLD_DAYS = 14
+TX_MAX_QUANTILES = 126
+_TX_CALENDAR_GUARD = IdRangeGuard("tx_calendar: a negative day")
+_TX_ROWS_GUARD = IdRangeGuard("tx_segment_rows: offsets that do not run from 0 to T without decreasing")
+_TX_STATS_GUARD = IdRangeGuard("tx_segment_stats: a row_seg that decreases or has an entry >= S, or a perm entry outside "
+                               "[0, T)")
+_TX_DISTINCT_GUARD = IdRangeGuard("tx_segment_distinct: a value column that decreases inside a segment, or a row_seg "
+                                  "that decreases or has an entry >= S")
+_TX_WEEKLY_GUARD = IdRangeGuard("tx_weekly_sales: an item outside [0, N) or a week that is not a column")
+_TX_SEQ_GUARD = IdRangeGuard("tx_sequences: an item outside [0, N), or a row_seg that decreases or has an entry >= C")
+
+
+def _tx_rows(fn, t, name="row_seg"):
+    """t is a contiguous int32 device vector of 1 <= T < 2^31 rows; returns T."""
+    N.ensure_device(t)
+    T = t.numel()
+    if not 1 <= T < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= T < 2^31 rows (got {T})")
+    _gbdt_rows(fn, name, t, torch.int32, T, t)
+    return T
+
+
+def _tx_count(fn, name, n):
+    n = int(n)
+    if not 1 <= n < 2 ** 31 - 1:
+        raise ValueError(f"{fn}: need 1 <= {name} < 2^31 - 1 (got {n})")
+    return n
+
+
+def _tx_ws(T, dev):
+    return torch.empty(N.lib().rsx_tx_workspace_bytes(T), device=dev, dtype=torch.uint8)
+
+
+def tx_calendar(day):
+    """day int32 [T], days since 1970-01-01 -> (weekend uint8, month int32 = 12 year + month - 1, week int32 =
+    floor((day + 3) / 7), Monday-start weeks). A negative day counts as 0 and raises IndexError at a later call
+    (_TX_CALENDAR_GUARD.check())."""
+    fn = "tx_calendar"
+    T = _tx_rows(fn, day, "day")
+    dev = day.device
+    weekend = torch.empty(T, device=dev, dtype=torch.uint8)
+    month = torch.empty(T, device=dev, dtype=torch.int32)
+    week = torch.empty(T, device=dev, dtype=torch.int32)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/calendar"):
+        N.check(N.lib().rsx_tx_calendar(N.ptr(day), T, N.ptr(weekend), N.ptr(month), N.ptr(week), N.ptr(flag),
+                                        N.stream()), fn)
+    _TX_CALENDAR_GUARD.watch(flag)
+    return weekend, month, week
+
+
+def tx_segment_rows(seg_off, T):
+    """seg_off int64 [S + 1] (device) over T rows -> row_seg int32 [T], the segment of every row (-1: none). Offsets
+    are clamped to [0, T]; malformed ones raise IndexError at a later call (_TX_ROWS_GUARD.check())."""
+    fn = "tx_segment_rows"
+    N.ensure_device(seg_off)
+    T = int(T)
+    if not 1 <= T < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= T < 2^31 rows (got {T})")
+    if seg_off.dim() != 1 or seg_off.numel() < 2:
+        raise ValueError(f"{fn}: seg_off must hold S + 1 >= 2 offsets, got shape {tuple(seg_off.shape)}")
+    S = _tx_count(fn, "S", seg_off.numel() - 1)
+    _gbdt_rows(fn, "seg_off", seg_off, torch.int64, S + 1, seg_off)
+    dev = seg_off.device
+    row_seg = torch.empty(T, device=dev, dtype=torch.int32)
+    ws = _tx_ws(T, dev)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/segment_rows"):
+        N.check(N.lib().rsx_tx_segment_rows(N.ptr(seg_off), S, T, N.ptr(ws), ws.numel(), N.ptr(row_seg), N.ptr(flag),
+                                            N.stream()), fn)
+    _TX_ROWS_GUARD.watch(flag)
+    return row_seg
+
+
+def tx_segment_stats(row_seg, S, price, day, channel, weekend, perm=None):
+    """Per segment of row_seg int32 [T] (tx_segment_rows, or a sorted column) over the table columns price fp32,
+    day int32, channel uint8, weekend uint8 [T] (read through perm int64 [T] when given: sorted position -> table
+    row): a dict of count int32, sum fp64, m2 fp64 = sum (price - sum / count)^2, last fp32, dmin, dmax int32, chan
+    int64, wkend int32, each [S]. Fixed combination order: the same bits every call."""
+    fn = "tx_segment_stats"
+    T = _tx_rows(fn, row_seg)
+    S = _tx_count(fn, "S", S)
+    _gbdt_rows(fn, "price", price, torch.float32, T, row_seg)
+    _gbdt_rows(fn, "day", day, torch.int32, T, row_seg)
+    _gbdt_rows(fn, "channel", channel, torch.uint8, T, row_seg)
+    _gbdt_rows(fn, "weekend", weekend, torch.uint8, T, row_seg)
+    if perm is not None:
+        _gbdt_rows(fn, "perm", perm, torch.int64, T, row_seg)
+    dev = row_seg.device
+    out = {"count": torch.empty(S, device=dev, dtype=torch.int32), "sum": torch.empty(S, device=dev, dtype=torch.float64),
+           "m2": torch.empty(S, device=dev, dtype=torch.float64), "last": torch.empty(S, device=dev, dtype=torch.float32),
+           "dmin": torch.empty(S, device=dev, dtype=torch.int32), "dmax": torch.empty(S, device=dev, dtype=torch.int32),
+           "chan": torch.empty(S, device=dev, dtype=torch.int64), "wkend": torch.empty(S, device=dev, dtype=torch.int32)}
+    ws = _tx_ws(T, dev)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/segment_stats"):
+        N.check(N.lib().rsx_tx_segment_stats(N.ptr(row_seg), S, T, N.ptr(perm), N.ptr(price), N.ptr(day), N.ptr(channel),
+                                             N.ptr(weekend), N.ptr(ws), ws.numel(), N.ptr(out["count"]), N.ptr(out["sum"]),
+                                             N.ptr(out["m2"]), N.ptr(out["last"]), N.ptr(out["dmin"]), N.ptr(out["dmax"]),
+                                             N.ptr(out["chan"]), N.ptr(out["wkend"]), N.ptr(flag), N.stream()), fn)
+    _TX_STATS_GUARD.watch(flag)
+    return out
+
+
+def tx_segment_distinct(row_seg, S, val):
+    """The number of distinct values of val int32 [T] per segment of row_seg, int32 [S]; val is non-decreasing
+    inside every segment (a decreasing pair raises IndexError at a later call, _TX_DISTINCT_GUARD.check())."""
+    fn = "tx_segment_distinct"
+    T = _tx_rows(fn, row_seg)
+    S = _tx_count(fn, "S", S)
+    _gbdt_rows(fn, "val", val, torch.int32, T, row_seg)
+    dev = row_seg.device
+    out = torch.empty(S, device=dev, dtype=torch.int32)
+    ws = _tx_ws(T, dev)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/segment_distinct"):
+        N.check(N.lib().rsx_tx_segment_distinct(N.ptr(row_seg), S, T, N.ptr(val), N.ptr(ws), ws.numel(), N.ptr(out),
+                                                N.ptr(flag), N.stream()), fn)
+    _TX_DISTINCT_GUARD.watch(flag)
+    return out
+
+
+def _tx_grid(fn, n_items, W):
+    n_items, W = int(n_items), int(W)
+    if not (1 <= W <= 65536 and n_items >= 1 and n_items * W < 2 ** 31):
+        raise ValueError(f"{fn}: need 1 <= W <= 65536 weeks, N >= 1 items and N W < 2^31 (got N {n_items}, W {W})")
+    return n_items, W
+
+
+def tx_weekly_sales(item, week, n_items, weeks=None):
+    """(weekly int32 [N, W], weeks int32 [W]): weekly[i, j] = the rows of item i in week weeks[j]; weeks = the
+    distinct values of week ascending (torch.unique: one host read for W) unless given. The reference's
+    groupby([article_id, week_start]).size().unstack(fill_value=0).sort_index(axis=1)."""
+    fn = "tx_weekly_sales"
+    T = _tx_rows(fn, item, "item")
+    _gbdt_rows(fn, "week", week, torch.int32, T, item)
+    if weeks is None:
+        weeks = torch.unique(week)
+    n_items, W = _tx_grid(fn, n_items, weeks.numel())
+    _gbdt_rows(fn, "weeks", weeks, torch.int32, W, item)
+    weekly = torch.empty(n_items, W, device=item.device, dtype=torch.int32)
+    flag = torch.zeros(1, device=item.device, dtype=torch.int32)
+    with timed("tx/weekly_sales"):
+        N.check(N.lib().rsx_tx_weekly_sales(N.ptr(item), N.ptr(week), T, N.ptr(weeks), W, n_items, N.ptr(weekly),
+                                            N.ptr(flag), N.stream()), fn)
+    _TX_WEEKLY_GUARD.watch(flag, n_items)
+    return weekly, weeks
+
+
+def tx_item_features(weekly, count, price_sum, dmin, n_rows, max_day, cold_days=TX_COLD_DAYS):
+    """The eight item columns TX_ITEM_COLUMNS, fp32 [8, N], from weekly int32 [N, W] and the per-item count int32,
+    price_sum fp64 and dmin int32 [N] (tx_segment_stats over a by-item order), the number of rows T and the
+    largest day; the cold-start imputation included. Evaluated in fp64, rounded once."""
+    fn = "tx_item_features"
+    N.ensure_device(weekly)
+    if weekly.dtype != torch.int32 or weekly.dim() != 2 or not weekly.is_contiguous():
+        raise ValueError(f"{fn}: weekly must be a contiguous int32 [N, W] matrix")
+    n_items, W = _tx_grid(fn, *weekly.shape)
+    _gbdt_rows(fn, "count", count, torch.int32, n_items, weekly)
+    _gbdt_rows(fn, "price_sum", price_sum, torch.float64, n_items, weekly)
+    _gbdt_rows(fn, "dmin", dmin, torch.int32, n_items, weekly)
+    n_rows, max_day, cold_days = int(n_rows), int(max_day), int(cold_days)
+    if not 1 <= n_rows < 2 ** 31 or not 0 <= max_day < 2 ** 31 or cold_days < 0:
+        raise ValueError(f"{fn}: need 1 <= T < 2^31, 0 <= max_day < 2^31 and cold_days >= 0")
+    out = torch.empty(len(TX_ITEM_COLUMNS), n_items, device=weekly.device, dtype=torch.float32)
+    col_sum = torch.empty(4 + 4 * ((n_items + 4095) // 4096), device=weekly.device, dtype=torch.float64)
+    with timed("tx/item_features"):
+        N.check(N.lib().rsx_tx_item_features(N.ptr(weekly), n_items, W, N.ptr(count), N.ptr(price_sum), N.ptr(dmin), n_rows,
+                                             max_day, cold_days, N.ptr(col_sum), col_sum.numel(), N.ptr(out), N.stream()), fn)
+    return out
+
+
+def tx_user_features(stats, uniq, months, max_day):
+    """The user columns from the per-customer stats (tx_segment_stats), uniq and months int32 [C] (the distinct items
+    and months, tx_segment_distinct) and the largest day: (f64 fp64 [3, C] in the order TX_USER_F64, cols fp32
+    [11, C] in the order TX_USER_COLUMNS, preferred_channel int8 [C], active_months int16 [C])."""
+    fn = "tx_user_features"
+    count = stats["count"]
+    N.ensure_device(count)
+    C = _tx_count(fn, "C", count.numel())
+    for name, dt in (("count", torch.int32), ("sum", torch.float64), ("m2", torch.float64), ("last", torch.float32),
+                     ("dmax", torch.int32), ("chan", torch.int64), ("wkend", torch.int32)):
+        _gbdt_rows(fn, name, stats[name], dt, C, count)
+    _gbdt_rows(fn, "uniq", uniq, torch.int32, C, count)
+    _gbdt_rows(fn, "months", months, torch.int32, C, count)
+    max_day = int(max_day)
+    if not 0 <= max_day < 2 ** 31:
+        raise ValueError(f"{fn}: need 0 <= max_day < 2^31 (got {max_day})")
+    dev = count.device
+    f64 = torch.empty(len(TX_USER_F64), C, device=dev, dtype=torch.float64)
+    cols = torch.empty(len(TX_USER_COLUMNS), C, device=dev, dtype=torch.float32)
+    channel = torch.empty(C, device=dev, dtype=torch.int8)
+    active = torch.empty(C, device=dev, dtype=torch.int16)
+    ws = torch.empty(4 * C + 8 + 4 * ((C + 4095) // 4096), device=dev, dtype=torch.float64)
+    with timed("tx/user_features"):
+        N.check(N.lib().rsx_tx_user_features(N.ptr(count), N.ptr(stats["sum"]), N.ptr(stats["m2"]), N.ptr(stats["last"]),
+                                             N.ptr(stats["dmax"]), N.ptr(stats["chan"]), N.ptr(stats["wkend"]), N.ptr(uniq),
+                                             N.ptr(months), C, max_day, N.ptr(ws), ws.numel() * 8, N.ptr(f64), N.ptr(cols),
+                                             N.ptr(channel), N.ptr(active), N.stream()), fn)
+    return f64, cols, channel, active
+
+
+def quantile_bucket(x, q=10, return_edges=False):
+    """pd.qcut(x, q, labels=False, duplicates='drop') + 1 of x fp64 [n] on the device, int8 [n]: the edges are the
+    linear interpolations at (n - 1) k / q of the sorted copy (torch.sort, plumbing) in the float64 steps pandas
+    takes (include/recsys_amd.h: the same bits as pd.Series.quantile), equal edges dropped, bucket =
+    #{edges < x}, the lowest edge in bucket 1; a constant column is 1 everywhere. No host read. With return_edges
+    also (edges fp64 [q + 1], n_edges int32 [1])."""
+    fn = "quantile_bucket"
+    N.ensure_device(x)
+    n, q = x.numel(), int(q)
+    if not 1 <= n < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= n < 2^31 values (got {n})")
+    _gbdt_rows(fn, "x", x, torch.float64, n, x)
+    if not 1 <= q <= TX_MAX_QUANTILES:
+        raise ValueError(f"{fn}: need 1 <= q <= {TX_MAX_QUANTILES} (got {q})")
+    s = torch.sort(x).values
+    edges = torch.zeros(q + 1, device=x.device, dtype=torch.float64)
+    n_edges = torch.zeros(1, device=x.device, dtype=torch.int32)
+    bucket = torch.empty(n, device=x.device, dtype=torch.int8)
+    with timed("tx/quantile_bucket"):
+        N.check(N.lib().rsx_quantile_bucket(N.ptr(x), N.ptr(s), n, q, N.ptr(edges), N.ptr(n_edges), N.ptr(bucket),
+                                            N.stream()), fn)
+    return (bucket, edges, n_edges) if return_edges else bucket
+
+
+def tx_sequences(row_seg, C, item, day, valid, max_len=50):
+    """Per customer of row_seg int32 [T] the last max_len rows whose item is marked in valid uint8 [N]: the CSR
+    (seq_off int64 [C + 1], seq_item int32, seq_delta int32 = the day of the customer's last kept row - day), in
+    table order. A customer without a valid row has an empty range. One host read (the number of kept rows)."""
+    fn = "tx_sequences"
+    T = _tx_rows(fn, row_seg)
+    C, max_len = _tx_count(fn, "C", C), int(max_len)
+    _gbdt_rows(fn, "item", item, torch.int32, T, row_seg)
+    _gbdt_rows(fn, "day", day, torch.int32, T, row_seg)
+    if valid.dtype != torch.uint8 or valid.dim() != 1 or not 1 <= valid.numel() < 2 ** 31 or not valid.is_contiguous():
+        raise ValueError(f"{fn}: valid must be a contiguous uint8 vector over the items")
+    if valid.device != row_seg.device:
+        raise RuntimeError(f"{fn}: valid is on {valid.device}, expected {row_seg.device}")
+    if max_len < 1:
+        raise ValueError(f"{fn}: max_len must be >= 1 (got {max_len})")
+    dev = row_seg.device
+    rank = torch.empty(T, device=dev, dtype=torch.int32)
+    n_valid = torch.empty(C, device=dev, dtype=torch.int32)
+    last_day = torch.empty(C, device=dev, dtype=torch.int32)
+    ws = _tx_ws(T, dev)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/sequence_ranks"):
+        N.check(N.lib().rsx_tx_sequence_ranks(N.ptr(row_seg), C, T, N.ptr(item), N.ptr(day), N.ptr(valid), valid.numel(),
+                                              N.ptr(ws), ws.numel(), N.ptr(rank), N.ptr(n_valid), N.ptr(last_day),
+                                              N.ptr(flag), N.stream()), fn)
+    seq_off = torch.zeros(C + 1, device=dev, dtype=torch.int64)
+    torch.cumsum(n_valid.clamp(max=max_len), 0, out=seq_off[1:])
+    n_out = int(seq_off[-1])
+    seq_item = torch.empty(n_out, device=dev, dtype=torch.int32)
+    seq_delta = torch.empty(n_out, device=dev, dtype=torch.int32)
+    with timed("tx/sequences"):
+        N.check(N.lib().rsx_tx_sequences(N.ptr(row_seg), C, T, N.ptr(item), N.ptr(day), N.ptr(rank), N.ptr(last_day),
+                                         N.ptr(seq_off), max_len, n_out, N.ptr(seq_item), N.ptr(seq_delta), N.ptr(flag),
+                                         N.stream()), fn)
+    _TX_SEQ_GUARD.watch(flag)
+    return seq_off, seq_item, seq_delta
+
+
+# ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}
 
