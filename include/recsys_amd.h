@@ -1358,6 +1358,74 @@ int rsx_tx_sequence_ranks(const int* row_seg, int64_t C, int64_t T, const int* i
 int rsx_tx_sequences(const int* row_seg, int64_t C, int64_t T, const int* item, const int* day, const int* rank,
                      const int* last_day, const int64_t* seq_off, int max_len, int64_t n_out, int* seq_item,
                      int* seq_delta, int* flag, void* stream);
+/* The persona columns (reference staticstics/preprocess_clustering.py) add three passes in the same shape:
+ *   segment runs: val int32 [T] non-decreasing inside every segment (flag bit 1 on a decreasing pair, as segment
+ *          distinct). A run is a maximal stretch of equal val inside one segment, of length n. Per segment: runs
+ *          int32 = the number of runs (= segment distinct), repeated int32 = the sum of n over the runs with n > 1,
+ *          nlogn double = the sum of n ln n over the runs, in fp64, the runs in their order through the fixed
+ *          scan. Two passes: the inclusive maximum of "t + 1 where a run starts" gives every run's last row its
+ *          length; the lengths' contributions are summed per segment. With n = count: ln n - nlogn / n is the
+ *          entropy of the value counts (natural log), repeated / n the share of rows whose value occurs more than
+ *          once. ws: rsx_tx_workspace_bytes(T) + 4 T bytes (the tiles' slots, then one int32 per row).
+ *   segment sum f64: x double [T] (read through perm as segment stats does): count int32, sum double = the fp64
+ *          sum, m2 double = sum (x - sum / count)^2 (a second pass; NULL: not computed). A flag column is summed
+ *          as 0.0 / 1.0, exactly. A segment without rows has zeros.
+ *   price ratio: ratio[t] = (double)price[t] / cat_mean[item_cat[item[t]]] in fp64, item_cat int32 [N], cat_mean
+ *          double [n_cat]. An item outside [0, N) or a category outside [0, n_cat) gives 0 and sets flag bit 0. */
+int rsx_tx_segment_runs(const int* row_seg, int64_t S, int64_t T, const int* val, void* ws, int64_t ws_bytes,
+                        int* runs, int* repeated, double* nlogn, int* flag, void* stream);
+int rsx_tx_segment_sum_f64(const int* row_seg, int64_t S, int64_t T, const int64_t* perm, const double* x, void* ws,
+                           int64_t ws_bytes, int* count, double* sum, double* m2, int* flag, void* stream);
+int rsx_tx_price_ratio(const int* item, const float* price, int64_t T, const int* item_cat, const double* cat_mean,
+                       int64_t N, int64_t n_cat, double* ratio, int* flag, void* stream);
+
+/* ---- A21 k-means on a fixed-point grid: the customer personas, csrc/kmeans.hip ---------------------------------
+ * The reference standardises seven per-customer columns and runs scikit-learn's KMeans on the host
+ * (staticstics/preprocess_clustering.py). Here the clustering runs on q int32 [d, C], feature-major, standing for
+ * the values q 2^-frac_bits exactly. A cluster's sum is then an integer, so the centres, and with them the whole
+ * trajectory, are the same bits every run and in any row order. Limits: d <= 32, K <= 256, K d <= 4096, C < 2^31;
+ * anything else is an error. max_workgroups caps every row kernel's grid (min(ceil(C / 256), max_workgroups)
+ * workgroups stride over the 256-row tiles); it changes no result. flag is int32, OR-ed; no access leaves its
+ * array whatever the inputs hold (a label is written, never used as an index unchecked).
+ *   standardize columns: x double [d, C]: mean = sum / C and var = sum (x - mean)^2 / C (ddof = 0) from the
+ *          two-pass fixed-order two-level sums of "item features" above; scale = sqrt(var), or 1 for a constant
+ *          column: var <= C eps var + (C mean eps)^2 with eps = 2^-52, scikit-learn's rule, which holds var = 0.
+ *          out = (x - mean) / scale (NULL: the moments only). ws: (2 + ceil(C / 4096)) d doubles.
+ *   quantize: q = rint(x 2^frac_bits) (ties to even), 0 <= frac_bits <= 30. A value outside +-(2^31 - 1) is
+ *          clamped there, a NaN becomes 0; both set flag bit 0.
+ *   distance: D(i, k) = sum_j (x_ij - c_kj)^2 with x_ij = (double)q 2^-frac_bits, in fp64, j ascending from an
+ *          accumulator of 0, the subtraction first, product and sum not contracted. The label of a row is the
+ *          smallest k among the minima.
+ *   seed (k-means++ as an exponential race): seeds[0] = hash_u32(seed, 0) mod C. Round r = 1 .. K - 1: dmin_i =
+ *          min(dmin_i, D(i, row seeds[r - 1])); u_i = (hash_u32(seed + r, i) + 0.5) 2^-32 (csrc/rsx_common.h);
+ *          key_i = dmin_i / -ln u_i; seeds[r] = the row with the largest key, the lowest row on ties. Row i wins
+ *          with probability dmin_i / sum dmin, and a row with dmin = 0 only when every row has. One launch per
+ *          round leaves a candidate per workgroup, a one-workgroup launch picks among them; no host read.
+ *          centres double [K, d] = the seed rows. ws: rsx_kmeans_seed_workspace_bytes(C, max_workgroups) = 8 C +
+ *          16 min(ceil(C / 256), max_workgroups) bytes, 16-byte aligned.
+ *   iterate (Lloyd): n_iter iterations numbered from first_iteration >= 1, all enqueued. An iteration assigns
+ *          every row (the centres in LDS, one row per thread), each workgroup adds int64 sum_q [K, d], int32 count
+ *          [K] and the number of rows whose label changed in LDS over its tiles and flushes the non-zero slots
+ *          with integer atomic adds; then one workgroup sets c_kj = (double)sum_q / ((double)count 2^frac_bits) (a
+ *          cluster without rows keeps its centre), shift = sum_k sum_j (c_new - c_old)^2 sequentially, k outer, j
+ *          inner, ctl[1] (done) = the iteration's number the first time changed == 0 or shift <= tol_abs, and
+ *          clears the accumulators. Once done is set the later kernels return at once, so the result does not
+ *          depend on n_iter. The caller zeroes sum_q, count and ctl int32 [4] = {changed, done, iterations run, 0}
+ *          and fills labels with -1 before the first call; shift double [1] holds the last shift.
+ *   assign: labels int32 [C] and, when given, dmin double [C] = D(i, label) and inertia double [1] = the fixed-order
+ *          two-level sum of dmin (ws: ceil(C / 4096) doubles). */
+int rsx_standardize_columns(const double* x, int64_t d, int64_t C, double* ws, int64_t ws_doubles, double* out,
+                            double* mean, double* var, double* scale, void* stream);
+int rsx_kmeans_quantize(const double* x, int64_t d, int64_t C, int frac_bits, int* q, int* flag, void* stream);
+int64_t rsx_kmeans_seed_workspace_bytes(int64_t C, int64_t max_workgroups);
+int rsx_kmeans_seed(const int* q, int64_t d, int64_t C, int frac_bits, int64_t K, uint64_t seed, int64_t max_workgroups,
+                    void* ws, int64_t ws_bytes, int* seeds, double* centres, int* flag, void* stream);
+int rsx_kmeans_iterate(const int* q, int64_t d, int64_t C, int frac_bits, int64_t K, double* centres, int* labels,
+                       int64_t* sum_q, int* count, int* ctl, double* shift, double tol_abs, int first_iteration,
+                       int n_iter, int64_t max_workgroups, void* stream);
+int rsx_kmeans_assign(const int* q, int64_t d, int64_t C, int frac_bits, int64_t K, const double* centres,
+                      int64_t max_workgroups, double* ws, int64_t ws_doubles, int* labels, double* dmin,
+                      double* inertia, void* stream);
 
 #ifdef __cplusplus
 }

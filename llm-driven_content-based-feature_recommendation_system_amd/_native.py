@@ -248,6 +248,16 @@ _SIGS = {
     "rsx_quantile_bucket": (c_i, [c_p, c_p, c_i64, c_i, c_p, c_p, c_p, c_p]),
     "rsx_tx_sequence_ranks": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "rsx_tx_sequences": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_i, c_i64, c_p, c_p, c_p, c_p]),
+    "rsx_tx_segment_runs": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_tx_segment_sum_f64": (c_i, [c_p, c_i64, c_i64, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_tx_price_ratio": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    "rsx_standardize_columns": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_kmeans_quantize": (c_i, [c_p, c_i64, c_i64, c_i, c_p, c_p, c_p]),
+    "rsx_kmeans_seed_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "rsx_kmeans_seed": (c_i, [c_p, c_i64, c_i64, c_i, c_i64, c_u64, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "rsx_kmeans_iterate": (c_i, [c_p, c_i64, c_i64, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_d, c_i, c_i, c_i64,
+                                 c_p]),
+    "rsx_kmeans_assign": (c_i, [c_p, c_i64, c_i64, c_i, c_i64, c_p, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())

@@ -1,7 +1,9 @@
 // The towers' feature frames from the transaction log (reference staticstics/preprosess_agg_parallel.py): the
 // calendar columns, per-customer and per-item statistics, the weekly sales matrix, the item and user columns,
-// quantile buckets and the cleaned sequences. Specified in include/recsys_amd.h ("transaction features") and
-// restated in pandas / numpy float64 by tests/tx_features_ref.py.
+// quantile buckets and the cleaned sequences; and the passes behind the persona columns (reference
+// staticstics/preprocess_clustering.py): run statistics, float64 segment sums and the price ratio. Specified in
+// include/recsys_amd.h ("transaction features") and restated in pandas / numpy float64 by tests/tx_features_ref.py
+// and tests/persona_ref.py.
 //
 // Every per-segment quantity is a segmented scan over the rows in their sorted order, the shape of gbdt_ts.hip:
 //   seg_tile_k<P, REV, false>  per 256-row tile the segmented workgroup scan (rsx_block.h) -> the tile's aggregate
@@ -12,6 +14,7 @@
 // the order of combination is fixed: the same bits every run, floating-point sums included. The only atomics are
 // integer: the OR into flag, the maximum of the segment marks and the counts of the weekly matrix.
 #include "rsx_block.h"
+#include "rsx_colsum.h"
 #include "rsx_common.h"
 
 #include <limits.h>
@@ -307,43 +310,9 @@ __global__ __launch_bounds__(kThreads) void weekly_k(const int* __restrict__ ite
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// fixed-order column sums in two levels. Workgroup (k, c) sums chunk k of x[c, 0 .. n), len elements (minus mean_of[c] /
-// n_mean, squared, when mean_of is given): thread j takes the chunk's elements j, j + 256, ... in order, then the 256
-// partial sums meet in a fixed tree; out[c, k]. col_sums runs it over chunks of 4096, then once more over the chunk sums.
-template <class T>
-__global__ __launch_bounds__(kThreads) void col_reduce_k(const T* __restrict__ x, int64_t n, int64_t len,
-                                                         const double* __restrict__ mean_of, int64_t n_mean,
-                                                         double* __restrict__ out) {
-  __shared__ double sm[kThreads];
-  const T* col = x + (int64_t)blockIdx.y * n;
-  const int64_t lo = (int64_t)blockIdx.x * len, hi = lo + len < n ? lo + len : n;
-  const double mean = mean_of ? mean_of[blockIdx.y] / (double)n_mean : 0.0;
-  double acc = 0.0;
-  for (int64_t i = lo + threadIdx.x; i < hi; i += kThreads) {
-    const double v = (double)col[i] - mean;
-    acc += mean_of ? v * v : v;
-  }
-  sm[threadIdx.x] = acc;
-  __syncthreads();
-  for (int s = kThreads / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = sm[0];
-}
-
-constexpr int kChunk = 4096;
-int64_t chunks_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
-
-// out[c] = the sum over x[c, 0 .. n) for c < cols; part holds cols * chunks_of(n) doubles
-template <class T>
-void col_sums(const T* x, int64_t n, int cols, const double* mean_of, double* part, double* out, hipStream_t st) {
-  const int64_t nc = chunks_of(n);
-  hipLaunchKernelGGL(col_reduce_k<T>, dim3((unsigned)nc, (unsigned)cols), dim3(kThreads), 0, st, x, n, (int64_t)kChunk, mean_of, n,
-                     part);
-  hipLaunchKernelGGL(col_reduce_k<double>, dim3(1, (unsigned)cols), dim3(kThreads), 0, st, (const double*)part, nc, nc,
-                     (const double*)nullptr, nc, out);
-}
+// fixed-order column sums in two levels: rsx_colsum.h
+using rsx::col_sums;
+int64_t chunks_of(int64_t n) { return rsx::col_chunks(n); }
 
 // ---------------------------------------------------------------------------------------------------------
 // 5. item columns
@@ -544,6 +513,147 @@ __global__ __launch_bounds__(kThreads) void seq_write_k(const int* __restrict__ 
   seq_delta[pos] = last_day[sid] - day[t];
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// 9. runs of a column that is non-decreasing inside every segment (the persona columns). A run starts at a segment's
+// first row and wherever val changes. RunLenP: the inclusive maximum of "t + 1 where a run starts" is the start of
+// the run a row is in, so a run's last row knows its length; tail_len[t] = that length there and 0 elsewhere.
+// RunSumP sums what the run tails contribute per segment.
+struct RunLenP {
+  using V = IntV;
+  using Op = MaxInt;
+  const int* val;
+  int S;
+  int* tail_len;
+  int* flag;
+  __device__ void unordered() const { atomicOr(flag, 1); }
+  __device__ static V ident() { return V{0}; }
+  __device__ V load(int64_t t, int sid, bool first) const {
+    if ((unsigned)sid >= (unsigned)S) {
+      if (first && sid >= S) atomicOr(flag, 1);
+      return ident();
+    }
+    if (first) return V{(int)t + 1};
+    const int a = val[t - 1], b = val[t];
+    if (b < a) atomicOr(flag, 2);
+    return V{a != b ? (int)t + 1 : 0};
+  }
+  __device__ void store(int64_t t, int sid, V incl, V, bool tail) const {
+    int len = 0;
+    if ((unsigned)sid < (unsigned)S && incl.n >= 1 && (tail || val[t + 1] != val[t])) len = (int)t + 2 - incl.n;
+    tail_len[t] = len;
+  }
+};
+
+struct RunV {
+  double nlogn;
+  int runs, repeated;
+};
+struct RunOp {
+  __device__ __forceinline__ RunV operator()(RunV a, RunV b) const {
+    return RunV{a.nlogn + b.nlogn, a.runs + b.runs, a.repeated + b.repeated};
+  }
+};
+struct RunSumP {
+  using V = RunV;
+  using Op = RunOp;
+  const int* tail_len;
+  int S;
+  int *runs, *repeated;
+  double* nlogn;
+  __device__ void unordered() const {}
+  __device__ static V ident() { return V{0.0, 0, 0}; }
+  __device__ V load(int64_t t, int sid, bool) const {
+    if ((unsigned)sid >= (unsigned)S) return ident();
+    const int n = tail_len[t];
+    if (n <= 0) return ident();
+    return V{(double)n * log((double)n), 1, n > 1 ? n : 0};
+  }
+  __device__ void store(int64_t, int sid, V incl, V, bool tail) const {
+    if (!tail || (unsigned)sid >= (unsigned)S) return;
+    runs[sid] = incl.runs;
+    repeated[sid] = incl.repeated;
+    nlogn[sid] = incl.nlogn;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// 10. count, sum and two-pass M2 of a double column per segment: StatsP / M2P without the table's columns
+struct SumV {
+  double sum;
+  int cnt;
+};
+struct SumOp {
+  __device__ __forceinline__ SumV operator()(SumV a, SumV b) const { return SumV{a.sum + b.sum, a.cnt + b.cnt}; }
+};
+struct SumF64P {
+  using V = SumV;
+  using Op = SumOp;
+  const int64_t* perm;
+  const double* x;
+  int64_t T;
+  int S;
+  int* count;
+  double* sum;
+  int* flag;
+  __device__ void unordered() const { atomicOr(flag, 1); }
+  __device__ static V ident() { return V{0.0, 0}; }
+  __device__ V load(int64_t t, int sid, bool first) const {
+    if (first && sid >= S) atomicOr(flag, 1);
+    if ((unsigned)sid >= (unsigned)S) return ident();
+    const int64_t r = row_at(perm, t, T, flag);
+    if (r < 0) return ident();
+    return V{x[r], 1};
+  }
+  __device__ void store(int64_t, int sid, V incl, V, bool tail) const {
+    if (!tail || (unsigned)sid >= (unsigned)S) return;
+    count[sid] = incl.cnt;
+    sum[sid] = incl.sum;
+  }
+};
+struct M2F64P {
+  using V = DblV;
+  using Op = AddDbl;
+  const int64_t* perm;
+  const double* x;
+  int64_t T;
+  int S;
+  const int* count;
+  const double* sum;
+  double* m2;
+  int* flag;
+  __device__ void unordered() const { atomicOr(flag, 1); }
+  __device__ static V ident() { return V{0.0}; }
+  __device__ V load(int64_t t, int sid, bool) const {
+    if ((unsigned)sid >= (unsigned)S) return ident();
+    const int64_t r = row_at(perm, t, T, flag);
+    const int n = count[sid];
+    if (r < 0 || n <= 0) return ident();
+    const double d = x[r] - sum[sid] / (double)n;
+    return V{d * d};
+  }
+  __device__ void store(int64_t, int sid, V incl, V, bool tail) const {
+    if (tail && (unsigned)sid < (unsigned)S) m2[sid] = incl.s;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// 11. the price of a row over the mean price of its item's category
+__global__ __launch_bounds__(kThreads) void price_ratio_k(const int* __restrict__ item, const float* __restrict__ price, int64_t T,
+                                                          const int* __restrict__ item_cat, const double* __restrict__ cat_mean,
+                                                          int64_t N, int n_cat, double* __restrict__ ratio, int* flag) {
+  const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (t >= T) return;
+  const int i = item[t];
+  int c = -1;
+  if ((uint64_t)i < (uint64_t)N) c = item_cat[i];
+  if ((unsigned)c >= (unsigned)n_cat) {
+    atomicOr(flag, 1);
+    ratio[t] = 0.0;
+    return;
+  }
+  ratio[t] = (double)price[t] / cat_mean[c];
+}
+
 bool ws_ok(const void* ws, int64_t ws_bytes, int64_t T) { return ws && rsx::aligned16(ws) && ws_bytes >= kTileBytes * tiles_of(T); }
 
 }  // namespace
@@ -706,6 +816,53 @@ RSX_API int rsx_tx_sequences(const int* row_seg, int64_t C, int64_t T, const int
   if (n_out == 0) return 0;
   hipLaunchKernelGGL(seq_write_k, dim3((unsigned)tiles_of(T)), dim3(kThreads), 0, (hipStream_t)stream, row_seg, C, T, item, day,
                      rank, last_day, seq_off, max_len, n_out, seq_item, seq_delta, flag);
+  RSX_LAUNCHED();
+  return 0;
+}
+
+RSX_API int rsx_tx_segment_runs(const int* row_seg, int64_t S, int64_t T, const int* val, void* ws, int64_t ws_bytes,
+                                int* runs, int* repeated, double* nlogn, int* flag, void* stream) {
+  RSX_ARG(row_seg && val && runs && repeated && nlogn && flag, "null tensor");
+  RSX_ARG(rows_ok(T), "need 1 <= T < 2^31 rows");
+  RSX_ARG(S >= 1 && S < (1ll << 31) - 1, "need 1 <= S < 2^31 - 1 segments");
+  RSX_ARG(ws && rsx::aligned16(ws) && ws_bytes >= kTileBytes * tiles_of(T) + 4 * T,
+          "workspace too small (rsx_tx_workspace_bytes(T) + 4 T bytes) or not 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  int* tail_len = rsx::at<int>(ws, kTileBytes * tiles_of(T));      // behind the tiles' slots
+  (void)hipMemsetAsync(runs, 0, (size_t)S * 4, st);
+  (void)hipMemsetAsync(repeated, 0, (size_t)S * 4, st);
+  (void)hipMemsetAsync(nlogn, 0, (size_t)S * 8, st);
+  run_pass<RunLenP, false>(RunLenP{val, (int)S, tail_len, flag}, row_seg, T, ws, st);
+  run_pass<RunSumP, false>(RunSumP{tail_len, (int)S, runs, repeated, nlogn}, row_seg, T, ws, st);
+  RSX_LAUNCHED();
+  return 0;
+}
+
+RSX_API int rsx_tx_segment_sum_f64(const int* row_seg, int64_t S, int64_t T, const int64_t* perm, const double* x, void* ws,
+                                   int64_t ws_bytes, int* count, double* sum, double* m2, int* flag, void* stream) {
+  RSX_ARG(row_seg && x && count && sum && flag, "null tensor");
+  RSX_ARG(rows_ok(T), "need 1 <= T < 2^31 rows");
+  RSX_ARG(S >= 1 && S < (1ll << 31) - 1, "need 1 <= S < 2^31 - 1 segments");
+  RSX_ARG(ws_ok(ws, ws_bytes, T), TX_WS_MSG);
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipMemsetAsync(count, 0, (size_t)S * 4, st);
+  (void)hipMemsetAsync(sum, 0, (size_t)S * 8, st);
+  run_pass<SumF64P, false>(SumF64P{perm, x, T, (int)S, count, sum, flag}, row_seg, T, ws, st);
+  if (m2) {
+    (void)hipMemsetAsync(m2, 0, (size_t)S * 8, st);
+    run_pass<M2F64P, false>(M2F64P{perm, x, T, (int)S, count, sum, m2, flag}, row_seg, T, ws, st);
+  }
+  RSX_LAUNCHED();
+  return 0;
+}
+
+RSX_API int rsx_tx_price_ratio(const int* item, const float* price, int64_t T, const int* item_cat, const double* cat_mean,
+                               int64_t N, int64_t n_cat, double* ratio, int* flag, void* stream) {
+  RSX_ARG(item && price && item_cat && cat_mean && ratio && flag, "null tensor");
+  RSX_ARG(rows_ok(T), "need 1 <= T < 2^31 rows");
+  RSX_ARG(N >= 1 && N < (1ll << 31) && n_cat >= 1 && n_cat <= N, "need 1 <= n_cat <= N < 2^31 categories and items");
+  hipLaunchKernelGGL(price_ratio_k, dim3((unsigned)tiles_of(T)), dim3(kThreads), 0, (hipStream_t)stream, item, price, T, item_cat,
+                     cat_mean, N, (int)n_cat, ratio, flag);
   RSX_LAUNCHED();
   return 0;
 }

@@ -4874,6 +4874,267 @@ def tx_sequences(row_seg, C, item, day, valid, max_len=50):
     return seq_off, seq_item, seq_delta
 
 
+# the persona columns' passes (reference staticstics/preprocess_clustering.py)
+PERSONA_COLUMNS = ("basket_size", "avg_price", "cat_entropy", "long_tail_ratio", "weekend_ratio", "repurchase_rate",
+                   "relative_price_pos")
+_TX_RUNS_GUARD = IdRangeGuard("tx_segment_runs: a value column that decreases inside a segment, or a row_seg that "
+                              "decreases or has an entry >= S")
+_TX_SUM_GUARD = IdRangeGuard("tx_segment_sum_f64: a row_seg that decreases or has an entry >= S, or a perm entry outside "
+                             "[0, T)")
+_TX_RATIO_GUARD = IdRangeGuard("tx_price_ratio: an item outside [0, N) or a category outside [0, n_cat)")
+
+
+def tx_segment_runs(row_seg, S, val):
+    """The runs of val int32 [T] (non-decreasing inside every segment of row_seg) per segment: (runs int32 [S] = the
+    number of runs = tx_segment_distinct, repeated int32 [S] = the rows in runs longer than one, nlogn fp64 [S] =
+    sum n ln n over the runs). ln n - nlogn / n is the entropy of the value counts, repeated / n the share of rows
+    whose value occurs more than once. A decreasing pair raises IndexError at a later call (_TX_RUNS_GUARD)."""
+    fn = "tx_segment_runs"
+    T = _tx_rows(fn, row_seg)
+    S = _tx_count(fn, "S", S)
+    _gbdt_rows(fn, "val", val, torch.int32, T, row_seg)
+    dev = row_seg.device
+    runs = torch.empty(S, device=dev, dtype=torch.int32)
+    repeated = torch.empty(S, device=dev, dtype=torch.int32)
+    nlogn = torch.empty(S, device=dev, dtype=torch.float64)
+    ws = torch.empty(N.lib().rsx_tx_workspace_bytes(T) + 4 * T, device=dev, dtype=torch.uint8)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/segment_runs"):
+        N.check(N.lib().rsx_tx_segment_runs(N.ptr(row_seg), S, T, N.ptr(val), N.ptr(ws), ws.numel(), N.ptr(runs),
+                                            N.ptr(repeated), N.ptr(nlogn), N.ptr(flag), N.stream()), fn)
+    _TX_RUNS_GUARD.watch(flag)
+    return runs, repeated, nlogn
+
+
+def tx_segment_sum_f64(row_seg, S, x, perm=None, m2=True):
+    """(count int32, sum fp64, m2 fp64 or None), each [S]: per segment of row_seg int32 [T] the rows, the fp64 sum of
+    x fp64 [T] (read through perm int64 [T] when given) and, with m2, sum (x - sum / count)^2 from a second pass.
+    Fixed combination order: the same bits every call; a 0.0 / 1.0 column is counted exactly."""
+    fn = "tx_segment_sum_f64"
+    T = _tx_rows(fn, row_seg)
+    S = _tx_count(fn, "S", S)
+    _gbdt_rows(fn, "x", x, torch.float64, T, row_seg)
+    if perm is not None:
+        _gbdt_rows(fn, "perm", perm, torch.int64, T, row_seg)
+    dev = row_seg.device
+    count = torch.empty(S, device=dev, dtype=torch.int32)
+    total = torch.empty(S, device=dev, dtype=torch.float64)
+    second = torch.empty(S, device=dev, dtype=torch.float64) if m2 else None
+    ws = _tx_ws(T, dev)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("tx/segment_sum_f64"):
+        N.check(N.lib().rsx_tx_segment_sum_f64(N.ptr(row_seg), S, T, N.ptr(perm), N.ptr(x), N.ptr(ws), ws.numel(),
+                                               N.ptr(count), N.ptr(total), N.ptr(second), N.ptr(flag), N.stream()), fn)
+    _TX_SUM_GUARD.watch(flag)
+    return count, total, second
+
+
+def tx_price_ratio(item, price, item_cat, cat_mean):
+    """ratio fp64 [T] = price / cat_mean[item_cat[item]] in fp64: item int32 [T], price fp32 [T], item_cat int32 [N],
+    cat_mean fp64 [n_cat]. An item or category out of range gives 0 and raises IndexError at a later call
+    (_TX_RATIO_GUARD.check())."""
+    fn = "tx_price_ratio"
+    T = _tx_rows(fn, item, "item")
+    _gbdt_rows(fn, "price", price, torch.float32, T, item)
+    n_items, n_cat = item_cat.numel(), cat_mean.numel()
+    if not 1 <= n_cat <= n_items < 2 ** 31:
+        raise ValueError(f"{fn}: need 1 <= n_cat <= N < 2^31 (got n_cat {n_cat}, N {n_items})")
+    _gbdt_rows(fn, "item_cat", item_cat, torch.int32, n_items, item)
+    _gbdt_rows(fn, "cat_mean", cat_mean, torch.float64, n_cat, item)
+    ratio = torch.empty(T, device=item.device, dtype=torch.float64)
+    flag = torch.zeros(1, device=item.device, dtype=torch.int32)
+    with timed("tx/price_ratio"):
+        N.check(N.lib().rsx_tx_price_ratio(N.ptr(item), N.ptr(price), T, N.ptr(item_cat), N.ptr(cat_mean), n_items, n_cat,
+                                           N.ptr(ratio), N.ptr(flag), N.stream()), fn)
+    _TX_RATIO_GUARD.watch(flag)
+    return ratio
+
+
+# ----------------------------------------------------------------------------------------
+# A21 k-means on a fixed-point grid (csrc/kmeans.hip; include/recsys_amd.h, "k-means"). The data are feature-major:
+# X fp64 [d, C], q int32 [d, C] standing for q 2^-frac_bits; centres fp64 [K, d].
+KMEANS_MAX_D = 32
+KMEANS_MAX_K = 256
+KMEANS_MAX_KD = 4096
+KMEANS_MAX_FRAC_BITS = 20
+KMEANS_POLL = 8           # iterations enqueued between two looks at the done flag
+_CUS = {}
+
+
+def num_cus(device=None) -> int:
+    """The compute units of a device (grid sizing, speed only)."""
+    idx = torch.device("cuda" if device is None else device).index
+    idx = torch.cuda.current_device() if idx is None else idx
+    if idx not in _CUS:
+        _CUS[idx] = int(torch.cuda.get_device_properties(idx).multi_processor_count)
+    return _CUS[idx]
+
+
+def _km_matrix(fn, name, t, dtype, ref=None):
+    """t is a contiguous dtype [d, C] device matrix; returns (d, C)."""
+    N.ensure_device(t)
+    if t.dtype != dtype:
+        raise TypeError(f"{fn}: {name} must be {dtype}, got {t.dtype}")
+    if ref is not None and t.device != ref.device:
+        raise RuntimeError(f"{fn}: {name} is on {t.device}, expected {ref.device}")
+    if t.dim() != 2 or t.numel() == 0 or not t.is_contiguous():
+        raise ValueError(f"{fn}: {name} must be a contiguous non-empty matrix, got shape {tuple(t.shape)}")
+    return t.shape[0], t.shape[1]
+
+
+def _km_shape(fn, d, C, K):
+    if not (1 <= d <= KMEANS_MAX_D and 1 <= K <= KMEANS_MAX_K and K * d <= KMEANS_MAX_KD and 1 <= C < 2 ** 31):
+        raise ValueError(f"{fn}: need 1 <= d <= {KMEANS_MAX_D}, 1 <= K <= {KMEANS_MAX_K}, K d <= {KMEANS_MAX_KD} and "
+                         f"1 <= C < 2^31 rows (got d {d}, K {K}, C {C})")
+
+
+def _km_grid(max_workgroups, dev):
+    g = 4 * num_cus(dev) if max_workgroups is None else int(max_workgroups)
+    if g < 1:
+        raise ValueError(f"kmeans: max_workgroups must be >= 1 (got {g})")
+    return g
+
+
+def _km_centres(fn, centres, d, ref):
+    if centres.dtype != torch.float64 or centres.dim() != 2 or centres.shape[1] != d or not centres.is_contiguous():
+        raise ValueError(f"{fn}: centres must be a contiguous fp64 [K, {d}] matrix, got {centres.dtype} "
+                         f"{tuple(centres.shape)}")
+    if centres.device != ref.device:
+        raise RuntimeError(f"{fn}: centres is on {centres.device}, expected {ref.device}")
+    return centres.shape[0]
+
+
+def standardize_columns(X, out=True):
+    """X fp64 [d, C], feature-major -> ((X - mean) / scale fp64 [d, C], mean, scale, var), each of the last three fp64
+    [d]: sklearn's StandardScaler (population variance, scale 1 for a constant column) from two-pass fixed-order
+    sums: the same bits every call. out=False: the moments only (the first entry is None)."""
+    fn = "standardize_columns"
+    d, C = _km_matrix(fn, "X", X, torch.float64)
+    if d > 65535 or C >= 2 ** 31:
+        raise ValueError(f"{fn}: need d <= 65535 columns of C < 2^31 values (got {d}, {C})")
+    dev = X.device
+    Z = torch.empty_like(X) if out else None
+    mean, var, scale = (torch.empty(d, device=dev, dtype=torch.float64) for _ in range(3))
+    ws = torch.empty((2 + (C + 4095) // 4096) * d, device=dev, dtype=torch.float64)
+    with timed("kmeans/standardize"):
+        N.check(N.lib().rsx_standardize_columns(N.ptr(X), d, C, N.ptr(ws), ws.numel(), N.ptr(Z), N.ptr(mean), N.ptr(var),
+                                                N.ptr(scale), N.stream()), fn)
+    return Z, mean, scale, var
+
+
+def kmeans_frac_bits(X) -> int:
+    """min(20, 30 - ceil(log2(max |X|))): the grid on which every value of X fits an int32 with a bit to spare. One
+    host read (the maximum)."""
+    m = float(X.abs().max())
+    if not math.isfinite(m):
+        raise ValueError("kmeans: the data hold a NaN or an infinity")
+    bits = KMEANS_MAX_FRAC_BITS if m == 0.0 else min(KMEANS_MAX_FRAC_BITS, 30 - math.ceil(math.log2(m)))
+    if bits < 0:
+        raise ValueError(f"kmeans: max |x| = {m} does not fit the fixed-point grid (|x| <= 2^30)")
+    return bits
+
+
+def kmeans_quantize(X, frac_bits=None):
+    """X fp64 [d, C] -> (q int32 [d, C] = rint(X 2^frac_bits), frac_bits). Raises ValueError when a value does not
+    fit or is a NaN (one host read of the flag)."""
+    fn = "kmeans_quantize"
+    d, C = _km_matrix(fn, "X", X, torch.float64)
+    frac_bits = kmeans_frac_bits(X) if frac_bits is None else int(frac_bits)
+    if not 0 <= frac_bits <= 30:
+        raise ValueError(f"{fn}: need 0 <= frac_bits <= 30 (got {frac_bits})")
+    q = torch.empty(d, C, device=X.device, dtype=torch.int32)
+    flag = torch.zeros(1, device=X.device, dtype=torch.int32)
+    with timed("kmeans/quantize"):
+        N.check(N.lib().rsx_kmeans_quantize(N.ptr(X), d, C, frac_bits, N.ptr(q), N.ptr(flag), N.stream()), fn)
+    if int(flag):
+        raise ValueError(f"{fn}: a value does not fit frac_bits = {frac_bits} (|x| 2^frac_bits < 2^31), or is a NaN")
+    return q, frac_bits
+
+
+def kmeans_seed(q, frac_bits, K, seed, max_workgroups=None):
+    """k-means++ seeds of q int32 [d, C] as an exponential race (include/recsys_amd.h): (seeds int32 [K], the rows
+    drawn, centres fp64 [K, d] = those rows). No host read; the same bits every call."""
+    fn = "kmeans_seed"
+    d, C = _km_matrix(fn, "q", q, torch.int32)
+    K = int(K)
+    _km_shape(fn, d, C, K)
+    dev = q.device
+    grid = _km_grid(max_workgroups, dev)
+    seeds = torch.empty(K, device=dev, dtype=torch.int32)
+    centres = torch.empty(K, d, device=dev, dtype=torch.float64)
+    ws = torch.empty(N.lib().rsx_kmeans_seed_workspace_bytes(C, grid), device=dev, dtype=torch.uint8)
+    flag = torch.zeros(1, device=dev, dtype=torch.int32)
+    with timed("kmeans/seed"):
+        N.check(N.lib().rsx_kmeans_seed(N.ptr(q), d, C, int(frac_bits), K, int(seed) & (2 ** 64 - 1), grid, N.ptr(ws),
+                                        ws.numel(), N.ptr(seeds), N.ptr(centres), N.ptr(flag), N.stream()), fn)
+    return seeds, centres
+
+
+def kmeans_assign(q, frac_bits, centres, max_workgroups=None, inertia=True):
+    """The nearest centre of every row of q int32 [d, C] (the smallest index among equals): (labels int32 [C], dmin
+    fp64 [C] = the squared distance to it, inertia fp64 [1] = their fixed-order sum, or None)."""
+    fn = "kmeans_assign"
+    d, C = _km_matrix(fn, "q", q, torch.int32)
+    K = _km_centres(fn, centres, d, q)
+    _km_shape(fn, d, C, K)
+    dev = q.device
+    labels = torch.empty(C, device=dev, dtype=torch.int32)
+    dmin = torch.empty(C, device=dev, dtype=torch.float64)
+    total = torch.empty(1, device=dev, dtype=torch.float64) if inertia else None
+    ws = torch.empty((C + 4095) // 4096, device=dev, dtype=torch.float64)
+    with timed("kmeans/assign"):
+        N.check(N.lib().rsx_kmeans_assign(N.ptr(q), d, C, int(frac_bits), K, N.ptr(centres), _km_grid(max_workgroups, dev),
+                                          N.ptr(ws), ws.numel(), N.ptr(labels), N.ptr(dmin), N.ptr(total), N.stream()), fn)
+    return labels, dmin, total
+
+
+class KMeansFit:
+    """centres fp64 [K, d], labels int32 [C], dmin fp64 [C], inertia fp64 [1] (all on the device), n_iter (int) and
+    counts int32 [K]: the rows of every cluster under the final labels."""
+
+    def __init__(self, centres, labels, dmin, inertia, n_iter, frac_bits):
+        self.centres, self.labels, self.dmin, self.inertia = centres, labels, dmin, inertia
+        self.n_iter, self.frac_bits = n_iter, frac_bits
+
+    @property
+    def counts(self):
+        return torch.bincount(self.labels, minlength=self.centres.shape[0]).to(torch.int32)
+
+
+def kmeans_fit(q, frac_bits, centres, tol_abs=0.0, max_iter=300, max_workgroups=None, poll=KMEANS_POLL):
+    """Lloyd's iterations on q int32 [d, C] from the centres fp64 [K, d] (not modified): an iteration assigns every
+    row, sums the clusters in integers and moves the centres; the fit ends with the first iteration after which no
+    label changed or the centres' squared shift is <= tol_abs, or after max_iter. The device decides that; the host
+    looks every `poll` iterations, which changes no result. Then one assignment against the final centres, as
+    sklearn does. Returns a KMeansFit."""
+    fn = "kmeans_fit"
+    d, C = _km_matrix(fn, "q", q, torch.int32)
+    K = _km_centres(fn, centres, d, q)
+    _km_shape(fn, d, C, K)
+    max_iter, poll, frac_bits, tol_abs = int(max_iter), int(poll), int(frac_bits), float(tol_abs)
+    if max_iter < 1 or poll < 1 or not tol_abs >= 0.0:
+        raise ValueError(f"{fn}: need max_iter >= 1, poll >= 1 and tol_abs >= 0")
+    dev = q.device
+    grid = _km_grid(max_workgroups, dev)
+    centres = centres.clone()
+    labels = torch.full((C,), -1, device=dev, dtype=torch.int32)
+    sum_q = torch.zeros(K, d, device=dev, dtype=torch.int64)
+    count = torch.zeros(K, device=dev, dtype=torch.int32)
+    ctl = torch.zeros(4, device=dev, dtype=torch.int32)
+    shift = torch.zeros(1, device=dev, dtype=torch.float64)
+    it, done = 0, 0
+    with timed("kmeans/iterate"):
+        while it < max_iter and not done:
+            n = min(poll, max_iter - it)
+            N.check(N.lib().rsx_kmeans_iterate(N.ptr(q), d, C, frac_bits, K, N.ptr(centres), N.ptr(labels), N.ptr(sum_q),
+                                               N.ptr(count), N.ptr(ctl), N.ptr(shift), tol_abs, it + 1, n, grid,
+                                               N.stream()), fn)
+            it += n
+            done = int(ctl[1])
+    labels, dmin, inertia = kmeans_assign(q, frac_bits, centres, grid)
+    return KMeansFit(centres, labels, dmin, inertia, done if done else max_iter, frac_bits)
+
+
 # ----------------------------------------------------------------------------------------
 # Optional per-op device timing (bench.py): HIP events on the launching (current) stream.
 _TIMING = {"on": False, "events": {}}

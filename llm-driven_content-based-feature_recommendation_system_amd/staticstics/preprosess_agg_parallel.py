@@ -101,14 +101,23 @@ class TransactionTable:
     def max_day(self) -> int:
         return self._get("max_day", lambda: int(self.day.max()))
 
+    def _sorted_within_customer(self, val):
+        """val int32 [T] in ascending order inside every customer: one sort of the 64-bit key (customer, val)."""
+        keys = torch.sort((self.row_customer.to(torch.int64) << 32) | val.to(torch.int64)).values
+        return (keys & 0xFFFFFFFF).to(torch.int32)
+
+    @property
+    def items_by_customer(self):
+        """int32 [T]: every customer's items in ascending order (the distinct items, the repurchase runs)."""
+        return self._get("items_by_customer", lambda: self._sorted_within_customer(self.item))
+
     def customer_stats(self):
         """ops.tx_segment_stats per customer plus uniq (distinct items) and months (distinct months), int32 [C]."""
         def make():
             seg, C = self.row_customer, self.n_customers
             weekend, month, _ = self.calendar
             st = ops.tx_segment_stats(seg, C, self.price, self.day, self.channel, weekend)
-            keys = torch.sort((seg.to(torch.int64) << 32) | self.item.to(torch.int64)).values
-            st["uniq"] = ops.tx_segment_distinct(seg, C, (keys & 0xFFFFFFFF).to(torch.int32))
+            st["uniq"] = ops.tx_segment_distinct(seg, C, self.items_by_customer)
             st["months"] = ops.tx_segment_distinct(seg, C, month)
             return st
         return self._get("customer_stats", make)
@@ -154,10 +163,63 @@ class TransactionTable:
             raise ValueError(f"TransactionTable.sequences: valid has {v.numel()} entries for {self.n_items} items")
         return ops.tx_sequences(self.row_customer, self.n_customers, self.item, self.day, v, max_len)
 
+    def item_categories(self):
+        """(item_cat int32 [N] on the device, the category codes): the reference's category_code = the first three
+        characters of the article id. The ids ascend as strings, so a category's items are contiguous and item_cat
+        does not decrease. Host work over the N items only."""
+        def make():
+            codes, cats = pd.factorize(pd.Series(_ids(self.article_ids)).str[:3].to_numpy(dtype=object))
+            return torch.from_numpy(codes.astype(np.int32)).to(self.item.device), np.asarray(cats)
+        return self._get("item_categories", make)
+
+    def persona_features(self):
+        """fp64 [7, C] in the order ops.PERSONA_COLUMNS, the behaviour columns of the reference's
+        staticstics/preprocess_clustering.py:
+          basket_size         the customer's rows n
+          avg_price           sum / n
+          cat_entropy         ln n - (sum n_c ln n_c) / n over the customer's category counts n_c (ops.tx_segment_runs
+                              over the rows sorted by (customer, category)): scipy's entropy(value_counts), natural
+                              log; 0 for a single category
+          long_tail_ratio     the share of rows whose item is not a head item. Head items: the first max(int(0.2 N),
+                              1) items by count descending, ties by ascending item index (the reference leaves
+                              ties to pandas' value_counts; this is the project's definition)
+          weekend_ratio       wkend / n
+          repurchase_rate     the share of rows whose item the customer bought more than once (repeated / n of
+                              ops.tx_segment_runs over (customer, item)). Not user_features()' repurchase_ratio =
+                              1 - uniq / n, the share of rows beyond an item's first: for purchases a, a, a, b the
+                              rate is 3/4 and the ratio 2/4. Both are kept, each for its reference module
+          relative_price_pos  the mean over the customer's rows of price / the mean price of the item's category
+        """
+        def make():
+            seg, C = self.row_customer, self.n_customers
+            st, it = self.customer_stats(), self.item_stats()
+            n = st["count"].to(torch.float64)
+            per_row = lambda total: torch.where(n > 0, total / n, torch.zeros_like(n))      # noqa: E731
+            item_cat, cats = self.item_categories()
+            item_l = self.item.to(torch.int64)
+            # categories per customer
+            runs, _, nlogn = ops.tx_segment_runs(seg, C, self._sorted_within_customer(item_cat[item_l]))
+            entropy = torch.where(runs > 1, torch.log(n) - nlogn / n, torch.zeros_like(n))
+            # head items: one stable sort of the N counts
+            n_head = max(int(0.2 * self.n_items), 1)
+            is_tail = torch.ones(self.n_items, device=seg.device, dtype=torch.float64)
+            is_tail[torch.sort(it["count"], descending=True, stable=True).indices[:n_head]] = 0.0
+            tail_rows = ops.tx_segment_sum_f64(seg, C, is_tail[item_l].contiguous(), m2=False)[1]
+            _, repeated, _ = ops.tx_segment_runs(seg, C, self.items_by_customer)
+            # the category's mean price: its items' sums over its items' counts
+            n_cat = len(cats)
+            cat_sum = ops.tx_segment_sum_f64(item_cat, n_cat, it["sum"], m2=False)[1]
+            cat_cnt = ops.tx_segment_sum_f64(item_cat, n_cat, it["count"].to(torch.float64), m2=False)[1]
+            ratio = ops.tx_price_ratio(self.item, self.price, item_cat, cat_sum / cat_cnt)
+            ratio_sum = ops.tx_segment_sum_f64(seg, C, ratio, m2=False)[1]
+            return torch.stack([n, per_row(st["sum"]), entropy, per_row(tail_rows), per_row(st["wkend"].to(torch.float64)),
+                                per_row(repeated.to(torch.float64)), per_row(ratio_sum)])
+        return self._get("persona_features", make)
+
     def check(self):
         """Raise IndexError for any range error the kernels flagged so far (waits for their flags)."""
         for g in (ops._TX_CALENDAR_GUARD, ops._TX_ROWS_GUARD, ops._TX_STATS_GUARD, ops._TX_DISTINCT_GUARD,
-                  ops._TX_WEEKLY_GUARD, ops._TX_SEQ_GUARD):
+                  ops._TX_WEEKLY_GUARD, ops._TX_SEQ_GUARD, ops._TX_RUNS_GUARD, ops._TX_SUM_GUARD, ops._TX_RATIO_GUARD):
             g.check()
 
 
