@@ -1260,6 +1260,48 @@ int rsx_gbdt_ordered_ts(const int* codes, const int64_t* order, const float* y, 
                         int64_t Vmax, double ap, double a, void* ws, int64_t ws_bytes, float* ts, int* totals,
                         float* table, int* flag, void* stream);
 
+/* ---- A22 explaining the boosted ranker: leaf weights, SHAP values and importances, csrc/gbdt_explain.hip ----
+ * CatBoost's get_feature_importance() on the oblivious-tree model of A17; restated in float64 numpy by
+ * tests/gbdt_explain_ref.py. Everything below is fp64 but the weights, which are integers.
+ *   row bits: for a tree with the levels d < depth and the splits (f_d, b_d), r_d = go right exactly as
+ *          rsx_gbdt_predict decides it (a feature >= F reads as feature 0); leaf = sum_d r_d 2^(depth-1-d).
+ *   leaf weights: w[t][l] = the number of rows of a data set that reach leaf l of tree t, int64 [T, 64], 0 at and
+ *          beyond 2^depth. Integer sums: the same bits every run and in any row order.
+ *   cover: the cover of node n of level d is the sum of w over the leaves below it.
+ *   E(s), s in {0, 1, *}^depth: E(s) = ev(root, 0) with ev(n, depth) = value[n]; ev(n, d) = ev(2n + s_d, d + 1)
+ *          where s_d is 0 or 1; else ev(n, d) = (c0 ev(2n, d+1) + c1 ev(2n+1, d+1)) / (c0 + c1) with c0, c1 the
+ *          children's covers, and 1/2 ev(2n, d+1) + 1/2 ev(2n+1, d+1) where c0 + c1 = 0 (this model's own
+ *          convention: Lundberg's path-dependent recursion divides 0 by 0 there). table[t][idx] = E(s) at idx =
+ *          sum_d s_d 3^(depth-1-d) with * as digit 2, double [T, 729]; entries at and beyond 3^depth are unused.
+ *   Shapley values of a tree: the players are its distinct split features, m <= depth of them; a feature that
+ *          splits on several levels is one player and owns all of them. v(S) = table[idx] with s_d = r_d where
+ *          f_d is in S and * elsewhere; phi_j = sum over S not holding j of |S|! (m - |S| - 1)! / m! (v(S + j) -
+ *          v(S)). A feature not in the tree has phi_j = 0 exactly.
+ *   Shapley values of a model: phi[j][r] = sum_t phi_j, j < F, and phi[F][r] = f0 + sum_t E(*, ..., *), the
+ *          expected value (CatBoost's last column), each summed in tree order by one lane: the bits do not
+ *          depend on R, the grid or the chunking. A row's F + 1 entries sum to its raw score.
+ *   PredictionValuesChange: pvc[t][d] = the sum over the pairs of leaves (l1, l2) that differ only in the bit of
+ *          level d, in ascending order, of c1 c2 / (c1 + c2) (v1 - v2)^2 (0 where c1 + c2 = 0), double [T, 6], 0
+ *          at and beyond depth. A feature's importance is the sum of its levels over the trees in tree order,
+ *          the vector scaled to sum 100 (all zeros stay zeros).
+ *   LossFunctionChange of feature j: metric(F - phi_j) - metric(F) on labelled rows, the metric the model's own
+ *          loss (CatBoost's SHAP-based approximation; positive = the feature helps). Composed in Python from
+ *          rsx_gbdt_shap and the evaluation entries.
+ * Every access stays in its array whatever the splits and bins hold. */
+/* trees rsx_gbdt_shap stages in LDS at a time */
+int64_t rsx_gbdt_shap_tree_chunk(void);
+/* weights int64 [T, 64]: the rows [tree_begin, tree_end) are zeroed here, then counted (LDS and 64-bit global integer
+ * atomics); splits int32 [T, 6, 2]. */
+int rsx_gbdt_leaf_weights(const uint8_t* bins, int64_t R, int F, const int* splits, const uint8_t* is_cat, int depth,
+                          int tree_begin, int tree_end, int64_t* weights, void* stream);
+/* leaf_values fp32 [T, 64], weights int64 [T, 64] -> table double [T, 729], pvc double [T, 6], the rows [tree_begin,
+ * tree_end). One workgroup per tree. splits is not read: both depend on the leaves and the weights alone. */
+int rsx_gbdt_explain_plan(const int* splits, const float* leaf_values, const int64_t* weights, int depth, int tree_begin,
+                          int tree_end, double* table, double* pvc, void* stream);
+/* phi double [F + 1, R] of the trees [tree_begin, tree_end). One row per lane, the trees staged through LDS. */
+int rsx_gbdt_shap(const uint8_t* bins, int64_t R, int F, const int* splits, const uint8_t* is_cat, int depth,
+                  int tree_begin, int tree_end, const double* table, double f0, double* phi, void* stream);
+
 /* ---- A20 transaction features: the towers' frames from the purchase log, csrc/tx_features.hip --------------
  * The reference builds features_user_w_meta, features_item and features_sequence with pandas groupbys and a
  * pandarallel apply per customer (staticstics/preprosess_agg_parallel.py). Here the log is a table sorted by

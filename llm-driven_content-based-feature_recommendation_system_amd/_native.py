@@ -235,6 +235,10 @@ _SIGS = {
                                c_p, c_p]),
     "rsx_gbdt_ts_keys": (c_i, [c_p, c_i64, c_i, c_u64, c_p, c_p]),
     "rsx_gbdt_ordered_ts": (c_i, [c_p, c_p, c_p, c_p, c_i64, c_i, c_i64, c_d, c_d, c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
+    "rsx_gbdt_shap_tree_chunk": (c_i64, []),
+    "rsx_gbdt_leaf_weights": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    "rsx_gbdt_explain_plan": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "rsx_gbdt_shap": (c_i, [c_p, c_i64, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_d, c_p, c_p]),
     "rsx_tx_workspace_bytes": (c_i64, [c_i64]),
     "rsx_tx_calendar": (c_i, [c_p, c_i64, c_p, c_p, c_p, c_p, c_p]),
     "rsx_tx_segment_rows": (c_i, [c_p, c_i64, c_i64, c_p, c_i64, c_p, c_p, c_p]),

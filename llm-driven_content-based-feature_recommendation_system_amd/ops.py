@@ -4487,6 +4487,109 @@ def gbdt_ordered_ts(codes, order, y, V, prior=(0.5, 1.0)):
 
 
 # ----------------------------------------------------------------------------------------
+# A22 explaining the boosted ranker (csrc/gbdt_explain.hip; include/recsys_amd.h, "explaining the boosted ranker")
+GBDT_TABLE_STRIDE = 729     # 3^6 states {0, 1, *} per level of a tree
+
+
+class GBDTExplainPlan:
+    """What gbdt_explain_plan returns, on the model's device: table float64 [T, 729] (a tree's conditional values
+    E(s), the first 3^depth entries used), pvc float64 [T, 6] (PredictionValuesChange per level), depth and
+    n_trees, the trees it covers."""
+
+    def __init__(self, table, pvc, depth, n_trees):
+        self.table, self.pvc, self.depth, self.n_trees = table, pvc, int(depth), int(n_trees)
+
+
+def _gbdt_trees(fn, model, ntree_end, dev):
+    """The checks of a GBDTModel that gbdt_predict makes (splits, leaf_values, depth, the tree count); returns
+    (T, end)."""
+    T = model.splits.shape[0]
+    end = model.n_trees if ntree_end is None else int(ntree_end)
+    if not 0 <= end <= T:
+        raise ValueError(f"{fn}: need 0 <= ntree_end <= {T} (got {end})")
+    if not 1 <= model.depth <= GBDT_MAX_DEPTH:
+        raise ValueError(f"{fn}: need 1 <= depth <= {GBDT_MAX_DEPTH} (got {model.depth})")
+    sp, lv = model.splits, model.leaf_values
+    if sp.dtype != torch.int32 or tuple(sp.shape[1:]) != (GBDT_MAX_DEPTH, 2) or not sp.is_contiguous() or sp.device != dev:
+        raise ValueError(f"{fn}: model.splits must be a contiguous int32 [T, {GBDT_MAX_DEPTH}, 2] tensor on {dev}")
+    if lv.dtype != torch.float32 or tuple(lv.shape) != (T, GBDT_LEAF_STRIDE) or not lv.is_contiguous() or lv.device != dev:
+        raise ValueError(f"{fn}: model.leaf_values must be a contiguous fp32 [{T}, {GBDT_LEAF_STRIDE}] tensor on {dev}")
+    return T, end
+
+
+def _gbdt_weights(fn, weights, end, dev):
+    """weights is a contiguous int64 [>= end, 64] tensor on dev: a row per tree in use."""
+    if weights.dtype != torch.int64:
+        raise TypeError(f"{fn}: weights must be int64, got {weights.dtype}")
+    if (weights.dim() != 2 or weights.shape[0] < end or weights.shape[1] != GBDT_LEAF_STRIDE or not weights.is_contiguous()
+            or weights.device != dev):
+        raise ValueError(f"{fn}: weights must be a contiguous int64 [>= {end}, {GBDT_LEAF_STRIDE}] tensor on {dev}, got "
+                         f"{tuple(weights.shape)} on {weights.device}")
+
+
+def gbdt_leaf_weights(bins, model, ntree_end=None, out=None):
+    """The leaf weights int64 [T, 64] of a GBDTModel over the binned rows bins uint8 [F, R]: out[t][l] = the number
+    of rows that reach leaf l of tree t (rsx_gbdt_leaf_weights: LDS and global integer atomics, the same bits every
+    run and in any row order), for the first ntree_end trees (default: model.n_trees); the other rows of a fresh
+    out are 0, those of a given out (int64 [>= ntree_end, 64]) are left as they are. No host read."""
+    F, R = _gbdt_bins("gbdt_leaf_weights", bins)
+    T, end = _gbdt_trees("gbdt_leaf_weights", model, ntree_end, bins.device)
+    _gbdt_features("gbdt_leaf_weights", model.is_cat, None, F, bins)
+    if out is None:
+        out = torch.zeros(T, GBDT_LEAF_STRIDE, device=bins.device, dtype=torch.int64)
+    else:
+        _gbdt_weights("gbdt_leaf_weights", out, end, bins.device)
+    with timed("gbdt/leaf_weights"):
+        N.check(N.lib().rsx_gbdt_leaf_weights(N.ptr(bins), R, F, N.ptr(model.splits), N.ptr(model.is_cat), model.depth, 0,
+                                              end, N.ptr(out), N.stream()), "gbdt_leaf_weights")
+    return out
+
+
+def gbdt_explain_plan(model, weights, ntree_end=None):
+    """The GBDTExplainPlan of the first ntree_end trees (default: model.n_trees) of a GBDTModel under the leaf
+    weights int64 [>= ntree_end, 64] (gbdt_leaf_weights): per tree the table of the conditional values E(s) and the
+    PredictionValuesChange of every level (rsx_gbdt_explain_plan, one workgroup per tree). The rows of the other
+    trees are 0. No host read."""
+    N.ensure_device(weights)
+    dev = weights.device
+    T, end = _gbdt_trees("gbdt_explain_plan", model, ntree_end, dev)
+    _gbdt_weights("gbdt_explain_plan", weights, end, dev)
+    table = torch.zeros(T, GBDT_TABLE_STRIDE, device=dev, dtype=torch.float64)
+    pvc = torch.zeros(T, GBDT_MAX_DEPTH, device=dev, dtype=torch.float64)
+    with timed("gbdt/explain_plan"):
+        N.check(N.lib().rsx_gbdt_explain_plan(N.ptr(model.splits), N.ptr(model.leaf_values), N.ptr(weights), model.depth, 0,
+                                              end, N.ptr(table), N.ptr(pvc), N.stream()), "gbdt_explain_plan")
+    return GBDTExplainPlan(table, pvc, model.depth, end)
+
+
+def gbdt_shap(bins, model, plan, ntree_end=None, out=None):
+    """The exact path-dependent Shapley values float64 [F + 1, R] of the binned rows bins uint8 [F, R] under the
+    first ntree_end trees (default: plan.n_trees; at most that) of a GBDTModel: row j < F is feature j's, row F
+    the expected value f0 + sum_t E_t(*, ..., *), and a row's F + 1 entries sum to its raw score
+    (rsx_gbdt_shap: one row per lane, every sum in tree order, so the bits depend neither on R nor on the grid).
+    plan: the model's GBDTExplainPlan. No host read."""
+    F, R = _gbdt_bins("gbdt_shap", bins)
+    if not isinstance(plan, GBDTExplainPlan):
+        raise TypeError(f"gbdt_shap: plan must be a GBDTExplainPlan, got {type(plan).__name__}")
+    T, end = _gbdt_trees("gbdt_shap", model, plan.n_trees if ntree_end is None else ntree_end, bins.device)
+    if end > plan.n_trees or plan.depth != model.depth:
+        raise ValueError(f"gbdt_shap: the plan covers {plan.n_trees} trees of depth {plan.depth}, asked for {end} of depth "
+                         f"{model.depth}")
+    tb = plan.table
+    if tb.dtype != torch.float64 or tuple(tb.shape) != (T, GBDT_TABLE_STRIDE) or not tb.is_contiguous() or tb.device != bins.device:
+        raise ValueError(f"gbdt_shap: plan.table must be a contiguous float64 [{T}, {GBDT_TABLE_STRIDE}] tensor on {bins.device}")
+    _gbdt_features("gbdt_shap", model.is_cat, None, F, bins)
+    if out is None:
+        out = torch.empty(F + 1, R, device=bins.device, dtype=torch.float64)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (F + 1, R) or not out.is_contiguous() or out.device != bins.device:
+        raise ValueError(f"gbdt_shap: out must be a contiguous float64 [{F + 1}, {R}] tensor on {bins.device}")
+    with timed("gbdt/shap"):
+        N.check(N.lib().rsx_gbdt_shap(N.ptr(bins), R, F, N.ptr(model.splits), N.ptr(model.is_cat), model.depth, 0, end,
+                                      N.ptr(tb), model.f0, N.ptr(out), N.stream()), "gbdt_shap")
+    return out
+
+
+# ----------------------------------------------------------------------------------------
 # A18 the ranker's training rows (csrc/ranker_rows.hip; include/recsys_amd.h, "ranker training rows")
 _RANKER_ROWS_GUARD = IdRangeGuard("ranker_sample_rows: a positive's user or item, a bought list, or a customer who "
                                   "bought every item (nothing to draw a negative from)")

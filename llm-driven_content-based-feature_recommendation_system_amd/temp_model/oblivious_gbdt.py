@@ -22,6 +22,13 @@ model bit for bit.
 reference's per-customer groups (utils/monitor/log_importer.py: X_user, X_item, y, groups): ops.GBDTGroupPlan,
 ops.gbdt_tree(groups=...) (rsx_gbdt_tree_grouped: rsx_gbdt_grad_query_softmax in place of rsx_gbdt_grad),
 ops.query_softmax_eval; restated by tests/gbdt_rank_ref.py. The two classes share everything but fit.
+
+Explanations (include/recsys_amd.h, "explaining the boosted ranker"; csrc/gbdt_explain.hip; restated by
+tests/gbdt_explain_ref.py): a fit ends by counting the training rows per leaf (leaf_weights_, CatBoost's leaf
+weights; ops.gbdt_leaf_weights), and get_feature_importance gives CatBoost's "PredictionValuesChange" (also
+feature_importances_), exact path-dependent "ShapValues" (ops.gbdt_explain_plan, ops.gbdt_shap) and the
+SHAP-based "LossFunctionChange", in feature_names_ order. A model loaded from a file written before the
+weights existed needs calc_leaf_weights(X) first.
 """
 from __future__ import annotations
 
@@ -100,6 +107,7 @@ class _ObliviousBoosting:
         self.early_stopping_rounds, self.metric_period = early_stopping_rounds, int(metric_period)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model_, self._fitted_names = None, None
+        self.leaf_weights_, self._explain_plan = None, None
         self._no_ts()
         self.tree_count_ = 0
         self.evals_result_, self.best_iteration_, self.best_score_ = None, None, None
@@ -211,6 +219,7 @@ class _ObliviousBoosting:
         cannot train on. Returns (bins uint8 [F, R], y fp32 [R], is_cat uint8 [F], n_pos)."""
         dev = self.device
         self.model_, self._fitted_names = None, None
+        self.leaf_weights_, self._explain_plan = None, None
         num, cat, nums, cats = self._split_columns(X)
         Fn, Fc = len(nums), len(cats)
         F = Fn + Fc
@@ -319,6 +328,98 @@ class _ObliviousBoosting:
             raise ValueError(f"ntree_end must be in [0, {model.splits.shape[0]}] (got {ntree_end})")
         return ops.gbdt_predict(self._bins(X), model, ntree_end=ntree_end)
 
+    # ---- explanations ---------------------------------------------------------------------------------
+    def _count_leaves(self, bins):
+        """leaf_weights_ int64 [tree_count_, 64] = the rows of bins per leaf of the trees in use (no host read)."""
+        model = self._fitted()
+        self.leaf_weights_ = ops.gbdt_leaf_weights(bins, model)[:model.n_trees]
+        self._explain_plan = None
+
+    @torch.no_grad()
+    def calc_leaf_weights(self, X):
+        """Recompute leaf_weights_ from the rows X (as predict_logits takes them): what a model loaded from a
+        file without weights needs before it can explain itself, and a way to explain a model against other
+        rows than its training set. Returns self."""
+        self._count_leaves(self._bins(X))
+        return self
+
+    def _plan(self):
+        self._fitted()
+        if self.leaf_weights_ is None:
+            raise RuntimeError("the model has no leaf weights (it was loaded from a file written before they were "
+                               "saved): call calc_leaf_weights(X) first")
+        if self._explain_plan is None:
+            self._explain_plan = ops.gbdt_explain_plan(self.model_, self.leaf_weights_)
+        return self._explain_plan
+
+    def _name_order(self):
+        """The internal column (numeric, target-statistic, one-hot) of every entry of feature_names_."""
+        Fn, Fc = len(self._fitted_names[0]), len(self._fitted_names[1])
+        return list(range(Fn)) + self._cat_rows(Fn, Fc)
+
+    def _shap_of_bins(self, bins):
+        """ShapValues float64 [R, F + 1] of binned rows: the transposed view of ops.gbdt_shap's [F + 1, R] (of a
+        copy with the rows reordered where the model has target-statistic columns, whose internal order differs
+        from feature_names_')."""
+        phi = ops.gbdt_shap(bins, self.model_, self._plan())
+        order = self._name_order()
+        if order != list(range(len(order))):
+            phi = phi.index_select(0, torch.tensor(order + [len(order)], device=phi.device))
+        return phi.t()
+
+    @torch.no_grad()
+    def get_feature_importance(self, data=None, type="PredictionValuesChange", y=None, group_id=None):
+        """CatBoost's get_feature_importance, in feature_names_ order.
+        "PredictionValuesChange" (data not needed): a host float64 [F] summing to 100 (all zeros for a model
+            whose trees never change a prediction): per tree and level the cover-weighted squared differences of
+            the leaf pairs the level separates, from leaf_weights_; one host read, the per-feature sums formed on
+            the host in tree order.
+        "ShapValues": data (rows as predict_logits takes them) -> a device float64 [R, F + 1], exact
+            path-dependent Shapley values of the raw score with the expected value last; a row sums to its raw
+            score. No host read.
+        "LossFunctionChange": data, y (and group_id for a ranker) -> a host float64 [F]: metric(F - phi_j) -
+            metric(F) with the model's own loss (Logloss mean, QuerySoftMax), CatBoost's SHAP-based approximation;
+            positive = the feature helps. F + 1 evaluations on the device (ops.binary_eval /
+            ops.query_softmax_eval), fetched by one host read (a ranker's group plan reads the host once more).
+        RuntimeError without leaf weights (calc_leaf_weights)."""
+        model = self._fitted()
+        if type == "PredictionValuesChange":
+            plan = self._plan()
+            n, depth = model.n_trees, model.depth
+            host = torch.cat([plan.pvc[:n, :depth].reshape(-1),
+                              model.splits[:n, :depth, 0].reshape(-1).to(torch.float64)]).cpu().numpy()     # the one host read
+            pvc, feat = host[:n * depth], host[n * depth:].astype(np.int64)
+            F = len(self.feature_names_)
+            feat = np.where((feat < 0) | (feat >= F), 0, feat)
+            imp = np.zeros(F, np.float64)
+            for v, f in zip(pvc, feat):       # tree order, level by level
+                imp[f] += v
+            total = imp.sum()
+            imp = imp * (100.0 / total) if total > 0 else imp
+            return imp[self._name_order()]
+        if type not in ("ShapValues", "LossFunctionChange"):
+            raise ValueError(f'type must be "PredictionValuesChange", "ShapValues" or "LossFunctionChange" (got {type!r})')
+        if data is None:
+            raise ValueError(f"{type} needs data")
+        self._plan()
+        bins = self._bins(data)
+        phi = self._shap_of_bins(bins)
+        if type == "ShapValues":
+            return phi
+        if y is None:
+            raise ValueError("LossFunctionChange needs y")
+        R, F = phi.shape[0], phi.shape[1] - 1
+        y = torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).to(self.device, torch.float32).reshape(-1).contiguous()
+        if y.numel() != R:
+            raise ValueError(f"y holds {y.numel()} labels for {R} rows")
+        raw = ops.gbdt_predict(bins, model)
+        without = [(raw.double() - phi[:, j]).float() for j in range(F)]
+        return self._loss_change(raw, without, y, group_id)
+
+    @property
+    def feature_importances_(self):
+        return self.get_feature_importance()
+
     # ---- persistence -----------------------------------------------------------------------------------
     def save_model(self, path):
         """torch.save of the trees in use, the borders and the vocabularies, under the class's loss_function:
@@ -335,7 +436,7 @@ class _ObliviousBoosting:
                          "l2_leaf_reg": self.l2_leaf_reg, "border_count": self.border_count,
                          "cat_features": self.cat_features},
               "best_iteration": self.best_iteration_, "best_score": self.best_score_,
-              "evals_result": self.evals_result_}
+              "evals_result": self.evals_result_, "leaf_weights": cpu(self.leaf_weights_)}
         if self.ts_cols_:
             sd["format"] = "oblivious_gbdt/2"
             sd["params"].update(one_hot_max_size=self.one_hot_max_size, ts_prior=self.ts_prior, ts_seed=self.ts_seed)
@@ -368,6 +469,7 @@ class _ObliviousBoosting:
         self.feature_names_ = list(self._fitted_names[0]) + list(self._fitted_names[1])
         self.best_iteration_, self.best_score_, self.evals_result_ = sd["best_iteration"], sd["best_score"], sd["evals_result"]
         self.tree_count_ = self.model_.n_trees
+        self.leaf_weights_, self._explain_plan = to(sd.get("leaf_weights")), None      # None: a file from before the weights
         return self
 
 
@@ -391,8 +493,9 @@ class ObliviousBoostingClassifier(_ObliviousBoosting):
     numeric, TS, one-hot columns, each kind in the caller's order: the tie-break order. predict_logits on the
     training rows no longer equals the training approximant of such a model.
 
-    After fit: tree_count_, feature_names_, and with an eval_set evals_result_, best_iteration_ (the
-    0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
+    After fit: tree_count_, feature_names_, leaf_weights_ (int64 [tree_count_, 64] on the device: the training rows
+    per leaf, what get_feature_importance and feature_importances_ explain the model with), and with an eval_set
+    evals_result_, best_iteration_ (the 0-based index of the best tree) and best_score_, as DeepFM.fit fills them."""
 
     loss_function = "Logloss"
 
@@ -481,7 +584,15 @@ class ObliviousBoostingClassifier(_ObliviousBoosting):
         ops._GBDT_GUARD.watch(scratch.flag)      # a range error is reported by the next gbdt call, or by check()
         model.n_trees = self.best_iteration_ + 1 if (validate and use_best_model) else built
         self.tree_count_ = model.n_trees
+        self._count_leaves(bins)
         return self
+
+    def _loss_change(self, raw, without, y, group_id):
+        """LossFunctionChange: the Logloss mean of every score vector of `without` minus that of raw."""
+        R = raw.numel()
+        base = ops.binary_eval(raw, y)
+        _, sums = base.result(also=torch.cat([base.loss_sum] + [ops.binary_eval(z, y).loss_sum for z in without]))
+        return (np.asarray(sums[1:], np.float64) - sums[0]) / R
 
     def predict_proba(self, X) -> np.ndarray:
         """CatBoost's shape: [R, 2] = (1 - p, p) with p = sigmoid(raw score), a host array."""
@@ -615,7 +726,21 @@ class ObliviousBoostingRanker(_ObliviousBoosting):
         ops._GBDT_GUARD.watch(scratch.flag)      # a range error is reported by the next gbdt call, or by check()
         model.n_trees = self.best_iteration_ + 1 if (validate and use_best_model) else built
         self.tree_count_ = model.n_trees
+        self._count_leaves(bins)
         return self
+
+    def _loss_change(self, raw, without, y, group_id):
+        """LossFunctionChange: the QuerySoftMax of every score vector of `without` minus that of raw."""
+        if group_id is None:
+            raise ValueError("a ranker's LossFunctionChange needs group_id")
+        if len(group_id) != raw.numel():
+            raise ValueError(f"group_id has {len(group_id)} ids for {raw.numel()} rows")
+        plan = ops.GBDTGroupPlan(group_id, self.device)
+        yg = y.index_select(0, plan.order).contiguous()
+        evals = [ops.query_softmax_eval(z.index_select(0, plan.order).contiguous(), yg, plan) for z in [raw] + without]
+        host = torch.cat([e._buf for e in evals]).cpu()      # the one host read
+        loss = [ops.QuerySoftMaxEval._result(host[2 * i:2 * i + 2])["loss"] for i in range(len(evals))]
+        return np.asarray(loss[1:], np.float64) - loss[0]
 
     def predict(self, X, ntree_end=None):
         """The raw scores [R] (fp32 device tensor, the rows in X's order) after the first ntree_end trees

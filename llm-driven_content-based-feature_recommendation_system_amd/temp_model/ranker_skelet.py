@@ -628,6 +628,15 @@ class RecommendationRanker:
         self.model.load_model(path)
         self.is_fitted = True
 
+    def get_feature_importance(self, *args, **kwargs):
+        """The model's get_feature_importance: the native model's (oblivious_gbdt.py: "PredictionValuesChange",
+        "ShapValues" or "LossFunctionChange") or CatBoost's own."""
+        return self.model.get_feature_importance(*args, **kwargs)
+
+    @property
+    def feature_importances_(self):
+        return self.model.feature_importances_
+
     def predict_proba(self, X) -> np.ndarray:
         if self.loss_function == "QuerySoftMax":
             raise TypeError("a QuerySoftMax ranker scores, it has no probabilities: use predict")
@@ -745,6 +754,20 @@ class ReRankingSystem:
         top_p, top_j = torch.topk(prob.view(Q, K), final_k, dim=1)
         return torch.gather(cand_ids, 1, top_j), torch.gather(cand_scores, 1, top_j), top_p
 
+    @torch.no_grad()
+    def explain_batch(self, cand_ids: torch.Tensor, cand_scores: torch.Tensor, user_vectors: torch.Tensor, user_meta=None):
+        """Why the native tree ranker scores the candidates [Q, K] as it does: (SHAP values float64 [Q, K, F + 1] on
+        the device, the F column names followed by "expected_value"). The columns are the model's feature_names_,
+        the last entry the expected value, and a candidate's F + 1 entries sum to the raw score rerank_batch
+        ranks it by (the logit of its probability for a Logloss model). The bins are the very ones rerank_batch
+        scores; arguments as rerank_batch's native path."""
+        if not _is_native_ranker(self.ranker):
+            raise TypeError("explain_batch needs a native RecommendationRanker")
+        Q, K = cand_ids.shape
+        clf = self.ranker.model
+        phi = clf._shap_of_bins(self._tabular_bins(cand_ids, cand_scores, user_vectors, user_meta))
+        return phi.view(Q, K, -1), list(clf.feature_names_) + ["expected_value"]
+
     def recommend_batch(self, user_vectors: torch.Tensor, user_buckets: torch.Tensor = None,
                         top_k_retrieval: int = 100, final_k: int = 10, user_meta=None):
         """recommend (reference :170-237) for a batch of users with a DeepFM or a native
@@ -822,7 +845,9 @@ class ReRankingSystem:
         return cached
 
     @torch.no_grad()
-    def _rerank_tabular(self, cand_ids, cand_scores, user_vectors, user_meta, final_k):
+    def _tabular_bins(self, cand_ids, cand_scores, user_vectors, user_meta):
+        """The bins uint8 [F, Q K] of the candidates under the native ranker's model, in its internal column
+        order: what rerank_batch scores and explain_batch explains."""
         clf = self.ranker.model
         if clf.model_ is None:
             raise RuntimeError("the native ranker is not fitted")
@@ -855,6 +880,13 @@ class ReRankingSystem:
                 row.copy_(per_user.repeat_interleave(K))
             else:
                 row.zero_()
+        return bins
+
+    @torch.no_grad()
+    def _rerank_tabular(self, cand_ids, cand_scores, user_vectors, user_meta, final_k):
+        clf = self.ranker.model
+        Q, K = cand_ids.shape
+        bins = self._tabular_bins(cand_ids, cand_scores, user_vectors, user_meta)
         raw = ops.gbdt_predict(bins, clf.model_).view(Q, K)
         prob = raw if clf.loss_function == "QuerySoftMax" else torch.sigmoid(raw)      # a ranker's score is its raw score
         top_p, top_j = torch.topk(prob, final_k, dim=1)
